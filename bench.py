@@ -7,6 +7,10 @@ checkpoints offline).  N>1: one process per GPU (torchrun), rank 0 generates the
 over xGMI, every rank then denoises its own shard of 8 prompts with no per-step collective (weak scaling).
 
 Prints ONE JSON line (see the field notes in DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given, and prints the
+line. --full adds everything else the line can carry: the board clock / power sample (taken when --steps >= 20), the roofline
+pass, the CPU baseline and the parity legs (the last three each switched off by its own --no-* option).
 """
 import argparse
 import contextlib
@@ -54,6 +58,7 @@ WORKLOADS = {
 PARITY_CASES = ("sdxl_1x4x32x32_euler30", "sdxl_1x4x128x128_euler30")
 PEAK_BF16_TFLOPS = 2500.0  # dense MFMA bf16 / fp16, MI355X_MICROARCH.md chip table
 PEAK_FP8_TFLOPS = 5000.0   # dense MFMA fp8 (the W8A8 workload's block GEMMs)
+DUMP_BYTES = 64 * 10**6     # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -62,6 +67,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)    # 3 warm-up + >= 30 timed steps (one Euler schedule)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="sdxl-1024-bs8", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: board clock / power during the timed steps, "
+                         "the roofline pass, the CPU baseline and the parity legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (latents after the scheduler update, the "
+                         "model's noise prediction) as DIR/<name>.npy, float32; at most 64 MB in all (above that, a fixed seeded "
+                         "sample of the batch rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
@@ -235,7 +247,7 @@ def main():
         model = on_emulator(UNet2DConditionModel, cfg, P, device=dev, use_graph=not args.no_graph, **kw)
     else:
         model = UNet2DConditionModel(cfg, P, device=dev, use_graph=not args.no_graph, **kw)
-    P_cpu_needed = rank == 0 and not multi and not args.no_cpu_baseline and not cpu
+    P_cpu_needed = rank == 0 and not multi and args.full and not args.no_cpu_baseline and not cpu
     if not P_cpu_needed:
         del P
     if not cpu:
@@ -296,6 +308,7 @@ def main():
     stream = model._stream
     stream_ptr = model._stream_ptr
     lat0 = latents.clone()
+    last = {}   # the noise prediction of the latest step (--dump-outputs)
 
     def step(i):
         """one denoising step, everything stream-ordered on the model's stream"""
@@ -310,7 +323,7 @@ def main():
             sched._step_index = k
             scale = sched.model_input_scale(t)
             model.stage_inputs(plan, latents, float(t), enc, added, in_scale=scale)
-        eps = model.run(plan)
+        eps = last["noise_pred"] = model.run(plan)
         _lib.check(lib.mi355x_sd_axpby(latents.data_ptr(), eps.data_ptr(), latents.data_ptr(),
                                        coef_all.data_ptr() + 8 * k, latents.numel(), stream_ptr))
 
@@ -345,7 +358,7 @@ def main():
         for i in range(args.warmup):
             step(i)
         sync_all()
-        if rank == 0 and not cpu and args.steps >= 20:
+        if rank == 0 and not cpu and args.full and args.steps >= 20:
             import threading
             sampler = threading.Thread(target=sample_board, daemon=True)
             sampler.start()
@@ -371,6 +384,20 @@ def main():
             raise SystemExit("non-finite latents on some rank")
         if cpu and rank == 0:   # self-test: the ranks drew different prompts (per-rank seed) and the gather is rank-major
             assert torch.equal(allz[:B], latents) and (world == 1 or not torch.allclose(allz[:B], allz[B:2 * B]))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the updated latents (every rank's, rank-major, when the job
+        # has several) and the model's noise prediction (rank 0's), float32. Before the roofline pass, which reuses the output buffer.
+        # Above DUMP_BYTES in all (SD3 on 8 ranks: 72 MiB), every array keeps the same fixed, seeded, sorted sample of its batch rows.
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        outs = {"latents": allz if dist is not None else latents, "noise_pred": last["noise_pred"]}
+        total = sum(4 * t.numel() for t in outs.values())
+        for name, t in outs.items():
+            if total > DUMP_BYTES:
+                keep = max(1, t.shape[0] * DUMP_BYTES // total)
+                rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+                t = t[rows.to(t.device)]
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
 
     res = {
         "metric": {"sdxl-1024-bs8": "UNet denoising steps/sec (SD-XL 1024^2, bs=8)",
@@ -416,7 +443,7 @@ def main():
         res["parity_live_bs8"] = dict({k: v for k, v in fw.items() if k != "pred"}, fixture=fwd_name)
 
     # ---- roofline of the dominant kernel: per-launch HIP-event timing on the launch stream, one eager step ----
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         model.profile = True
         model.kernel_times.clear()
         with torch.cuda.stream(stream):
@@ -524,7 +551,8 @@ def main():
     #   "parity":      the benchmarked mode itself (a short loop only: its throughput is the line's `value`)
     #   "parity_mode": the CHEAPEST mode that meets north_star's 1e-3 on the end latents -- fp16 elements with the same 16-bit
     #                  residual stream and the same kernels as the headline (the other instantiation of the element typedef)
-    if rank == 0 and not multi and not cpu and not args.no_parity_mode and not args.parity_child and args.workload == "sdxl-1024-bs8":
+    parity_legs = rank == 0 and not multi and not cpu and args.full and not args.no_parity_mode and not args.parity_child
+    if parity_legs and args.workload == "sdxl-1024-bs8":
         import subprocess
 
         def parity_leg(dtype, residual, steps, warmup):
@@ -563,7 +591,7 @@ def main():
         if res["parity_mode"].get("meets_target"):
             res["value_meeting_target"] = {"steps_per_s": res["parity_mode"]["steps_per_s"], "dtype": res["parity_mode"]["dtype"],
                                            "residual": res["parity_mode"]["residual"]}
-    if rank == 0 and not multi and not cpu and not args.no_parity_mode and not args.parity_child and is_sd3:
+    if parity_legs and is_sd3:
         # SD3 lines: one whole-batch forward of the benchmarked mode at the benchmarked geometry (8x16x128x128, 4,250-key joint
         # attention) against the committed oracle forward -- for the fp8 modes the oracle on the same quantised operands
         # (tests/parity_cases.py FWD_CASES; per-prediction bars of tests/test_gpu_parity_loops.py). A child process on the fixtures'

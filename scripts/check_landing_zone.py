@@ -13,6 +13,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
@@ -20,10 +21,8 @@ BASE = 216
 REG = re.compile(r"\bv\[(\d+):(\d+)\]|\bv(\d+)\b")
 
 
-def code_objects(lib):
-    """the gfx950 code objects inside a fat library -> paths of extracted ELF files"""
-    tmp = os.path.join("/tmp", "landing_zone_" + os.path.basename(lib))
-    os.makedirs(tmp, exist_ok=True)
+def code_objects(lib, tmp):
+    """the gfx950 code objects inside a fat library -> paths of extracted ELF files (written under the directory `tmp`)"""
     subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o", f"--input={lib}"], capture_output=True)
     out = []
     # the device code sits in the .hip_fatbin section as an offload bundle; roc-obj-ls / clang-offload-bundler unpack it
@@ -106,8 +105,9 @@ def main():
             n_k, bad = check_disassembly(text, lib)
         else:
             text = ""
-            for co in code_objects(lib):
-                text += subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
+            with tempfile.TemporaryDirectory(prefix="landing_zone_") as tmp:   # private to this run: no clash with another user's
+                for co in code_objects(lib, tmp):
+                    text += subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
             n_k, bad = check_disassembly(text, os.path.basename(lib))
         fail |= bool(bad) or n_k == 0
     sys.exit(1 if fail else 0)

@@ -22,7 +22,7 @@ cat $O/${TAG}_gemm_timeline.txt
 : > $O/${TAG}_step_ab.txt
 run() {   # label, env assignments...
   local label=$1; shift
-  env "$@" timeout 90 python bench.py --no-cpu-baseline --no-parity-mode --steps 20 > /tmp/b.json 2>/tmp/b.err
+  env "$@" timeout 90 python bench.py --full --no-cpu-baseline --no-parity-mode --steps 20 > /tmp/b.json 2>/tmp/b.err
   python - "$label" >> $O/${TAG}_step_ab.txt <<'PY'
 import json,sys
 try:

@@ -133,6 +133,36 @@ def test_bench_single_process_prints_one_line_with_the_contract_fields():
     assert abs(r["value"] - 1e3 / r["ms_per_step"]) < 1e-6 * r["value"]
 
 
+def test_bench_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """`--dump-outputs DIR`: the last step's latents and noise prediction as float32 .npy files, the same from run to run with the
+    same arguments (seeded inputs), so two builds can be compared output for output. The dump follows the number of steps run
+    (`--warmup` + `--steps`, one continuous schedule) and is the LAST step's: 3 + 1 and 2 + 2 steps give the same files, 4 + 1
+    steps give other latents and another prediction -- so `--steps` really adds timed steps, and the dump is taken after them."""
+    import json
+    import subprocess
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+
+    def run(tag, steps, warmup):
+        d = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--selftest-cpu",
+                            "--dump-outputs", str(d)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert r["steps"] == steps and r["warmup"] == warmup and r["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["latents.npy", "noise_pred.npy"]
+        return {n: np.load(d / (n + ".npy")) for n in ("latents", "noise_pred")}
+
+    a, b, same_total, longer = run("a", 3, 1), run("b", 3, 1), run("c", 2, 2), run("d", 4, 1)
+    for n, x in a.items():
+        assert x.dtype == np.float32 and x.shape == (2, 4, 8, 8) and np.isfinite(x).all(), n
+        assert np.array_equal(x, b[n]), n                 # same arguments: same outputs
+        assert np.array_equal(x, same_total[n]), n        # same number of steps in all: same last step
+        assert not np.array_equal(x, longer[n]), n        # one timed step more: another last step
+    assert not np.array_equal(a["latents"], a["noise_pred"])
+
+
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
     import subprocess
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
