@@ -26,6 +26,7 @@
 // address. Out-of-range chunks (M/N/K tails, the conv zero padding) are sourced from 16 zero bytes.
 // The MFMA is issued "swapped" (W as the row operand) so every lane ends up with 4 consecutive output channels
 // of one row -> 8-byte stores, and the GEGLU value/gate pair of a channel sits in one lane.
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -326,7 +327,7 @@ static int pick_tile(const GemmArgs& a) {
   // (N = 640 / 1280: to_q / to_out / FF2 with their residuals) was built and LOST in the step: 57.10 / 56.71 / 56.96 vs 56.40 / 55.91 /
   // 56.15 ms, three interleaved rounds (profiles/r06_s24_step_ab.txt) -- one tile per CU there: prologue and epilogue dominate, and two
   // waves per SIMD overlap them where one cannot. It stays selectable (MI355X_SD_GEMM_TILE=259 or MI355X_SD_GEMM_TILE_MAP="160:259",
-  // debug build) and bit-identical to the generic loop (tests/test_gpu_gemm_variants.py).
+  // debug build) and bit-identical to the generic loop (tests/test_gpu_gemm_w4.py: the generic 256 x 256 loop, MI355X_SD_NO_W4).
   // The small launches of a batch-1 step (<= 128 tiles of 128 x 128, K <= 2560: what used to take split-K slices + a reduce kernel)
   // take the 64 x 64 tile with the six-stage ring (gemm_small.hip, id 64). MI355X_SD_NO_SMALL (debug build): the round-5 path.
   static const bool small_off = sd_switch("MI355X_SD_NO_SMALL") != nullptr;
@@ -424,7 +425,25 @@ static bool widen_fp8_applies(const GemmArgs& a) {
   return tiles > 128 && a.M >= min_m;
 }
 
-int launch_gemm(const GemmArgs& a_in, hipStream_t stream) {
+// The route of a launch, for MI355X_SD_GEMM_LOG (debug build): fam (when not null) receives the kernel family that ran --
+// small, w4/256 | w4/160 (+ex, +ws), pipe/<tile>, gemm256, generic/<cfg> (+f8, +ln), and +splitk where the K range was sliced.
+static int dispatch_gemm(const GemmArgs& a_in, hipStream_t stream, char* fam);
+
+int launch_gemm(const GemmArgs& a, hipStream_t stream) {
+  // MI355X_SD_GEMM_LOG=<path> appends "M N K family" per launch (tests/gemm_w4_child.py: each case reached the kernel it is named for)
+  static FILE* const log = [] {
+    const char* e = sd_switch("MI355X_SD_GEMM_LOG");
+    return e ? fopen(e, "a") : nullptr;
+  }();
+  if (!log) return dispatch_gemm(a, stream, nullptr);
+  char fam[48] = "rejected";
+  const int rc = dispatch_gemm(a, stream, fam);
+  fprintf(log, "%d %d %d %s\n", a.M, a.N, a.K, fam);
+  fflush(log);
+  return rc;
+}
+
+static int dispatch_gemm(const GemmArgs& a_in, hipStream_t stream, char* fam) {
   if (widen_fp8_applies(a_in)) {
     const long n16 = (long)a_in.N * a_in.K / 16;   // (K % 64 == 0)
     // (grid: every lane four loads where the matrix is large enough to still give each CU two blocks)
@@ -434,7 +453,7 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t stream) {
     GemmArgs b = a_in;
     b.W = reinterpret_cast<const bf16*>(a_in.ws_base);
     b.w16 = 1;
-    return launch_gemm(b, stream);
+    return dispatch_gemm(b, stream, fam);
   }
   GemmArgs a = a_in;
   a.splitk = 0;
@@ -462,15 +481,23 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t stream) {
   static const bool epi_batch_off = sd_switch("MI355X_SD_GEMM_NO_EPI_BATCH") != nullptr;   // A/B switch (gemm_epilogue.h)
   a.epi_batch = epi_batch_off ? 0 : 1;
   a.bias_acc = 0;   // launch_gemm_pipe decides
+  auto routed = [&](const char* f, int tile_id, int rc, const char* kind = "") {
+    if (fam && tile_id) snprintf(fam, 48, "%s/%d%s%s", f, tile_id, kind, a.splitk > 1 ? "+splitk" : "");
+    else if (fam) snprintf(fam, 48, "%s%s%s", f, kind, a.splitk > 1 ? "+splitk" : "");
+    return rc;
+  };
   int tile = pick_tile(a);
   if (tile == 64) {    // 64 x 64 tile, six-stage ring (gemm_small.hip), else the 128 x 128 tiles (with split-K slices)
     const int rc = launch_gemm_small(a, stream);
-    if (rc != SD_ERR_UNSUPPORTED) return rc;
+    if (rc != SD_ERR_UNSUPPORTED) return routed("small", 0, rc);
     tile = 128;
   }
   if (tile == 258 || tile == 259) {   // four-wave 256 x 256 / 256 x 160 tile (gemm_w4.hip) where it applies, else the model's choice among the others
     const int rc = launch_gemm_w4(a, stream, tile == 258 ? 256 : 160);
-    if (rc != SD_ERR_UNSUPPORTED) return rc;
+    if (rc != SD_ERR_UNSUPPORTED) {
+      if (fam) snprintf(fam, 48, "w4/%d%s%s", tile == 258 ? 256 : 160, (a.R || a.gate || a.a_rpb || a.c_rpb) ? "+ex" : "", a.wscale ? "+ws" : "");
+      return rc;
+    }
     tile = pick_tile_model(a);
   }
   // Column groups by tile width (round 4). An XCD runs 32 consecutive tile ids per round = 32/g row-tiles x g column-tiles; what
@@ -484,31 +511,33 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t stream) {
     return SD_ERR_UNSUPPORTED;
   {   // software-pipelined loop (gemm_pipe.hip) where it applies (128 / 160 tiles; 256 only as an experiment)
     const int rc = launch_gemm_pipe(a, tile, stream);
-    if (rc != SD_ERR_UNSUPPORTED) return rc;
+    if (rc != SD_ERR_UNSUPPORTED) return routed("pipe", tile, rc);
   }
   if (a.rowstat) {   // LayerNorm-folded projection: own kernel instantiations (epilogue in gemm_epilogue_ln)
-    if (tile == 257 && !(a.K & 63)) return launch_gemm256(a, stream);
-    if (tile == 256 || tile == 257) return launch_cfg<false, Cfg256, false, true>(a, stream);
-    if (tile == 160 && !a.geglu) return launch_cfg<false, Cfg256x160, false, true>(a, stream);
-    if (tile == 320) return a.geglu ? launch_cfg<false, Cfg256x320g, false, true>(a, stream)
-                                    : launch_cfg<false, Cfg256x320, false, true>(a, stream);
-    return launch_cfg<false, Cfg128, false, true>(a, stream);
+    if (tile == 257 && !(a.K & 63)) return routed("gemm256", 0, launch_gemm256(a, stream), "+ln");
+    if (tile == 256 || tile == 257) return routed("generic", 256, launch_cfg<false, Cfg256, false, true>(a, stream), "+ln");
+    if (tile == 160 && !a.geglu) return routed("generic", 160, launch_cfg<false, Cfg256x160, false, true>(a, stream), "+ln");
+    if (tile == 320) return routed("generic", 320, a.geglu ? launch_cfg<false, Cfg256x320g, false, true>(a, stream)
+                                                              : launch_cfg<false, Cfg256x320, false, true>(a, stream), "+ln");
+    return routed("generic", 128, launch_cfg<false, Cfg128, false, true>(a, stream), "+ln");
   }
   if (w_is_f8(a)) {   // fp8 weight bytes read by the kernel: generic configurations only
     if (a.conv || (a.K & 15)) return SD_ERR_UNSUPPORTED;
-    if (tile == 160 && !a.geglu) return launch_cfg<false, Cfg256x160, true>(a, stream);
-    if (tile == 320) return a.geglu ? launch_cfg<false, Cfg256x320g, true>(a, stream) : launch_cfg<false, Cfg256x320, true>(a, stream);
-    if (tile == 256 || tile == 257) return launch_cfg<false, Cfg256, true>(a, stream);
-    return launch_cfg<false, Cfg128, true>(a, stream);
+    if (tile == 160 && !a.geglu) return routed("generic", 160, launch_cfg<false, Cfg256x160, true>(a, stream), "+f8");
+    if (tile == 320)
+      return routed("generic", 320, a.geglu ? launch_cfg<false, Cfg256x320g, true>(a, stream) : launch_cfg<false, Cfg256x320, true>(a, stream), "+f8");
+    if (tile == 256 || tile == 257) return routed("generic", 256, launch_cfg<false, Cfg256, true>(a, stream), "+f8");
+    return routed("generic", 128, launch_cfg<false, Cfg128, true>(a, stream), "+f8");
   }
-  if (tile == 257 && !((a.K & 63) || (a.conv && (a.Cin & 63)) || a.a_rpb)) return launch_gemm256(a, stream);
-  if (tile == 256 || tile == 257) return a.conv ? launch_cfg<true, Cfg256>(a, stream) : launch_cfg<false, Cfg256>(a, stream);
+  if (tile == 257 && !((a.K & 63) || (a.conv && (a.Cin & 63)) || a.a_rpb)) return routed("gemm256", 0, launch_gemm256(a, stream));
+  if (tile == 256 || tile == 257)
+    return routed("generic", 256, a.conv ? launch_cfg<true, Cfg256>(a, stream) : launch_cfg<false, Cfg256>(a, stream));
   if (tile == 160 && !a.geglu)
-    return a.conv ? launch_cfg<true, Cfg256x160>(a, stream) : launch_cfg<false, Cfg256x160>(a, stream);
+    return routed("generic", 160, a.conv ? launch_cfg<true, Cfg256x160>(a, stream) : launch_cfg<false, Cfg256x160>(a, stream));
   if (tile == 320 && !a.geglu)
-    return a.conv ? launch_cfg<true, Cfg256x320>(a, stream) : launch_cfg<false, Cfg256x320>(a, stream);
-  if (tile == 320 && !a.conv) return launch_cfg<false, Cfg256x320g>(a, stream);
-  return a.conv ? launch_cfg<true, Cfg128>(a, stream) : launch_cfg<false, Cfg128>(a, stream);
+    return routed("generic", 320, a.conv ? launch_cfg<true, Cfg256x320>(a, stream) : launch_cfg<false, Cfg256x320>(a, stream));
+  if (tile == 320 && !a.conv) return routed("generic", 320, launch_cfg<false, Cfg256x320g>(a, stream));
+  return routed("generic", 128, a.conv ? launch_cfg<true, Cfg128>(a, stream) : launch_cfg<false, Cfg128>(a, stream));
 }
 
 }  // namespace sd

@@ -203,7 +203,8 @@ __device__ __forceinline__ void w4_epilogue_ex(const GemmArgs& p, f32x4 (&acc)[T
         const int n = n_wave + h * 32 + lq * 8;
         if (n >= p.N) continue;
         f32x4 a0 = acc[2 * h][tm], a1 = acc[2 * h + 1][tm];
-        if constexpr (WS) {   // (the order of gemm_epilogue.h epi4: scale, bias, gate -- bit-identical to the other kernels)
+        if constexpr (WS) {   // (the order of gemm_epilogue.h epi4: scale, bias, gate; scale and bias contract to ONE fma here, where
+                              // epi4 rounds the product first: one fp32 rounding apart, tests/test_gpu_gemm_w4.py WS_NOTE)
           a0 *= ws[2 * h];
           a1 *= ws[2 * h + 1];
         }

@@ -1,0 +1,122 @@
+"""Elementwise float64 error bound for the GEMM kernels (csrc/gemm*.hip): every output element is held to a bound derived from the
+kernel's arithmetic, against a float64 reference computed from the exact 16-bit operands. Plain Python + torch; runs on whatever
+device the tensors live on.
+
+Derivation. A kernel multiplies 16-bit operands exactly (a bf16 / fp16 product fits in fp32) and sums them in fp32: a 32-deep
+v_mfma_f32_16x16x32 step adds 32 products to its accumulator, K / 32 such steps chain. With unit roundoff u32 = 2^-24 and at most
+K / 32 + 32 roundings on any product's way into the sum (the chain plus the inside of one MFMA step), the accumulator satisfies
+
+    |acc - sum_k a_k w_k| <= gamma_K * sum_k |a_k w_k|,      gamma_K = (K / 32 + 32) * 2^-24
+
+and sum_k |a_k w_k| is one float64 |A| @ |W|^T. Weight-only fp8 (WS) runs on the widened matrix: acc = A . Q^T then * scale, so the
+same bound holds with W = dequantize_fp8_rows(Q, scale) (the scale is positive).
+
+Epilogue, in fp32, the order of gemm_epilogue.h epi4: z = ((acc + bias) * gate + R) * out_scale. Bias, gate and out_scale are
+linear, so the accumulator error arrives at z multiplied by |gate * out_scale|. The epilogue's own fp32 roundings (bias add, gate
+multiply, residual add, scale: at most EPI_OPS of them) add EPI_OPS * 2^-24 times the magnitudes they act on,
+(|acc| + |bias|) |gate| + |R|, times |out_scale|. The residual R is a 16-bit tensor read exactly, so its only error is that add.
+
+    e_z = |out_scale| * ( |gate| gamma_K S + EPI_OPS 2^-24 ((|acc| + |bias|) |gate| + |R|) )
+
+Activations: out = f(z) with |f(z + e) - f(z)| <= L_f |e|, L_f the maximum slope of f over R (SiLU 1.0999 -> 1.10; erf-GELU 1.1289
+and tanh-GELU 1.1295 -> 1.13), plus the device form's own approximation error as a stated constant:
+  * SiLU and tanh-GELU are x * sigmoid(.) with v_exp_f32 / v_rcp_f32 (a few fp32 ulps): ACT_REL = 2^-20 relative to |z|;
+  * erf-GELU (GEGLU's gate) is x * sigmoid(p(x)) with p a fitted quintic, 2.6e-5 absolute on Phi (common.h gelu_erf_f):
+    GELU_ERF_ABS = 3e-5 times max(|g|, 1).
+GEGLU pairs a value h and a gate g: out = h * gelu(g), so
+    e_out = |gelu(g)| e_h + (|h| + e_h) (1.13 e_g + GELU_ERF_ABS max(|g|, 1)).
+
+Finally the 16-bit store rounds once: |fl(y) - y| <= u |y| with u = 2^-8 for bf16 (8 significand bits) and 2^-11 for fp16. The
+bound takes u_out = 2 u -- 2^-7 for bf16, 2^-10 for fp16 -- so that a correct kernel sits at or below half of it; the kernel's y
+is itself off by e, hence
+
+    |out - ref| <= u_out |ref| + (1 + u_out) e + 2^-24         (the last term: fp16's subnormal spacing)
+
+check() returns the worst |out - ref| / bound over the WHOLE output (the margin the logs show; a correct kernel stays below ~0.5, a
+wrong sub-tile or a doubled bias lands far above 1) and the rel-L2 of the same comparison.
+"""
+import torch
+
+U_OUT = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10}
+U32 = 2.0 ** -24
+EPI_OPS = 4
+SLOPE = {"silu": 1.10, "gelu_tanh": 1.13, "gelu_erf": 1.13}
+ACT_REL = 2.0 ** -20
+GELU_ERF_ABS = 3e-5
+
+
+def gamma(K: int) -> float:
+    """fp32 accumulation error factor of a K-deep sum in chains of 16x16x32 MFMAs"""
+    return (K / 32 + 32) * U32
+
+
+def _act(name, z):
+    if name == "silu":
+        return z * torch.sigmoid(z)
+    if name == "gelu_tanh":
+        return torch.nn.functional.gelu(z, approximate="tanh")
+    if name == "gelu_erf":
+        return torch.nn.functional.gelu(z)
+    raise ValueError(name)
+
+
+def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=False, gate=None, rows_per_batch=0,
+              residual=None):
+    """float64 reference and elementwise accumulator-side error e (before the output rounding) of
+    out = act(((a @ w^T) * w_scale + bias) * gate[m // rows_per_batch] + residual) * out_scale ..., or the GEGLU form.
+    a [M, K], w [N, K] (for WS: the dequantized weights, w_scale None), bias [N], gate [batches, N], residual [M, N]: the
+    logical operands exactly as the kernel reads them."""
+    M, K = a.shape
+    A, W = a.double(), w.double()
+    acc = A @ W.t()
+    e = gamma(K) * (A.abs() @ W.abs().t())
+    del A, W
+    if w_scale is not None:   # (callers pass dequantized weights instead; kept for completeness)
+        acc = acc * w_scale.double()
+        e = e * w_scale.double().abs()
+    b = bias.double() if bias is not None else torch.zeros(acc.shape[1], dtype=torch.float64, device=acc.device)
+    mag = acc.abs() + b.abs()
+    z = acc + b
+    del acc
+    if gate is not None:
+        g = gate.double()[torch.arange(M, device=z.device) // rows_per_batch]
+        z, e, mag = z * g, e * g.abs(), mag * g.abs()
+        del g
+    if residual is not None:
+        r = residual.double()
+        z, mag = z + r, mag + r.abs()
+        del r
+    e = abs(out_scale) * (e + EPI_OPS * U32 * mag)
+    z = z * out_scale
+    del mag
+    if geglu:
+        N = z.shape[1]
+        zz, ee = z.reshape(M, N // 32, 2, 16), e.reshape(M, N // 32, 2, 16)
+        h, g, eh, eg = zz[:, :, 0], zz[:, :, 1], ee[:, :, 0], ee[:, :, 1]
+        gg = _act("gelu_erf", g)
+        ref = (h * gg).reshape(M, N // 2)
+        e = (gg.abs() * eh + (h.abs() + eh) * (SLOPE["gelu_erf"] * eg + GELU_ERF_ABS * g.abs().clamp_min(1.0))).reshape(M, N // 2)
+        return ref, e
+    if act is not None:
+        e = SLOPE[act] * e + ACT_REL * z.abs()
+        z = _act(act, z)
+    return z, e
+
+
+def check(out, ref, e):
+    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit output against reference() (non-finite -> inf)"""
+    u = U_OUT[out.dtype]
+    o = out.double()
+    err = (o - ref).abs()
+    bound = u * ref.abs() + (1 + u) * e + U32
+    ratio = (err / bound).max().item()
+    if not torch.isfinite(o).all() or ratio != ratio:
+        ratio = float("inf")
+    rel = ((o - ref).norm() / ref.norm()).item()
+    return ratio, rel
+
+
+def bound_check(out, a, w, **kw):
+    """reference() + check() in one call: (worst err / bound, rel-L2)"""
+    ref, e = reference(a, w, **kw)
+    return check(out, ref, e)

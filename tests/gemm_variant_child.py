@@ -14,7 +14,26 @@ from paddlemix_amd import _lib, ops  # noqa: E402
 
 ops.init(0)
 ed = _lib.elem_dtype()
-res = {}
+_log = os.environ.get("MI355X_SD_GEMM_LOG")   # (debug build: launch_gemm appends "M N K family" per launch)
+_log_pos = [0]
+
+
+def _routes():
+    if not _log or not os.path.exists(_log):
+        return []
+    with open(_log) as f:
+        f.seek(_log_pos[0])
+        lines = f.read().splitlines()
+        _log_pos[0] = f.tell()
+    return lines
+
+
+class _Res(dict):   # each case's entry also lists the kernel families its launches took (the lines logged since the last case)
+    def __setitem__(self, k, v):
+        super().__setitem__(k, dict(v, route=_routes()))
+
+
+res = _Res()
 # the 256x160 three-stage tile (N = 1280 column tiles) with K on both sides of the loader-wave threshold, ragged M, residual
 for M, N, K, resid in ((8192, 1280, 5120, True), (1000, 1280, 4096, False), (8192, 1280, 1280, True), (777, 2560, 8192, False)):
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
@@ -102,8 +121,10 @@ for B, H, W, Cin, Cout in ((8, 32, 32, 1280, 1280), (2, 30, 34, 640, 1280)):    
     res[f"conv {B}x{H}x{W}x{Cin}->{Cout}"] = dict(
         sha=hashlib.sha256(out.cpu().view(torch.int16).numpy().tobytes()).hexdigest()[:16],
         rel=((out[:H * W].float() - ref).norm() / ref.norm()).item())
-# wide launches without per-row operands (what the four-wave 256 x 256 tile of csrc/gemm_w4.hip takes, round 6): one K-tile (its
-# prologue + last iteration alone), two, an odd count; ragged M and N; SiLU; fewer tiles than CUs and several rounds of persistent blocks
+# wide launches without per-row operands (the shapes of the picker's four-wave 256 x 256 tile, csrc/gemm_w4.hip, round 6): one K-tile
+# and two (the generic loops' prologue + last iteration alone: the four-wave tile needs three K-tiles and refuses these -- its own
+# K = 192 / 256 / 320 cases are in tests/gemm_w4_child.py), an odd count; ragged M and N; SiLU; fewer tiles than CUs and several rounds
+# of persistent blocks
 for M, N, K, kind in ((1000, 1288, 64, "plain"), (515, 1928, 128, "silu"), (3000, 3840, 1280, "plain"), (8192, 3840, 1280, "nobias"),
                       (33000, 1536, 1536, "plain"), (700, 2048, 320, "plain")):
     g = torch.Generator(device="cuda").manual_seed(M + N + K + 5)

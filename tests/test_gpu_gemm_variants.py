@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -13,6 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 _CACHE = {}
+W4_REF = {"MI355X_SD_GEMM_TILE": "256", "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_NO_BIAS_ACC": "1", "MI355X_SD_NO_SPLITK": "1",
+          "MI355X_SD_NO_W4": "1"}
 
 
 def _bar(key):   # rel-L2 of a case against its fp32 reference (16-bit stores)
@@ -27,9 +30,10 @@ def _run(env_extra):
 
 
 def _run_child(env_extra):
-    env = dict(os.environ, MI355X_SD_LIB="dbg", **env_extra)   # the A/B switches exist in the debug-switch build only
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gemm_variant_child.py")], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=600)
+    with tempfile.TemporaryDirectory() as td:   # (MI355X_SD_GEMM_LOG: the kernel family of every launch, reported per case)
+        env = dict(os.environ, MI355X_SD_LIB="dbg", MI355X_SD_GEMM_LOG=os.path.join(td, "gemm.log"), **env_extra)   # the A/B switches exist in the debug-switch build only
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gemm_variant_child.py")], env=env, cwd=ROOT, capture_output=True,
+                           text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("VARIANT_JSON ")][-1][len("VARIANT_JSON "):])
 
@@ -95,6 +99,24 @@ def test_pipelined_loops_are_bit_identical_to_the_generic_loop(tile_env):
     The same comparison held the interleaved loop to the round-3 burst loop before that was deleted (profiles/r04_s2_tests.txt)."""
     ref = _run(dict(tile_env, MI355X_SD_NO_PIPE="1", MI355X_SD_GEMM_NO_BIAS_ACC="1"))
     new = _run(dict(tile_env, MI355X_SD_GEMM_NO_BIAS_ACC="1"))
+    # MI355X_SD_NO_PIPE does not reach the four-wave tile (launch_gemm takes it before the pipelined loops, and a forced tile returns
+    # from pick_tile before MI355X_SD_NO_W4 is read): the launches that ran it (route log) are held to the generic 256 x 256 loop with
+    # the four-wave tile off instead -- the same K order, the bias after the sum (tests/test_gpu_gemm_w4.py has its own case matrix)
+    w4_ref = _run(W4_REF)
+    w4 = [k for k, v in new.items() if any(r.split()[-1].startswith("w4/") for r in v["route"])]
+    if tile_env.get("MI355X_SD_GEMM_TILE") in ("258", "259") or not tile_env:
+        assert w4, (tile_env, "no launch reached the four-wave tile")
     for k, v in new.items():
         assert v["rel"] < _bar(k), (tile_env, k, v)
-        assert v["sha"] == ref[k]["sha"], (tile_env, k, v, ref[k])
+        if k in w4 and any(r.split()[-1].endswith("+ws") for r in v["route"]):
+            # (widened e4m3: the four-wave epilogue fuses scale and bias into one FMA where the generic loop rounds twice --
+            # tests/test_gpu_gemm_w4.py WS_NOTE -- so the four-wave tile of the other width is the bit-exact reference)
+            other = _run({"MI355X_SD_GEMM_TILE": "258" if tile_env.get("MI355X_SD_GEMM_TILE") == "259" else "259",
+                          "MI355X_SD_GEMM_NO_BIAS_ACC": "1"})
+            if any(r.split()[-1].startswith("w4/") for r in other[k]["route"]):
+                assert v["sha"] == other[k]["sha"], (tile_env, k, v, other[k])
+        elif k in w4:
+            assert not any(r.split()[-1].startswith("w4/") for r in w4_ref[k]["route"]), (k, w4_ref[k]["route"])
+            assert v["sha"] == w4_ref[k]["sha"], (tile_env, k, v, w4_ref[k])
+        else:
+            assert v["sha"] == ref[k]["sha"], (tile_env, k, v, ref[k])
