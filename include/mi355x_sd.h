@@ -295,6 +295,7 @@ int mi355x_sd_conv3x3(const void* X, int ldx, int B, int Hs, int Ws, int Cin, in
 /* out = softmax(q k^T * scale + bias) v, layouts q [B,Sq,H,D], k/v [B,Skv,H,D], out [B,Sq,H,D] with explicit
  * batch (bs) and token (ts) strides in elements; bias optional fp32 additive mask addressed
  * b*bias_bs + h*bias_hs + q*bias_qs + kv (0 strides broadcast).  D % 8 == 0, D <= 160.
+ * A query row whose keys are ALL masked with -inf has no softmax: its output row is 0 (torch's sdpa gives NaN there).
  * Replaces scaled_dot_product_attention_ (PPD/patches/paddle_patch.py:414-529) and the body of
  * AttnProcessor.__call__ / get_attention_scores (PPD/models/attention_processor.py:673-735, 552-586). */
 int mi355x_sd_sdpa(const void* q, const void* k, const void* v, const float* bias, void* out,

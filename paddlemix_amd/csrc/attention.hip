@@ -15,6 +15,7 @@
 //   * O^T = V^T P^T: P (bf16) is consumed straight from those registers as the MFMA B operand; the matching
 //     V^T A operand comes from ds_read_b64_tr_b16 transpose reads of the row-major V tile;
 //   * K rows padded by 16 B and V rows to a stride == 64 (mod 256) B so both fragment reads are bank-conflict free.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -24,7 +25,6 @@
 
 namespace sd {
 
-constexpr int ATTN_LAZY_DEFAULT = 1;
 // Lazy-maximum guard (FL bit 0): a lane's partial row sum of the freshly exponentiated tile must stay below this, else the tile
 // is redone the exact way. Every P value of the lane is <= that sum, and P is stored in the build's 16-bit type: bf16 shares
 // fp32's exponent range (any finite value converts), IEEE half tops out at 65504 -- a score more than ~16 log2 units above the
@@ -850,14 +850,18 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_short_kernel(const A
   }
 }
 
-// lazy row maximum (on: profiles/r02_attention.txt)
-static bool attn_lazy() { return ATTN_LAZY_DEFAULT != 0; }
+// The route of a launch, for MI355X_SD_ATTN_LOG (debug build): fam (when not null) receives the kernel family that ran --
+// short/<NSB>, flash64/qt2, m16, flash64+lazy, flash64+bias, flash96, flash160 (+log2, +wide, +bias where they apply).
+static void attn_route(char* fam, const char* name) {
+  if (fam) snprintf(fam, 48, "%s", name);
+}
 
 template <int DP>
-static int launch_dp(const AttnArgs& a0, hipStream_t stream) {
+static int launch_dp(const AttnArgs& a0, hipStream_t stream, char* fam) {
   const AttnArgs& a = a0;
-  // lazy only where it costs no occupancy step: the d <= 64 kernel without mask (158 / 168 VGPRs: still 3 waves per SIMD)
-  const bool lazy = DP == 64 && !a.bias && (attn_lazy() || a.log2);
+  // lazy row maximum (profiles/r02_attention.txt) only where it costs no occupancy step: the d <= 64 kernel without mask (158 / 168
+  // VGPRs: still 3 waves per SIMD). It is always on there: the d <= 64 flash kernel has no eager unmasked form.
+  const bool lazy = DP == 64 && !a.bias;
   if (a.log2 && (DP != 64 || a.bias)) return SD_ERR_UNSUPPORTED;
   // short KV (both tiles stay resident in the two LDS buffers) and enough query tiles to keep every CU busy: two query
   // tiles per block
@@ -879,6 +883,7 @@ static int launch_dp(const AttnArgs& a0, hipStream_t stream) {
       if (a.log2) hipLaunchKernelGGL((attention_short_kernel<N, true>), grid, block, 0, stream, a, qtpb);              \
       else hipLaunchKernelGGL((attention_short_kernel<N, false>), grid, block, 0, stream, a, qtpb);                    \
     } while (0)
+    if (fam) snprintf(fam, 48, "short/%d%s", nsb, a.log2 ? "+log2" : "");
     if (nsb == 1) SD_SHORT(1);
     else if (nsb == 2) SD_SHORT(2);
     else if (nsb == 3) SD_SHORT(3);
@@ -894,6 +899,7 @@ static int launch_dp(const AttnArgs& a0, hipStream_t stream) {
     const int nqb = (a.Sq + QBLK * QT - 1) / (QBLK * QT);
     dim3 grid(nqb * a.B * a.H), block(ATT_THREADS);
     // (the two-query-tile kernel keeps the exact maximum: lazy would cost it an occupancy step, 168 -> 199 VGPRs)
+    attn_route(fam, a.log2 ? "flash64/qt2+log2" : "flash64/qt2");
     if (DP == 64 && a.log2) hipLaunchKernelGGL((attention_kernel<DP, false, Q, (DP == 64 ? 3 : 0)>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((attention_kernel<DP, false, Q, 0>), grid, block, 0, stream, a);
     return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
@@ -909,38 +915,63 @@ static int launch_dp(const AttnArgs& a0, hipStream_t stream) {
 #ifdef MI355X_SD_DEBUG_SWITCHES
     static const bool stamp = sd_switch("MI355X_SD_ATTN_STAMP") != nullptr;
     if (stamp && a.log2) {
+      attn_route(fam, "m16+log2+stamp");
       hipLaunchKernelGGL((attention16_kernel<true, true>), grid, block, 0, stream, a);
       return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
     }
 #endif
+    attn_route(fam, a.log2 ? "m16+log2" : "m16");
     if (a.log2) hipLaunchKernelGGL((attention16_kernel<true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((attention16_kernel<false>), grid, block, 0, stream, a);
     return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
   }
+  constexpr const char* flash = DP == 64 ? "flash64" : DP == 96 ? "flash96" : "flash160";
   if (a.bias) {
+    if (fam) snprintf(fam, 48, "%s+bias", flash);
     hipLaunchKernelGGL((attention_kernel<DP, true, 1, 0>), grid, block, 0, stream, a);
-  } else if (DP == 64 && a.log2) {
-    if (wide) hipLaunchKernelGGL((attention_kernel<DP, false, 1, (DP == 64 ? 7 : 0)>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((attention_kernel<DP, false, 1, (DP == 64 ? 3 : 0)>), grid, block, 0, stream, a);
-  } else if (lazy) {
-    if (wide) hipLaunchKernelGGL((attention_kernel<DP, false, 1, (DP == 64 ? 5 : 0)>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((attention_kernel<DP, false, 1, (DP == 64 ? 1 : 0)>), grid, block, 0, stream, a);
+  } else if constexpr (DP == 64) {   // (lazy: see above)
+    if (fam) snprintf(fam, 48, "flash64+%s%s", a.log2 ? "log2" : "lazy", wide ? "+wide" : "");
+    if (a.log2) {
+      if (wide) hipLaunchKernelGGL((attention_kernel<DP, false, 1, 7>), grid, block, 0, stream, a);
+      else hipLaunchKernelGGL((attention_kernel<DP, false, 1, 3>), grid, block, 0, stream, a);
+    } else {
+      if (wide) hipLaunchKernelGGL((attention_kernel<DP, false, 1, 5>), grid, block, 0, stream, a);
+      else hipLaunchKernelGGL((attention_kernel<DP, false, 1, 1>), grid, block, 0, stream, a);
+    }
   } else {
+    attn_route(fam, flash);
     hipLaunchKernelGGL((attention_kernel<DP, false, 1, 0>), grid, block, 0, stream, a);
   }
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
+static int dispatch_attention(const AttnArgs& a, hipStream_t stream, char* fam);
+
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
+  // MI355X_SD_ATTN_LOG=<path> appends "B H Sq Skv D family" per launch (tests/attn_child.py: each case reached the kernel it is named
+  // for; tests/test_gpu_attention.py: every instantiation launch_dp can launch is reached)
+  static FILE* const log = [] {
+    const char* e = sd_switch("MI355X_SD_ATTN_LOG");
+    return e ? fopen(e, "a") : nullptr;
+  }();
+  if (!log) return dispatch_attention(a, stream, nullptr);
+  char fam[48] = "rejected";
+  const int rc = dispatch_attention(a, stream, fam);
+  fprintf(log, "%d %d %d %d %d %s\n", a.B, a.H, a.Sq, a.Skv, a.D, fam);
+  fflush(log);
+  return rc;
+}
+
+static int dispatch_attention(const AttnArgs& a, hipStream_t stream, char* fam) {
   if (a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Skv <= 0 || a.D <= 0) return SD_ERR_INVALID;
   if ((a.D & 7) || a.D > 160) return SD_ERR_UNSUPPORTED;
   if ((a.q_ts & 7) || (a.k_ts & 7) || (a.v_ts & 7) || (a.o_ts & 3) || (a.q_bs & 7) || (a.k_bs & 7) || (a.v_bs & 7) ||
       (a.o_bs & 3))
     return SD_ERR_UNSUPPORTED;
   if (!(a.scale > 0.f)) return SD_ERR_INVALID;
-  if (a.D <= 64) return launch_dp<64>(a, stream);
-  if (a.D <= 96) return launch_dp<96>(a, stream);
-  return launch_dp<160>(a, stream);
+  if (a.D <= 64) return launch_dp<64>(a, stream, fam);
+  if (a.D <= 96) return launch_dp<96>(a, stream, fam);
+  return launch_dp<160>(a, stream, fam);
 }
 
 }  // namespace sd
