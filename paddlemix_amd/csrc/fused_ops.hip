@@ -100,9 +100,10 @@ int launch_fused_adaln_scale_residual(const bf16* x, int ldx, const bf16* mha, i
   const int cv = C >> 3;
   int blocks = (rows + 3) / 4;
   if (blocks > 2048) blocks = 2048;
-#define SD_FA_LAUNCH(NCH, M16)                                                                                                     \
+#define SD_FA_LAUNCH(NCH, M16) do {                                                                                                    \
   hipLaunchKernelGGL((fused_adaln_scale_residual_kernel<NCH, M16>), dim3(blocks), dim3(256), 0, stream, x, ldx, mha, ldm, gate, scale, \
-                     shift, ld_mod, rows_per_batch, weight, bias, eps, rows, C, resi, ldr, out, ldo)
+                     shift, ld_mod, rows_per_batch, weight, bias, eps, rows, C, resi, ldr, out, ldo);                                  \
+  norm_route("fused_adaln", C, NCH, 1, M16 ? "m16" : "m32"); } while (0)
   if (mod16) {
     if (cv <= 128) SD_FA_LAUNCH(2, true);
     else if (cv <= 256) SD_FA_LAUNCH(4, true);

@@ -92,6 +92,8 @@ struct AttnArgs {
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
 
+// MI355X_SD_NORM_LOG route log of the normalisation launchers (norm.hip; debug-switch build only)
+void norm_route(const char* entry, int C, int nch, int rows, const char* flags);
 // GroupNorm over NHWC rows: stats -> per-(batch, channel) scale/shift, then fused normalise(+SiLU)
 int launch_groupnorm_stats(const void* x, int x_f32, int B, int HW, int C, int ldx, int groups, float eps, const float* gamma,
                            const float* beta, float* partial, float* scale_shift, hipStream_t stream);

@@ -7,8 +7,11 @@
 // Statistics are biased (divide by N), accumulated in fp32 (+ fp64 across blocks), outputs written as bf16.
 //
 // GroupNorm is split in two so the second half is a pure per-channel affine (+SiLU):
-//   1. gn_partial_kernel:  per-(batch, pixel-strip) block sums of x and x^2 per group      (reads x once)
+//   1. gn_partial_kernel:  per-(batch, pixel-strip) block sums of x-K and (x-K)^2 per group  (reads x once)
 //      gn_finalize_kernel: mean / rstd per (batch, group) -> scale[b][c] = gamma*rstd, shift[b][c] = beta - mean*scale
+// K is the (batch, group)'s pilot x[b][pixel 0][first channel of the group]: every block reads it without communicating, and the
+// shifted sums keep the variance free of cancellation however large |mean| / std is (GroupNorm is translation-invariant; raw
+// sums of x^2 in fp32 lose the variance entirely at |mean| / std ~ 1000, tests/test_norm_bounds.py).
 //   2. scale_shift_act_kernel: y = act(x*scale + shift)                                    (reads x once, writes y once)
 // All loads/stores are 16-byte (8 x bf16) per lane.
 #include <stdio.h>
@@ -20,6 +23,20 @@
 namespace sd {
 
 static int ln_grid(int rows, int rows_per_block);
+
+// MI355X_SD_NORM_LOG=<path> (debug-switch build only, like MI355X_SD_GEMM_LOG / MI355X_SD_ATTN_LOG) appends "entry C NCH ROWS flags"
+// per kernel launch of the normalisation launchers here and in fused_ops.hip: entry is the kernel, NCH / ROWS / flags its template
+// arguments (0 / "-" where it has none). tests/norm_child.py: each case reached the instantiation it is named for, and the cases
+// together reach all of them.
+void norm_route(const char* entry, int C, int nch, int rows, const char* flags) {
+  static FILE* const log = [] {
+    const char* e = sd_switch("MI355X_SD_NORM_LOG");
+    return e ? fopen(e, "a") : nullptr;
+  }();
+  if (!log) return;
+  fprintf(log, "%s %d %d %d %s\n", entry, C, nch, rows, flags);
+  fflush(log);
+}
 
 // 8 consecutive channels of a row as fp32: from the build's 16-bit elements (one 16-byte load) or, in the fp32
 // residual-stream mode (XF32), from fp32 rows (two 16-byte loads). `x` is the row base in ELEMENTS of its own type.
@@ -43,6 +60,13 @@ __device__ __forceinline__ void load8f(const void* x, size_t elem_off, float (&f
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
   }
+}
+
+// one element of x as fp32 (the GroupNorm pilot K of a (batch, group): x[b][pixel 0][first channel of the group])
+template <bool XF32>
+__device__ __forceinline__ float load1f(const void* x, size_t elem_off) {
+  if constexpr (XF32) return reinterpret_cast<const float*>(x)[elem_off];
+  else return (float)reinterpret_cast<const bf16*>(x)[elem_off];
 }
 
 // pixels per thread-slot per block: statistics pass / apply pass (measured inside the SDXL step, profiles/r02_l_norm_knobs.txt:
@@ -85,10 +109,14 @@ __global__ void gn_partial_kernel(const void* __restrict__ x, int HW, int C, int
     const int cc = tid % cv, pl = tid / cv;
     const int p_begin = blockIdx.x * ppb;
     const int p_end = min(p_begin + ppb, HW);
-    float s[8], q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+    float s[8], q[8], K[8];
     const size_t xb = (size_t)b * HW * ldx + cc * 8;
+    const int cpg = C / groups;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s[j] = q[j] = 0.f;
+      K[j] = load1f<XF32>(x, (size_t)b * HW * ldx + (cc * 8 + j) / cpg * cpg);   // (a chunk can straddle groups when cpg < 8)
+    }
     // four pixels' loads in flight per thread (one 16-B load per trip left the kernel latency-bound at ~1.7 TB/s); the
     // accumulation order is the pixel order either way, so the partials do not depend on the unrolling
     int pix = p_begin + pl;
@@ -100,8 +128,9 @@ __global__ void gn_partial_kernel(const void* __restrict__ x, int HW, int C, int
       for (int u = 0; u < 4; ++u) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          s[j] += v[u][j];
-          q[j] = __builtin_fmaf(v[u][j], v[u][j], q[j]);
+          const float d = v[u][j] - K[j];
+          s[j] += d;
+          q[j] = __builtin_fmaf(d, d, q[j]);
         }
       }
     }
@@ -110,8 +139,9 @@ __global__ void gn_partial_kernel(const void* __restrict__ x, int HW, int C, int
       load8f<XF32>(x, xb + (size_t)pix * ldx, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        s[j] += v[j];
-        q[j] = __builtin_fmaf(v[j], v[j], q[j]);
+        const float d = v[j] - K[j];
+        s[j] += d;
+        q[j] = __builtin_fmaf(d, d, q[j]);
       }
     }
     float* ts = t_sum + (size_t)pl * C + cc * 8;
@@ -147,7 +177,7 @@ __global__ void gn_partial_kernel(const void* __restrict__ x, int HW, int C, int
 
 __global__ void gn_finalize_kernel(const float* __restrict__ partial, int nblk, int HW, int C, int groups, float eps,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                   float* __restrict__ scale_shift) {
+                                   float* __restrict__ scale_shift, const void* __restrict__ x, int ldx, int x_f32) {
   __shared__ float mean_s[64], rstd_s[64];
   __shared__ double part_s[64][8], part_q[64][8];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -173,11 +203,14 @@ __global__ void gn_finalize_kernel(const float* __restrict__ partial, int nblk, 
       s += part_s[tid][j];
       q += part_q[tid][j];
     }
+    // the partials are sums of x - K and (x - K)^2 with K the group's pilot (gn_partial_kernel)
+    const size_t pilot = (size_t)b * HW * ldx + (size_t)tid * cpg;
+    const double K = x_f32 ? (double)load1f<true>(x, pilot) : (double)load1f<false>(x, pilot);
     const double n = (double)HW * cpg;
-    const double mean = s / n;
-    double var = q / n - mean * mean;
+    const double m = s / n;
+    double var = q / n - m * m;
     if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)mean;
+    mean_s[tid] = (float)(K + m);
     rstd_s[tid] = (float)(1.0 / sqrt(var + (double)eps));
   }
   __syncthreads();
@@ -209,8 +242,10 @@ int launch_groupnorm_stats(const void* x, int x_f32, int B, int HW, int C, int l
   else
     hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(g.nblk, B), dim3(g.block), lds, stream, x, HW, C, ldx, groups, g.cv,
                        g.ppp, g.threads, g.ppb, partial);
+  norm_route("gn_partial", C, 0, 0, x_f32 ? "xf32" : "x16");
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(512), 0, stream, partial, g.nblk, HW, C, groups, eps, gamma,
-                     beta, scale_shift);
+                     beta, scale_shift, x, ldx, x_f32);
+  norm_route("gn_finalize", C, 0, 0, "-");
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
@@ -273,9 +308,10 @@ int launch_scale_shift_act(const void* x, int x_f32, int B, int HW, int C, int l
   if (raw16 && (!x_f32 || (ld_raw & 7))) return SD_ERR_UNSUPPORTED;
   const GnGeom g = gn_geom(HW, C, GN_ITERS_APPLY);
   if (g.block > 1024 || B > 65535) return SD_ERR_UNSUPPORTED;
-#define SD_SSA(S_, F_) \
+#define SD_SSA(S_, F_) do {                                                                                                   \
   hipLaunchKernelGGL((scale_shift_act_kernel<S_, F_>), dim3(g.nblk, B), dim3(g.block), 0, stream, x, HW, C, ldx, g.cv, g.ppp, \
-                     g.threads, g.ppb, scale_shift, y, ldy, raw16, ld_raw)
+                     g.threads, g.ppb, scale_shift, y, ldy, raw16, ld_raw);                                                   \
+  norm_route("scale_shift_act", C, 0, 0, S_ ? (F_ ? "silu,xf32" : "silu,x16") : (F_ ? "id,xf32" : "id,x16")); } while (0)
   if (silu) { if (x_f32) SD_SSA(true, true); else SD_SSA(true, false); }
   else      { if (x_f32) SD_SSA(false, true); else SD_SSA(false, false); }
 #undef SD_SSA
@@ -285,8 +321,9 @@ int launch_scale_shift_act(const void* x, int x_f32, int B, int HW, int C, int l
 // ---- GroupNorm (+SiLU) in ONE launch for small groups: the (batch, group) chunk held in registers --------------------------------
 // A block of 1024 threads owns one (batch item, group): HW pixels x cpg channels, at most 24 dwords (48 elements) per thread =
 // 96 KB per chunk. One read: every thread loads its dwords (2 channels each; cpg = C / groups is even for every SD width), sums
-// x and x^2 in fp32; block reduction in a fixed order (deterministic), mean / rstd in double like the two-launch form; then the
-// affine (+SiLU) is applied to the values still in registers and written. Three launches (statistics, finalize, apply) and the
+// x - K and (x - K)^2 in fp32 (K: the group's pilot, as in the two-launch form); block reduction in a fixed order
+// (deterministic), mean / rstd in double like the two-launch form; then the affine (+SiLU) is applied to the values still in
+// registers and written. Three launches (statistics, finalize, apply) and the
 // second read of x become one launch -- what the batch-1 SD-1.5 step needs (61 GroupNorms of 0.1-5 MB each: pure launch latency,
 // 19 % of its 6.3 ms step), and the 32x32 levels of SDXL. Larger groups (HW * cpg * 2 > 96 KB) keep the split form.
 constexpr int GNF_THREADS = 1024, GNF_MAXD = 24;
@@ -316,6 +353,7 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const bf16* __res
   }
   unsigned v[GNF_MAXD];
   float s = 0.f, q = 0.f;
+  const float K = (float)xb[0];   // the pilot: sums of x - K and (x - K)^2, as gn_partial_kernel
   // i / dpp == umulhi(i, ceil(2^32 / dpp)) for the i <= 24575 of a chunk; dpp == 1 (two channels per group) would need 2^32 itself
   const unsigned inv_dpp = dpp > 1 ? 0xFFFFFFFFu / (unsigned)dpp + 1u : 0u;
 #pragma unroll
@@ -328,9 +366,10 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const bf16* __res
     }
   }
 #pragma unroll
-  for (int k = 0; k < GNF_MAXD; ++k) {   // (zeros past the chunk's end add nothing)
+  for (int k = 0; k < GNF_MAXD; ++k) {   // (nothing past the chunk's end)
     const bf16x2 e = __builtin_bit_cast(bf16x2, v[k]);
-    const float a = (float)e[0], c = (float)e[1];
+    const bool in = tid + k * GNF_THREADS < nd;
+    const float a = in ? (float)e[0] - K : 0.f, c = in ? (float)e[1] - K : 0.f;
     s += a + c;
     q = __builtin_fmaf(a, a, __builtin_fmaf(c, c, q));
   }
@@ -348,10 +387,10 @@ __global__ __launch_bounds__(GNF_THREADS) void gn_fused_kernel(const bf16* __res
       sq += (double)red_q[w];
     }
     const double n = (double)HW * cpg;
-    const double mean = sa / n;
-    double var = sq / n - mean * mean;
+    const double m = sa / n;
+    double var = sq / n - m * m;
     if (var < 0.0) var = 0.0;
-    stat[0] = (float)mean;
+    stat[0] = (float)((double)K + m);
     stat[1] = (float)(1.0 / sqrt(var + (double)eps));
   }
   __syncthreads();
@@ -383,6 +422,7 @@ int launch_groupnorm_act(const bf16* x, int B, int HW, int C, int ldx, int group
     const int nb = B - b0 < 65535 ? B - b0 : 65535;
     const bf16* xb = x + (size_t)b0 * HW * ldx;
     bf16* yb = y + (size_t)b0 * HW * ldy;
+    norm_route("gn_fused", C, 0, 0, silu ? "silu" : "id");
     if (silu) hipLaunchKernelGGL(gn_fused_kernel<true>, dim3(groups, nb), dim3(GNF_THREADS), 0, stream, xb, HW, C, ldx, groups, eps, gamma, beta, yb, ldy);
     else hipLaunchKernelGGL(gn_fused_kernel<false>, dim3(groups, nb), dim3(GNF_THREADS), 0, stream, xb, HW, C, ldx, groups, eps, gamma, beta, yb, ldy);
   }
@@ -512,8 +552,10 @@ int launch_layernorm(const void* x, int x_f32, int rows, int C, int ldx, const f
   // the vector prologue and one trip per wave, 2 rows (twice the waves, ~110 instead of 200 registers) is ahead again: class
   // 2.80 -> 2.65 ms per step (profiles/r02_l_norm_knobs.txt).
   const int blocks = ln_grid(rows, wpb * 2);
-#define SD_LN_LAUNCH(NCH, R_, F_) \
-  hipLaunchKernelGGL((layernorm_kernel<NCH, R_, F_>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, gamma, beta, eps, y, ldy)
+#define SD_LN_LAUNCH(NCH, R_, F_) do {                                                                                               \
+  hipLaunchKernelGGL((layernorm_kernel<NCH, R_, F_>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, gamma, beta, eps, y, \
+                     ldy);                                                                                                           \
+  norm_route("layernorm", C, NCH, R_, F_ ? "xf32" : "x16"); } while (0)
   if (x_f32) {
     if (cv <= 128) SD_LN_LAUNCH(2, 2, true);
     else if (cv <= 192) SD_LN_LAUNCH(3, 2, true);
@@ -598,8 +640,9 @@ int launch_row_stats(const bf16* x, int rows, int C, int ldx, float eps, float* 
   const int wpb = 4, cv = C >> 3;
   constexpr int R = 4;
   const int blocks = ln_grid(rows, wpb * R);
-#define SD_RS_LAUNCH(NCH) \
-  hipLaunchKernelGGL((row_stats_kernel<NCH, R>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, eps, stats)
+#define SD_RS_LAUNCH(NCH) do {                                                                                          \
+  hipLaunchKernelGGL((row_stats_kernel<NCH, R>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, eps, stats); \
+  norm_route("row_stats", C, NCH, R, "-"); } while (0)
   if (cv <= 64) SD_RS_LAUNCH(1);
   else if (cv <= 128) SD_RS_LAUNCH(2);
   else if (cv <= 192) SD_RS_LAUNCH(3);
@@ -669,8 +712,9 @@ int launch_rmsnorm(const bf16* x, int rows, int C, int ldx, const float* weight,
   if ((C & 7) || (ldx & 7) || (ldy & 7) || C > 4096) return SD_ERR_UNSUPPORTED;
   const int cv = C >> 3;
   const int blocks = ln_grid(rows, 8);
-#define SD_RMS_LAUNCH(NCH) \
-  hipLaunchKernelGGL((rmsnorm_kernel<NCH, 2>), dim3(blocks), dim3(256), 0, stream, x, rows, C, ldx, weight, eps, y, ldy)
+#define SD_RMS_LAUNCH(NCH) do {                                                                                           \
+  hipLaunchKernelGGL((rmsnorm_kernel<NCH, 2>), dim3(blocks), dim3(256), 0, stream, x, rows, C, ldx, weight, eps, y, ldy); \
+  norm_route("rmsnorm", C, NCH, 2, "-"); } while (0)
   if (cv <= 128) SD_RMS_LAUNCH(2);
   else if (cv <= 256) SD_RMS_LAUNCH(4);
   else SD_RMS_LAUNCH(8);
@@ -857,9 +901,10 @@ int launch_adaln_f8(const bf16* x, int rows, int C, int ldx, const float* scale,
   const int cv = C >> 3;
   int blocks = (rows + 3) / 4;
   if (blocks > 2048) blocks = 2048;
-#define SD_AF8(NCH) \
+#define SD_AF8(NCH) do {                                                                                                \
   hipLaunchKernelGGL((adaln_f8_kernel<NCH>), dim3(blocks), dim3(256), 0, stream, x, rows, C, ldx, scale, shift, ld_mod, \
-                     rows_per_batch, eps, y8, ldy, yscale, yl2)
+                     rows_per_batch, eps, y8, ldy, yscale, yl2);                                                        \
+  norm_route("adaln_f8", C, NCH, 1, "-"); } while (0)
   if (cv <= 128) SD_AF8(2);
   else if (cv <= 192) SD_AF8(3);
   else SD_AF8(5);
@@ -908,6 +953,7 @@ int launch_quantize_rows(const bf16* x, long rows, int C, int ldx, int x_rpb, lo
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, rows, C, ldx, x_rpb, x_bstride, y8,
                      ldy, yscale);
+  norm_route("quantize_rows", C, 0, 1, "-");
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
@@ -922,9 +968,10 @@ int launch_adaln(const bf16* x, int rows, int C, int ldx, const void* scale, con
   // the per-batch scale / shift vectors add a dependent load to every iteration)
   int blocks = (rows + wpb * R - 1) / (wpb * R);
   if (blocks > 256 * 8) blocks = 256 * 8;
-#define SD_ADALN_LAUNCH(NCH, RR, M16)                                                                                         \
+#define SD_ADALN_LAUNCH(NCH, RR, M16) do {                                                                                         \
   hipLaunchKernelGGL((adaln_kernel<NCH, RR, M16>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, scale, shift, ld_mod, \
-                     rows_per_batch, eps, y, ldy)
+                     rows_per_batch, eps, y, ldy);                                                                                 \
+  norm_route("adaln", C, NCH, RR, M16 ? "m16" : "m32"); } while (0)
   if (mod16) {   // 16-bit modulation vectors (the reference's own operand type)
     if (cv <= 128) SD_ADALN_LAUNCH(2, R, true);
     else if (cv <= 192) SD_ADALN_LAUNCH(3, R, true);

@@ -70,13 +70,16 @@ def test_production_library_ignores_the_switches():
     every = {"MI355X_SD_ATTN_NO_M16": "1", "MI355X_SD_ATTN_NO_SHORT": "1", "MI355X_SD_ATTN_NO_QT": "1", "MI355X_SD_ATTN_NO_WIDE": "1",
              "MI355X_SD_NO_SPLITK": "1", "MI355X_SD_NO_GN_FUSED": "1", "MI355X_SD_NO_WIDEN_F8": "1", "MI355X_SD_GEMM_TILE": "128",
              "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_LOG": os.path.join(tempfile.mkdtemp(), "gemm.log"),
-             "MI355X_SD_ATTN_LOG": os.path.join(tempfile.mkdtemp(), "attn.log")}
+             "MI355X_SD_ATTN_LOG": os.path.join(tempfile.mkdtemp(), "attn.log"),
+             "MI355X_SD_NORM_LOG": os.path.join(tempfile.mkdtemp(), "norm.log")}
     prod_clean, prod_env = _run({"MI355X_SD_LIB": ""}), _run(dict(every, MI355X_SD_LIB=""))
     assert not os.path.exists(every["MI355X_SD_GEMM_LOG"])   # (the route logs: debug build only)
     assert not os.path.exists(every["MI355X_SD_ATTN_LOG"])
+    assert not os.path.exists(every["MI355X_SD_NORM_LOG"])
     dbg_clean, dbg_env = _run({}), _run(every)
     assert os.path.getsize(every["MI355X_SD_GEMM_LOG"]) > 0
     assert os.path.getsize(every["MI355X_SD_ATTN_LOG"]) > 0
+    assert os.path.getsize(every["MI355X_SD_NORM_LOG"]) > 0
     for k, v in prod_clean.items():
         assert prod_env[k]["sha"] == v["sha"] == dbg_clean[k]["sha"], (k, v, prod_env[k], dbg_clean[k])
     assert any(dbg_env[k]["sha"] != v["sha"] for k, v in dbg_clean.items())
