@@ -281,6 +281,9 @@ int mi355x_sd_conv3x3(const void* X, int ldx, int B, int Hs, int Ws, int Cin, in
   if (!g.pad && (stride != 2 || upsample))
     return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_conv3x3: MI355X_SD_PAD_BR is the stride-2 downsampler's padding");
   const int Hin = Hs << upsample, Win = Ws << upsample;
+  // (bottom / right padding of a one-pixel row or column: the padded image is narrower than the window and has no output; C's
+  // division truncates (1 + 1 - 3) / 2 to 0 and would compute one output row from a window that does not fit)
+  if (!g.pad && (Hin < 2 || Win < 2)) return fail(SD_ERR_INVALID, "mi355x_sd_conv3x3: image smaller than the padded 3 x 3 window");
   g.Ho = (Hin + 1 + g.pad - 3) / stride + 1;
   g.Wo = (Win + 1 + g.pad - 3) / stride + 1;
   g.M = B * g.Ho * g.Wo; g.N = Cout; g.K = 9 * Cin; g.lda = ldx; g.ldc = ldc;

@@ -529,7 +529,13 @@ static int dispatch_gemm(const GemmArgs& a_in, hipStream_t stream, char* fam) {
     if (tile == 256 || tile == 257) return routed("generic", 256, launch_cfg<false, Cfg256, true>(a, stream), "+f8");
     return routed("generic", 128, launch_cfg<false, Cfg128, true>(a, stream), "+f8");
   }
-  if (tile == 257 && !((a.K & 63) || (a.conv && (a.Cin & 63)) || a.a_rpb)) return routed("gemm256", 0, launch_gemm256(a, stream));
+  // The phased kernel addresses A and W through 32-bit buffer offsets (gemm256.hip: extent, image offset and pixel offset are
+  // `unsigned`), like launch_gemm_pipe. pick_tile_model's wide_ok bounds M * lda, which for a stride-2 conv is a quarter of the source:
+  // a 4 .. 8 GiB source (e.g. 3 x 1024 x 1024 pixels at a pixel stride of 1024 elements) passed it and reached the kernel with
+  // truncated offsets. Such a launch takes the generic 256 x 256 loop (64-bit addresses). The test holds for plain GEMMs too: the
+  // picker's wide_ok is the stricter one there, so it only matters for a forced tile (MI355X_SD_GEMM_TILE=257, debug build).
+  const bool fits32 = gemm_fits_32bit_offsets(a);
+  if (tile == 257 && fits32 && !((a.K & 63) || (a.conv && (a.Cin & 63)) || a.a_rpb)) return routed("gemm256", 0, launch_gemm256(a, stream));
   if (tile == 256 || tile == 257)
     return routed("generic", 256, a.conv ? launch_cfg<true, Cfg256>(a, stream) : launch_cfg<false, Cfg256>(a, stream));
   if (tile == 160 && !a.geglu)

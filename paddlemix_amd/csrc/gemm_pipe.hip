@@ -605,12 +605,7 @@ int launch_gemm_pipe(const GemmArgs& a_in, int tile, void* stream_) {
   if (a.geglu && tile == 129) return SD_ERR_UNSUPPORTED;   // odd number of 16-column sub-tiles per wave
   if (a.conv && (a.Cin & 7)) return SD_ERR_UNSUPPORTED;
   // 32-bit buffer offsets: every addressed byte of A and W must sit below 4 GiB - 64 KiB
-  const size_t lim = 0xFFFF0000ull;
-  size_t a_ext;
-  if (a.conv) a_ext = (size_t)(a.M / ((size_t)a.Ho * a.Wo)) * a.Hs * a.Ws * a.lda * 2;
-  else if (a.a_rpb) a_ext = ((size_t)((a.M - 1) / a.a_rpb) * a.a_bstride + (size_t)(a.a_rpb - 1) * a.lda + a.K) * 2;
-  else a_ext = ((size_t)(a.M - 1) * a.lda + a.K) * 2;
-  if (a_ext >= lim || (size_t)a.N * a.K * 2 >= lim) return SD_ERR_UNSUPPORTED;
+  if (!gemm_fits_32bit_offsets(a)) return SD_ERR_UNSUPPORTED;
   const bool ln = a.rowstat != nullptr;
   if (tile == 256) {
     if (ln) return launch_pipe<false, Cfg256, true>(a, stream);

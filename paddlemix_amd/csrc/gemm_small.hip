@@ -131,11 +131,7 @@ bool gemm_small_applies(const GemmArgs& a) {
   // (the three constants scanned inside the batch-1 SD-1.5 step, 24 .. 96 / 64 .. 320 / 40 .. 128: 5.22 .. 5.27 ms, flat --
   // profiles/r06_s35_small_policy.txt)
   if (nt > 48 && !(tiles >= 160 && nt <= 96)) return false;
-  const size_t lim = 0xFFFF0000ull;
-  size_t a_ext;
-  if (a.a_rpb) a_ext = ((size_t)((a.M - 1) / a.a_rpb) * a.a_bstride + (size_t)(a.a_rpb - 1) * a.lda + a.K) * 2;
-  else a_ext = ((size_t)(a.M - 1) * a.lda + a.K) * 2;
-  return a_ext < lim && (size_t)a.N * a.K * 2 < lim;
+  return gemm_fits_32bit_offsets(a);
 }
 
 int launch_gemm_small(const GemmArgs& a_in, hipStream_t stream) {

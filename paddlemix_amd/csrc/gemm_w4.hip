@@ -439,10 +439,7 @@ bool gemm_w4_applies(const GemmArgs& a, int bn) {
   }
   if ((a.K & 63) || a.K < 192 || (a.N & 7)) return false;   // (at least three K-tiles: first / last-but-one / last iterations)
   if (a.geglu && (a.N & 31)) return false;
-  const size_t lim = 0xFFFF0000ull;
-  const size_t a_ext = a.a_rpb ? ((size_t)((a.M - 1) / a.a_rpb) * a.a_bstride + (size_t)(a.a_rpb - 1) * a.lda + a.K) * 2
-                               : ((size_t)(a.M - 1) * a.lda + a.K) * 2;
-  return a_ext < lim && (size_t)a.N * a.K * 2 < lim;
+  return gemm_fits_32bit_offsets(a);
 }
 
 int launch_gemm_w4(const GemmArgs& a_in, hipStream_t stream, int bn) {

@@ -66,6 +66,17 @@ struct GemmArgs {
   void* ws_base;
   size_t ws_bytes;
 };
+// The kernels that address A and W through 32-bit buffer offsets (gemm_pipe.hip, gemm256.hip's 16-bit forms, gemm_small.hip,
+// gemm_w4.hip) can run a launch only when every addressed byte of both 16-bit operands sits below 4 GiB - 64 KiB. A: the whole
+// source of a conv (all images: for stride 2 that is four times M * lda), the remapped batches of an a_rpb launch, else M rows.
+inline bool gemm_fits_32bit_offsets(const GemmArgs& a) {
+  const size_t lim = 0xFFFF0000ull;
+  size_t a_ext;
+  if (a.conv) a_ext = (size_t)(a.M / ((size_t)a.Ho * a.Wo)) * a.Hs * a.Ws * a.lda * 2;
+  else if (a.a_rpb) a_ext = ((size_t)((a.M - 1) / a.a_rpb) * a.a_bstride + (size_t)(a.a_rpb - 1) * a.lda + a.K) * 2;
+  else a_ext = ((size_t)(a.M - 1) * a.lda + a.K) * 2;
+  return a_ext < lim && (size_t)a.N * a.K * 2 < lim;
+}
 void set_last_error(const char* msg);   // text behind mi355x_sd_last_error() (capi.hip), for the entry points defined elsewhere
 int launch_gemm(const GemmArgs& a, hipStream_t stream);
 int gemm_gm();   // tile rasterisation group of the GEMM kernels (-4 = column groups of 4)

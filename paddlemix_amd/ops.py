@@ -100,10 +100,12 @@ def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, rowbias: Opti
 
 def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, stride: int = 1, upsample: bool = False,
             rowbias: Optional[Tensor] = None, residual: Optional[Tensor] = None, out: Optional[Tensor] = None,
-            out_scale: float = 1.0, pad_br: bool = False, kb64: bool = False) -> Tensor:
+            out_scale: float = 1.0, pad_br: bool = False, kb64: bool = False, silu: bool = False,
+            out_f32: bool = False) -> Tensor:
     """x NHWC view [B,H,W,C] (pixel stride >= C), w [Cout, 9*Cin] -> rows [B*Ho*Wo, Cout]. ``pad_br`` (stride 2): zero
     padding at the bottom / right only -- Downsample2D(padding=0), resnet.py:277-279. ``kb64``: w is packed
-    [Cout][Cin/64][3][3][64] (MI355X_SD_CONV_KB64) instead of [Cout][3][3][Cin]."""
+    [Cout][Cin/64][3][3][64] (MI355X_SD_CONV_KB64) instead of [Cout][3][3][Cin]. ``silu`` / ``out_f32`` / an fp32 ``residual``:
+    MI355X_SD_SILU / MI355X_SD_OUT_F32 / MI355X_SD_R_F32, as in linear()."""
     lib = _lib.load()
     ws = _workspace(x.device)
     if x.dim() != 4 or x.dtype != _lib.elem_dtype() or x.stride(3) != 1 or not x.is_cuda:
@@ -120,14 +122,22 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, stride: int 
     Ho = ((H << up) + pad2 - 3) // stride + 1
     Wo = ((W << up) + pad2 - 3) // stride + 1
     M = B * Ho * Wo
+    if M <= 0:
+        raise ValueError("x: the image is smaller than the padded 3 x 3 window")
+    out_dtype = torch.float32 if out_f32 else _lib.elem_dtype()
     if out is None:
-        out = torch.empty((M, Cout), device=x.device, dtype=_lib.elem_dtype())
-    ldc = _rows(out, "out")
-    ldr = _rows(residual, "residual") if residual is not None else 0
+        out = torch.empty((M, Cout), device=x.device, dtype=out_dtype)
+    ldc = _rows(out, "out", out_dtype)
+    if out.shape != (M, Cout):
+        raise ValueError(f"out: expected {(M, Cout)}, got {tuple(out.shape)}")
+    r_f32 = residual is not None and residual.dtype == torch.float32
+    ldr = _rows(residual, "residual", torch.float32 if r_f32 else None) if residual is not None else 0
     ld_rb = rowbias.stride(0) if rowbias is not None else 0
+    flags = ((_lib.PAD_BR if pad_br else 0) | (_lib.CONV_KB64 if kb64 else 0) | (SILU if silu else 0) | (OUT_F32 if out_f32 else 0)
+             | (_lib.R_F32 if r_f32 else 0))
     check(lib.mi355x_sd_conv3x3(x.data_ptr(), ldx, B, H, W, C, stride, up, w.data_ptr(), out.data_ptr(), ldc, Cout,
                                 _p(_vec(bias, Cout, "bias")), _p(rowbias), ld_rb, _p(residual), ldr, float(out_scale),
-                                (_lib.PAD_BR if pad_br else 0) | (_lib.CONV_KB64 if kb64 else 0), *ws, _stream()))
+                                flags, *ws, _stream()))
     return out
 
 

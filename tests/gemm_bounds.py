@@ -32,6 +32,16 @@ is itself off by e, hence
 
     |out - ref| <= u_out |ref| + (1 + u_out) e + 2^-24         (the last term: fp16's subnormal spacing)
 
+Convolutions (tests/conv_bounds.py: K = 9 Cin on the im2col matrix) add three operands. rowbias [batches, N] is indexed like the
+gate, m // rows_per_batch, and added with the bias: its magnitude joins the bias's in the epilogue term. The residual may be fp32
+(r_f32): read exactly like the 16-bit one, its only error is the add. With bias, rowbias, residual and out_scale all present
+gemm_epilogue.h epi4 rounds four times -- bias add, rowbias add (the batched form adds rowbias + fp32 residual first, then that sum:
+still one rounding per operand), residual add, scale; a bias that starts the accumulators (bias_acc) saves one -- so EPI_OPS = 4 holds
+and is not raised. An fp32 output (OUT_F32) is the epilogue value itself: u_out = 0 and the bound is e + 2^-24 |ref| (the reference
+is compared in float64; 2^-24 |ref| is the fp32 representation of the value). Split-K needs no constant: a slice chains K / (32 s)
+steps, the reduce kernel adds the s slices in order, K / (32 s) + s roundings in all, which stays below K / 32 for 2 <= s <= K / 256 --
+what plan_splitk guarantees (at least 4 K-tiles of 64 per slice, nt >= 8) -- so gamma_K covers it.
+
 check() returns the worst |out - ref| / bound over the WHOLE output (the margin the logs show; a correct kernel stays below ~0.5, a
 wrong sub-tile or a doubled bias lands far above 1) and the rel-L2 of the same comparison.
 """
@@ -61,11 +71,11 @@ def _act(name, z):
 
 
 def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=False, gate=None, rows_per_batch=0,
-              residual=None):
+              residual=None, rowbias=None):
     """float64 reference and elementwise accumulator-side error e (before the output rounding) of
-    out = act(((a @ w^T) * w_scale + bias) * gate[m // rows_per_batch] + residual) * out_scale ..., or the GEGLU form.
-    a [M, K], w [N, K] (for WS: the dequantized weights, w_scale None), bias [N], gate [batches, N], residual [M, N]: the
-    logical operands exactly as the kernel reads them."""
+    out = act(((a @ w^T) * w_scale + bias + rowbias[m // rows_per_batch]) * gate[m // rows_per_batch] + residual) * out_scale ...,
+    or the GEGLU form. a [M, K], w [N, K] (for WS: the dequantized weights, w_scale None), bias [N], gate and rowbias
+    [batches, N], residual [M, N] (16-bit, or fp32 for r_f32 launches): the logical operands exactly as the kernel reads them."""
     M, K = a.shape
     A, W = a.double(), w.double()
     acc = A @ W.t()
@@ -78,6 +88,10 @@ def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=F
     mag = acc.abs() + b.abs()
     z = acc + b
     del acc
+    if rowbias is not None:
+        rb = rowbias.double()[torch.arange(M, device=z.device) // rows_per_batch]
+        z, mag = z + rb, mag + rb.abs()
+        del rb
     if gate is not None:
         g = gate.double()[torch.arange(M, device=z.device) // rows_per_batch]
         z, e, mag = z * g, e * g.abs(), mag * g.abs()
@@ -104,11 +118,15 @@ def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=F
 
 
 def check(out, ref, e):
-    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit output against reference() (non-finite -> inf)"""
-    u = U_OUT[out.dtype]
+    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit or fp32 output against reference() (non-finite -> inf)"""
     o = out.double()
     err = (o - ref).abs()
-    bound = u * ref.abs() + (1 + u) * e + U32
+    if out.dtype == torch.float32:   # (u_out = 0: the epilogue value, stored as it is)
+        bound = e + U32 * ref.abs()
+        bound = torch.where((bound == 0) & (err == 0), torch.ones_like(bound), bound)   # (an exact zero: 0 / 0 is a pass)
+    else:
+        u = U_OUT[out.dtype]
+        bound = u * ref.abs() + (1 + u) * e + U32
     ratio = (err / bound).max().item()
     if not torch.isfinite(o).all() or ratio != ratio:
         ratio = float("inf")

@@ -638,7 +638,8 @@ def test_fp32_residual_forms_of_the_norms(ops, rows, C):
 def test_conv3x3_kb64_weight_order(ops, B, H, W, Cin, Cout, stride, up):
     """MI355X_SD_CONV_KB64: weights packed [O][Cin/64][3][3][64], K loop tap-innermost per 64-channel block -- same result as
     the [O][3][3][Cin] packing bit for bit? No: the fp32 accumulation order over K differs, so to rounding; both against the
-    oracle. Covers every conv kernel (generic, pipelined 128 / 256x160, phased 256, split-K)."""
+    oracle. Each shape runs the ONE kernel the picker gives it; every conv kernel form (generic, pipelined, phased 256, split-K) under both
+    K orders, with the route of each case logged, is tests/test_gpu_convs.py."""
     g = torch.Generator().manual_seed(B * H + Cin + Cout + stride + 1)
     x = bfr(torch.randn(B, Cin, H, W, generator=g))
     w = bfr(torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin))
