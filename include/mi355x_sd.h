@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 12
+#define MI355X_SD_ABI_VERSION 13
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -431,6 +431,29 @@ int mi355x_sd_gated_activation(const void* x, int ldx, void* y, int ldy, int64_t
  * pipeline (pipeline_stable_diffusion.py:911). w bf16 [Cout][Cin]. */
 int mi355x_sd_conv1x1_nchw(const float* x_nchw, float in_scale, const void* w, const float* bias, float* y_nchw,
                            int B, int Cin, int Cout, int64_t HW, void* stream);
+/* ---- tiled AutoencoderKL (PPD/models/autoencoder_kl.py:334-446 tiled_encode / tiled_decode, blend_v / blend_h) ----
+ * tile_gather: copies a regular grid of equal windows of an fp32 NCHW tensor [B, C, H, W] into a stack of contiguous NCHW images
+ * [count, C, win_h, win_w] (the input batch of one tile plan). Window (iy, ix) of image b starts at (y0 + iy * stride_y,
+ * x0 + ix * stride_x) and is stack image n = (b * ny + iy) * nx + ix; the call writes images first <= n < first + count to dst[0..).
+ * Every window must lie inside the source. Rows that keep 16-byte alignment (W, x0, stride_x, win_w multiples of 4) move as 16-byte
+ * vectors. */
+int mi355x_sd_tile_gather(const float* src_nchw, int B, int C, int H, int W, int y0, int x0, int stride_y, int stride_x, int ny,
+                          int nx, int win_h, int win_w, int64_t first, int64_t count, float* dst, void* stream);
+/* tile_blend: the seam blend, crop and concatenation of the reference's tiled_decode / tiled_encode in one pass that writes every
+ * element of out [B, C, H, W] exactly once. Tile (i, j) covers the output from (i * lim, j * lim) and has min(S, H - i * lim) rows and
+ * min(S, W - j * lim) columns (ny = ceil(H / lim), nx = ceil(W / lim): derived here, not read from a table). The first
+ * e = min(extent of the neighbour, own extent, ext) rows of a tile are blended with the last e rows of the tile above,
+ * b[p] = a[Ea - e + p] * (1 - p / e) + b[p] * (p / e), then the first columns with the tile to the left, in the reference's order and
+ * rounding (the closed form of its sequential in-place algorithm, bit for bit in fp32: two rounded products and a rounded sum per
+ * lerp, no fma; needs ext <= lim <= S so that a blend reads rows the neighbour's own blend did not touch); everything else is a copy.
+ * tile_ptrs: DEVICE array of B * ny * nx pointers, [(b * ny + i) * nx + j] = element (channel 0, row 0, column 0) of tile (i, j) of
+ * image b. Inside a tile of eh x ew, element (c, y, x) lies at c * (t_chan_plane * eh * ew + t_chan) + (y * ew + x) * t_col floats:
+ * (1, 0, 1) = contiguous planes (the decoder's NCHW images), (0, 1, ld) = token-major rows [eh * ew][ld] (the encoder's moments).
+ * The output takes plain element strides (image, channel, row, column). With unit column strides and W, S, lim, ext multiples of 4
+ * the kernel moves 16-byte vectors. */
+int mi355x_sd_tile_blend(const void* tile_ptrs, int B, int C, int H, int W, int S, int lim, int ext, int ny, int nx,
+                         int64_t t_chan_plane, int64_t t_chan, int64_t t_col, float* out, int64_t o_img, int64_t o_chan, int64_t o_row,
+                         int64_t o_col, void* stream);
 /* y[r][0..n) = softmax(x[r][0..n)), x fp32 (scale already applied), y bf16; n % 4 == 0. The VAE mid-block attention
  * (one head of width C = 512: Attention(..., heads = C // C), unet_2d_blocks.py:606-619; get_attention_scores with
  * upcast_softmax, attention_processor.py:552-586) runs as linear(Q K^T, OUT_F32) -> softmax_rows -> linear(P V). */

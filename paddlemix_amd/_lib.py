@@ -24,7 +24,7 @@ if os.environ.get("MI355X_SD_LIB") == "dbg":
         raise ValueError("MI355X_SD_LIB=dbg: the debug-switch build exists for bf16 elements only")
     LIB_PATH = os.path.join(_HERE, "libmi355x_sd_dbg.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 GEGLU, OUT_F32, SILU, GELU_TANH, PAD_BR, R_F32, CONV_KB64 = 1, 2, 4, 8, 16, 32, 64
 UNET_ENC_MASK, UNET_SELF_MASK, UNET_CONTROLNET = 1, 2, 4   # mi355x_sd_unet_plan_ex flags
 SDPA_LOG2 = 1
@@ -125,6 +125,11 @@ SIGNATURES = {
     "mi355x_sd_activation": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mi355x_sd_conv1x1_nchw": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
                                          c_void_p]),
+    # tiled VAE (csrc/tiles.hip, ABI 13)
+    "mi355x_sd_tile_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int64, c_int64, c_void_p, c_void_p]),
+    "mi355x_sd_tile_blend": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64,
+                                     c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "mi355x_sd_softmax_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "mi355x_sd_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355x_sd_mask_to_bias": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

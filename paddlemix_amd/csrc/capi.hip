@@ -529,6 +529,37 @@ int mi355x_sd_conv1x1_nchw(const float* x_nchw, float in_scale, const void* w, c
                 "mi355x_sd_conv1x1_nchw");
 }
 
+int mi355x_sd_tile_gather(const float* src_nchw, int B, int C, int H, int W, int y0, int x0, int stride_y, int stride_x, int ny,
+                          int nx, int win_h, int win_w, int64_t first, int64_t count, float* dst, void* stream) {
+  if (!src_nchw || !dst) return fail(SD_ERR_INVALID, "mi355x_sd_tile_gather: null pointer");
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ny <= 0 || nx <= 0 || win_h <= 0 || win_w <= 0)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_gather: sizes and grid counts must be positive");
+  if (y0 < 0 || x0 < 0 || stride_y < 0 || stride_x < 0 || (int64_t)y0 + (int64_t)(ny - 1) * stride_y + win_h > H ||
+      (int64_t)x0 + (int64_t)(nx - 1) * stride_x + win_w > W)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_gather: a window of the grid leaves the source tensor");
+  if (first < 0 || count <= 0 || first + count > (int64_t)B * ny * nx)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_gather: [first, first + count) is not a range of the B * ny * nx windows");
+  return finish(launch_tile_gather(src_nchw, B, C, H, W, y0, x0, stride_y, stride_x, ny, nx, win_h, win_w, (long)first, (long)count,
+                                   dst, S(stream)), "mi355x_sd_tile_gather");
+}
+
+int mi355x_sd_tile_blend(const void* tile_ptrs, int B, int C, int H, int W, int S_, int lim, int ext, int ny, int nx,
+                         int64_t t_chan_plane, int64_t t_chan, int64_t t_col, float* out, int64_t o_img, int64_t o_chan, int64_t o_row,
+                         int64_t o_col, void* stream) {
+  if (!tile_ptrs || !out) return fail(SD_ERR_INVALID, "mi355x_sd_tile_blend: null pointer");
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || S_ <= 0 || lim <= 0 || ext < 0)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_blend: sizes must be positive (ext >= 0)");
+  if (ext > lim || lim > S_)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_blend: needs ext <= lim <= S (a blend must read outside the neighbour's own band)");
+  if (ny != (H + lim - 1) / lim || nx != (W + lim - 1) / lim)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_blend: ny, nx must be ceil(H / lim), ceil(W / lim)");
+  if (t_chan_plane < 0 || t_chan < 0 || t_col <= 0 || o_img < 0 || o_chan < 0 || o_row <= 0 || o_col <= 0)
+    return fail(SD_ERR_INVALID, "mi355x_sd_tile_blend: strides must be positive");
+  return finish(launch_tile_blend((const float* const*)tile_ptrs, B, C, H, W, S_, lim, ext, ny, nx, (long)t_chan_plane, (long)t_chan,
+                                  (long)t_col, out, (long)o_img, (long)o_chan, (long)o_row, (long)o_col, S(stream)),
+                "mi355x_sd_tile_blend");
+}
+
 int mi355x_sd_softmax_rows(const float* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int n, void* stream) {
   if (!x || !y) return fail(SD_ERR_INVALID, "mi355x_sd_softmax_rows: null pointer");
   return finish(launch_softmax_rows(x, (long)ldx, (bf16*)y, (long)ldy, (long)rows, n, S(stream)),

@@ -162,4 +162,10 @@ int launch_cfg_axpby(const float* x, const float* eu, const float* et, float* ou
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 
+// tiled VAE (tiles.hip)
+int launch_tile_gather(const float* src, int B, int C, int H, int W, int y0, int x0, int sy, int sx, int ny, int nx, int wh, int ww,
+                       long first, long count, float* dst, hipStream_t stream);
+int launch_tile_blend(const float* const* tiles, int B, int C, int H, int W, int S, int lim, int ext, int ny, int nx, long t_scp,
+                      long t_sc, long t_sx, float* out, long o_sb, long o_sc, long o_sy, long o_sx, hipStream_t stream);
+
 }  // namespace sd

@@ -434,6 +434,64 @@ def conv1x1_nchw(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, in_scale: 
     return y
 
 
+def tile_gather(src: Tensor, origin, stride, counts, window, first: int = 0, count: Optional[int] = None,
+                out: Optional[Tensor] = None) -> Tensor:
+    """The ``counts = (ny, nx)`` windows of ``window = (wh, ww)`` that start at ``origin + (iy, ix) * stride`` in every image of
+    src fp32 [B, C, H, W] -> fp32 [count, C, wh, ww]: stack images ``first .. first + count`` of the order (b, iy, ix)."""
+    lib = _lib.load()
+    if not src.is_cuda:
+        raise _lib.MI355XError("src: tensor must live on the GPU (no CPU fallback)")
+    if src.dtype != torch.float32 or src.dim() != 4 or not src.is_contiguous():
+        raise ValueError("src: expected a contiguous fp32 NCHW tensor")
+    B, C, H, W = src.shape
+    (y0, x0), (sy, sx), (ny, nx), (wh, ww) = origin, stride, counts, window
+    count = B * ny * nx - first if count is None else count
+    if out is None:
+        out = torch.empty((max(count, 0), C, wh, ww), device=src.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != count * C * wh * ww or not out.is_cuda:
+        raise ValueError(f"out: expected a contiguous fp32 GPU tensor of {count} x {C} x {wh} x {ww}")
+    check(lib.mi355x_sd_tile_gather(src.data_ptr(), B, C, H, W, y0, x0, sy, sx, ny, nx, wh, ww, first, count, out.data_ptr(),
+                                    _stream()))
+    return out
+
+
+def tile_blend(tiles, H: int, W: int, S: int, lim: int, ext: int, *, token_major: bool = False, C: Optional[int] = None,
+               out: Optional[Tensor] = None) -> Tensor:
+    """Blend, crop and join decoded tiles (AutoencoderKL.tiled_decode's second loop) in one launch. ``tiles[i][j]`` covers the
+    result from (i * lim, j * lim) with eh = min(S, H - i * lim) rows and ew = min(S, W - j * lim) columns: contiguous fp32
+    [B, C, eh, ew], result [B, C, H, W]; or, ``token_major``, fp32 rows [B, eh * ew, ld >= C], result [B, H * W, C]."""
+    lib = _lib.load()
+    ny, nx = len(tiles), len(tiles[0])
+    t00 = tiles[0][0]
+    if not t00.is_cuda:
+        raise _lib.MI355XError("tiles: tensors must live on the GPU (no CPU fallback)")
+    B = t00.shape[0]
+    C = (t00.shape[2] if token_major else t00.shape[1]) if C is None else C
+    ptrs = [[] for _ in range(B)]
+    for i, row in enumerate(tiles):
+        if len(row) != nx:
+            raise ValueError("tiles: every row needs the same number of tiles")
+        for j, t in enumerate(row):
+            eh, ew = min(S, H - i * lim), min(S, W - j * lim)
+            want = (B, eh * ew) if token_major else (B, C, eh, ew)
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape[:len(want)]) != want or \
+                    (token_major and (t.dim() != 3 or t.shape[2] < C or t.shape[2] != t00.shape[2])):
+                raise ValueError(f"tiles[{i}][{j}]: expected contiguous fp32 {want + (('ld >= %d' % C,) if token_major else ())}, "
+                                 f"got {t.dtype} {tuple(t.shape)}")
+            for b in range(B):
+                ptrs[b].append(t.data_ptr() + 4 * b * t.stride(0))
+    table = torch.tensor(ptrs, dtype=torch.int64).to(t00.device)
+    shape = (B, H * W, C) if token_major else (B, C, H, W)
+    if out is None:
+        out = torch.empty(shape, device=t00.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out: expected a contiguous fp32 GPU tensor {shape}")
+    ts = (0, 1, t00.shape[2]) if token_major else (1, 0, 1)
+    os_ = (H * W * C, 1, W * C, C) if token_major else (C * H * W, H * W, W, 1)
+    check(lib.mi355x_sd_tile_blend(table.data_ptr(), B, C, H, W, S, lim, ext, ny, nx, *ts, out.data_ptr(), *os_, _stream()))
+    return out
+
+
 def softmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """bf16 softmax over the last dim of an fp32 [rows, n] matrix."""
     lib = _lib.load()

@@ -25,7 +25,29 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
 
 
-class StableDiffusionDenoiser:
+class _VaeSwitches:
+    """``enable_vae_tiling`` / ``enable_vae_slicing`` of the reference's pipelines (pipeline_stable_diffusion.py enable_vae_slicing /
+    enable_vae_tiling and their disable_ twins): forwarded to the ``vae`` the pipeline owns."""
+
+    def _vae(self):
+        if self.vae is None:
+            raise ValueError("this pipeline was built without a `vae`")
+        return self.vae
+
+    def enable_vae_slicing(self) -> None:
+        self._vae().enable_slicing()
+
+    def disable_vae_slicing(self) -> None:
+        self._vae().disable_slicing()
+
+    def enable_vae_tiling(self) -> None:
+        self._vae().enable_tiling()
+
+    def disable_vae_tiling(self) -> None:
+        self._vae().disable_tiling()
+
+
+class StableDiffusionDenoiser(_VaeSwitches):
     """``pipe = StableDiffusionDenoiser(unet, scheduler); latents = pipe(prompt_embeds=..., ...)``"""
 
     def __init__(self, unet, scheduler, vae=None, text_encoder=None, text_encoder_2=None, controlnet=None):
@@ -386,7 +408,7 @@ class StableDiffusionDenoiser:
         return self.decode_latents(latents, output_type)
 
 
-class StableDiffusion3Denoiser:
+class StableDiffusion3Denoiser(_VaeSwitches):
     """The denoising loop of ``StableDiffusion3Pipeline.__call__`` (pipelines/stable_diffusion_3/
     pipeline_stable_diffusion_3.py:772-870) with the MI355X MMDiT in the ``transformer`` slot: CFG batch doubling
     ([negative, positive]), the transformer call, the guidance combine, ``FlowMatchEulerDiscreteScheduler.step`` and
@@ -465,7 +487,7 @@ class StableDiffusion3Denoiser:
         return image if output_type == "pt" else image.cpu().permute(0, 2, 3, 1).float().numpy()
 
 
-class DiTDenoiser:
+class DiTDenoiser(_VaeSwitches):
     """The loop of ``DiTPipeline.__call__`` (pipelines/dit/pipeline_dit.py:158-246) with the MI355X DiT in the ``transformer``
     slot: class-conditional classifier-free guidance with the null class (index ``num_embeds_ada_norm``) on the DUPLICATED
     latent half (:182-184), guidance applied to the epsilon channels only (:209-216), the learned-sigma channels dropped

@@ -21,7 +21,18 @@ linear) folded into conv_out's weights at load time; the moments leave the conv 
 them into the DiagonalGaussianDistribution's NCHW mean / clipped logvar / sample (vae.py:744-763). Encoder parameters are
 optional: a checkpoint without them gives a decode-only model whose ``encode`` raises.
 
-Tiling (``enable_tiling``) and the training-only ``kl`` / ``nll`` are not built. There is no CPU fallback.
+Tiling (``enable_tiling``, ``tiled_decode`` / ``tiled_encode``, autoencoder_kl.py:143-156, 334-446): inputs larger than
+``tile_latent_min_size`` / ``tile_sample_min_size`` are cut into overlapping tiles at stride int(size * (1 - tile_overlap_factor));
+the tiles of one size across all images run as ONE batch of the untiled plan above (tiles are independent images to GroupNorm and
+to the per-image attention loop), cut by the same _MAX_ELEMS rule, with mi355x_sd_tile_gather filling the plan's input batch.
+The reference then blends each tile with the finished tile above and to its left, in place, crops and concatenates; because a
+blend reads rows / columns its neighbour's own blend did not touch (factor <= 0.5) that sequence has a closed form per output
+element over at most four decoded tiles, and mi355x_sd_tile_blend (csrc/tiles.hip) writes the result in one pass, every element
+once, through a device table of tile pointers built with the plans. The mid-block attention's S x S scores are then those of one
+tile, so memory no longer grows with the image. Geometries the reference would answer with another image size, and ragged tiles
+the plan cannot take, are refused before anything is launched.
+
+The training-only ``kl`` / ``nll`` are not built. There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -222,6 +233,14 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         self.cfg = normalize_config(config)
         self.config = SimpleNamespace(**self.cfg)
         self.use_slicing = False
+        # tiling (autoencoder_kl.py:124-134): plain attributes a caller may assign, read at every call
+        self.use_tiling = False
+        ss = self.cfg["sample_size"]
+        self.tile_sample_min_size = ss
+        self.tile_latent_min_size = int((ss[0] if isinstance(ss, (list, tuple)) else ss)
+                                        / 2 ** (len(self.cfg["block_out_channels"]) - 1))
+        self.tile_overlap_factor = 0.25
+        self._tilings: Dict[tuple, SimpleNamespace] = {}
         self._load_weights(params)
 
     @classmethod
@@ -243,8 +262,17 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
     def disable_slicing(self) -> None:
         self.use_slicing = False
 
-    def enable_tiling(self, *a, **k):
-        raise NotImplementedError("tiled encode / decode (autoencoder_kl.py:335-449) is not built; use enable_slicing")
+    def enable_tiling(self, use_tiling: bool = True) -> None:
+        """decode / encode inputs larger than the tile size as overlapping tiles with blended seams, so that memory stays constant
+        in the image size (autoencoder_kl.py:143-156)"""
+        if use_tiling and not self.cfg["use_post_quant_conv"]:
+            # the reference's tiled_decode calls self.post_quant_conv(tile) unconditionally (:425): it cannot run there either
+            raise NotImplementedError("tiled decode needs post_quant_conv (autoencoder_kl.py:425 applies it to every tile); "
+                                      "this model has use_post_quant_conv=False")
+        self.use_tiling = bool(use_tiling)
+
+    def disable_tiling(self) -> None:
+        self.enable_tiling(False)
 
     # ------------------------------------------------------------------ weights
     def _load_weights(self, params: Mapping[str, Tensor]) -> None:
@@ -484,15 +512,19 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             self._plans[key] = self._build_plan(B, h, w_, in_scale, mode)
         return self._plans[key]
 
-    def _slice_batch(self, B: int, h: int, w_: int, mode: str = "decode") -> int:
-        if self.use_slicing:
-            return 1
+    def _max_batch(self, h: int, w_: int, mode: str = "decode") -> int:
+        """images of h x w one launch sequence may hold (the _MAX_ELEMS rule on the widest activation)"""
         n = len(self.cfg["block_out_channels"])
         if mode == "encode":
             widest = self.cfg["block_out_channels"][0] * h * w_
         else:
             widest = max(self.cfg["block_out_channels"][min(1, n - 1)], 1) * (h << (n - 1)) * (w_ << (n - 1))
-        return max(1, min(B, _MAX_ELEMS // max(widest, 1)))
+        return max(1, _MAX_ELEMS // max(widest, 1))
+
+    def _slice_batch(self, B: int, h: int, w_: int, mode: str = "decode") -> int:
+        if self.use_slicing:
+            return 1
+        return max(1, min(B, self._max_batch(h, w_, mode)))
 
     def _launch(self, plan: _Plan, stage) -> None:
         """stage the inputs and run the plan on the model's stream, ordered after / before the caller's stream"""
@@ -517,6 +549,8 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         if not self._emulated and not z.is_cuda:
             raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
         B, _, h, w_ = z.shape
+        if self.use_tiling and max(h, w_) > self._tile_sizes()[0]:
+            return self.tiled_decode(z, return_dict, in_scale=in_scale)
         if (h * w_) % 8:
             raise ValueError("h * w of the latent must be a multiple of 8 (mid-block attention GEMM alignment)")
         step = self._slice_batch(B, h, w_)
@@ -541,6 +575,8 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         if not self._emulated and not x.is_cuda:
             raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
         B, _, H, Wd = x.shape
+        if self.use_tiling and max(H, Wd) > self._tile_sizes()[1]:
+            return self.tiled_encode(x, return_dict)
         n = len(self.cfg["block_out_channels"])
         if H % (1 << (n - 1)) or Wd % (1 << (n - 1)) or ((H >> (n - 1)) * (Wd >> (n - 1))) % 8:
             raise ValueError(f"H and W must be multiples of {1 << (n - 1)} with (H * W) / {1 << (2 * n - 2)} a multiple of 8 "
@@ -562,24 +598,194 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             return (post,)
         return AutoencoderKLOutput(latent_dist=post)
 
-    def _sample_posterior(self, moments: Tensor, noise: Tensor, shape, out_scale: float) -> Tensor:
-        B, L, h, w_ = shape
-        mean = torch.empty(shape, device=moments.device, dtype=torch.float32)
-        logvar, sample = torch.empty_like(mean), torch.empty_like(mean)
+    # ------------------------------------------------------------------ tiling
+    def _tile_sizes(self):
+        """(tile_latent_min_size, tile_sample_min_size) as the integers the tiling uses"""
+        S = self.tile_sample_min_size
+        return int(self.tile_latent_min_size), int(S[0] if isinstance(S, (list, tuple)) else S)
 
-        def go(_nb):
-            rc = self._lib.mi355x_sd_latent_dist(moments.data_ptr(), moments.stride(0), B, L, h * w_, noise.data_ptr(),
-                                                 float(out_scale), mean.data_ptr(), logvar.data_ptr(), sample.data_ptr(),
-                                                 self._stream_ptr)
+    def _build_tiling(self, mode: str, B: int, h: int, w_: int, in_scale: float) -> SimpleNamespace:
+        """The tile grid of an h x w input (the latent for "decode", the image for "encode"), its size classes with their plans, and
+        the device table of tile pointers the blend reads. Every refusal is raised here, before anything is launched."""
+        cfg = self.cfg
+        T, S = self._tile_sizes()
+        f = self.tile_overlap_factor
+        F = 1 << (len(cfg["block_out_channels"]) - 1)
+        if not 0.0 <= f <= 0.5:
+            raise ValueError(f"tile_overlap_factor = {f!r} is outside [0, 0.5] (a seam would be blended from more than two tiles per axis)")
+        # `size` = extent of a full input tile; ext / lim are on the output side (autoencoder_kl.py:365-367, 414-416)
+        size, ext, lim = (T, int(S * f), S - int(S * f)) if mode == "decode" else (S, int(T * f), T - int(T * f))
+        ov = int(size * (1 - f))
+        if ov < 1:
+            raise ValueError(f"tile stride int({size} * (1 - {f!r})) = {ov} must be at least 1")
+        if mode == "decode" and ov * F != lim:
+            raise ValueError(f"tile_latent_min_size = {T}, tile_sample_min_size = {S}, tile_overlap_factor = {f!r}: the latent stride {ov} "
+                             f"times {F} is not the {lim} image rows kept per tile (the result would not be {F}x the latent)")
+        if mode == "encode" and ov != lim * F:
+            raise ValueError(f"tile_latent_min_size = {T}, tile_sample_min_size = {S}, tile_overlap_factor = {f!r}: the image stride {ov} "
+                             f"is not {F} times the {lim} latent rows kept per tile (the result would not be 1/{F} of the image)")
+        ys = [(s, min(size, h - s)) for s in range(0, h, ov)]
+        xs = [(s, min(size, w_ - s)) for s in range(0, w_, ov)]
+        for i, (_, th) in enumerate(ys):
+            for j, (_, tw) in enumerate(xs):
+                if mode == "encode" and (th % F or tw % F):
+                    raise ValueError(f"tile ({i}, {j}) of the image is {th} x {tw}: not a multiple of {F}")
+                lh, lw = (th, tw) if mode == "decode" else (th // F, tw // F)
+                if (lh * lw) % 8:
+                    raise ValueError(f"tile ({i}, {j}) has a {lh} x {lw} latent: h * w must be a multiple of 8 "
+                                     "(mid-block attention GEMM alignment)")
+
+        def runs(tiles):   # [(first index, count, extent)]: at most three extents per axis, each a contiguous range
+            out = []
+            for k, (_, e) in enumerate(tiles):
+                if out and out[-1][2] == e:
+                    out[-1][1] += 1
+                else:
+                    out.append([k, 1, e])
+            return out
+
+        tl = SimpleNamespace()   # tile grid, size classes (with their plans) and device pointer table of this geometry
+        tl.mode, tl.B, tl.ov, tl.ext, tl.lim, tl.ny, tl.nx = mode, B, ov, ext, lim, len(ys), len(xs)
+        L = cfg["latent_channels"]
+        if mode == "decode":
+            tl.C, tl.full, tl.H, tl.W = cfg["out_channels"], size * F, h * F, w_ * F
+        else:
+            tl.C, tl.full, tl.H, tl.W = 2 * L, size // F, h // F, w_ // F
+        tl.classes = []
+        ptrs = [[0] * (tl.ny * tl.nx) for _ in range(B)]
+        for i0, cy, th in runs(ys):
+            for j0, cx, tw in runs(xs):
+                c = SimpleNamespace(i0=i0, j0=j0, cy=cy, cx=cx, th=th, tw=tw)
+                N = B * cy * cx
+                step = min(N, self._max_batch(th, tw, mode))
+                if self.use_slicing:   # one image's tiles per launch sequence
+                    step = min(step, cy * cx)
+                c.slices = [(s, min(step, N - s), self._get_plan(min(step, N - s), th, tw, in_scale, mode)) for s in range(0, N, step)]
+                per = tl.C * th * tw * F * F if mode == "decode" else (th // F) * (tw // F) * 2 * L   # floats per result tile
+                # a class that runs as one launch sequence is blended out of its plan's own result; otherwise the slices' results are
+                # collected in a stack of the plan's layout
+                c.stack = None
+                if len(c.slices) > 1:
+                    c.stack = torch.empty((N, tl.C, th * F, tw * F) if mode == "decode" else (N * (th // F) * (tw // F), 2 * L),
+                                          device=self.device, dtype=torch.float32)
+                p0 = c.slices[0][2]
+                base = c.stack if c.stack is not None else (p0.out if mode == "decode" else p0.moments)
+                for b in range(B):
+                    for iy in range(cy):
+                        for ix in range(cx):
+                            ptrs[b][(i0 + iy) * tl.nx + j0 + ix] = base.data_ptr() + 4 * per * ((b * cy + iy) * cx + ix)
+                tl.classes.append(c)
+        tl.table = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+        return tl
+
+    def _get_tiling(self, mode, B, h, w_, in_scale) -> SimpleNamespace:
+        key = (mode, B, h, w_, float(in_scale), self._tile_sizes(), float(self.tile_overlap_factor), self.use_slicing)
+        if key not in self._tilings:
+            self._tilings[key] = self._build_tiling(mode, B, h, w_, in_scale)
+        return self._tilings[key]
+
+    def _run_tiling(self, tl: SimpleNamespace, src: Tensor, out: Tensor, o_strides) -> None:
+        """gather -> per-class tile plans -> one blend pass into `out`, all on the model's stream"""
+        lib, sp = self._lib, self._stream_ptr
+        _, Cin, h, w_ = src.shape
+        dec = tl.mode == "decode"
+
+        def body(nb):
+            for c in tl.classes:
+                for first, count, plan in c.slices:
+                    rc = lib.mi355x_sd_tile_gather(src.data_ptr(), tl.B, Cin, h, w_, c.i0 * tl.ov, c.j0 * tl.ov, tl.ov, tl.ov, c.cy, c.cx,
+                                                   c.th, c.tw, first, count, (plan.z if dec else plan.x).data_ptr(), sp)
+                    if rc:
+                        _lib.check(rc)
+                    if self._emulated:
+                        self._run_eager(plan)
+                    else:
+                        self.run(plan)
+                    if c.stack is not None:
+                        res = plan.out if dec else plan.moments
+                        c.stack[first * (res.shape[0] // count):(first + count) * (res.shape[0] // count)].copy_(res, non_blocking=nb)
+            ts = (1, 0, 1) if dec else (0, 1, tl.C)
+            rc = lib.mi355x_sd_tile_blend(tl.table.data_ptr(), tl.B, tl.C, tl.H, tl.W, tl.full, tl.lim, tl.ext, tl.ny, tl.nx, *ts,
+                                          out.data_ptr(), *o_strides, sp)
             if rc:
                 _lib.check(rc)
 
         if self._emulated:
-            go(False)
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                go(True)
-            cur.wait_stream(self._stream)
+            body(False)
+            return
+        cur = torch.cuda.current_stream(self.device)
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            body(True)
+        cur.wait_stream(self._stream)
+
+    def tiled_decode(self, z: Tensor, return_dict: bool = True, *, in_scale: float = 1.0):
+        """``decode`` over overlapping latent tiles of tile_latent_min_size at stride int(T * (1 - tile_overlap_factor)), each an
+        independent image to post_quant_conv and the decoder, seams blended over int(tile_sample_min_size * factor) pixels
+        (autoencoder_kl.py:400-446). The tiles of one size across all images run as one batch of the untiled plan."""
+        if not self.cfg["use_post_quant_conv"]:
+            raise NotImplementedError("tiled decode needs post_quant_conv (autoencoder_kl.py:425 applies it to every tile)")
+        if z.dim() != 4 or z.shape[1] != self.cfg["latent_channels"]:
+            raise ValueError(f"z: expected [B, {self.cfg['latent_channels']}, h, w], got {tuple(z.shape)}")
+        if not self._emulated and not z.is_cuda:
+            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        B, _, h, w_ = z.shape
+        tl = self._get_tiling("decode", B, h, w_, in_scale)
+        zc = z.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty((B, tl.C, tl.H, tl.W), device=self.device, dtype=torch.float32)
+        self._run_tiling(tl, zc, out, (tl.C * tl.H * tl.W, tl.H * tl.W, tl.W, 1))
+        if not return_dict:
+            return (out,)
+        return DecoderOutput(sample=out)
+
+    def tiled_encode(self, x: Tensor, return_dict: bool = True):
+        """``encode`` over overlapping image tiles of tile_sample_min_size: each goes through the encoder and quant_conv, the
+        moments are blended over int(tile_latent_min_size * factor) latent pixels, then the posterior (autoencoder_kl.py:346-398)."""
+        if not self.has_encoder:
+            raise _lib.MI355XError("this AutoencoderKL was built without encoder parameters (decode-only checkpoint)")
+        if not self.cfg["use_quant_conv"]:
+            raise NotImplementedError("tiled encode needs quant_conv (autoencoder_kl.py:376 applies it to every tile)")
+        if x.dim() != 4 or x.shape[1] != self.cfg["in_channels"]:
+            raise ValueError(f"x: expected [B, {self.cfg['in_channels']}, H, W], got {tuple(x.shape)}")
+        if not self._emulated and not x.is_cuda:
+            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        B, _, H, Wd = x.shape
+        tl = self._get_tiling("encode", B, H, Wd, 1.0)
+        L, dev = self.cfg["latent_channels"], self.device
+        xc = x.to(device=dev, dtype=torch.float32).contiguous()
+        moments = torch.empty((B * tl.H * tl.W, 2 * L), device=dev, dtype=torch.float32)
+        mean = torch.empty((B, L, tl.H, tl.W), device=dev, dtype=torch.float32)
+        logvar = torch.empty_like(mean)
+        self._run_tiling(tl, xc, moments, (tl.H * tl.W * 2 * L, 1, tl.W * 2 * L, 2 * L))
+        self._posterior_moments(moments, (B, L, tl.H, tl.W), None, 1.0, mean, logvar, None)
+        post = DiagonalGaussianDistribution(self, moments, B, L, tl.H, tl.W, mean, logvar)
+        if not return_dict:
+            return (post,)
+        return AutoencoderKLOutput(latent_dist=post)
+
+    def _posterior_moments(self, moments, shape, noise, out_scale, mean, logvar, sample) -> None:
+        """one launch of mi355x_sd_latent_dist on the model's stream"""
+        B, L, h, w_ = shape
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+
+        def go():
+            rc = self._lib.mi355x_sd_latent_dist(moments.data_ptr(), moments.stride(0), B, L, h * w_, p(noise), float(out_scale),
+                                                 mean.data_ptr(), logvar.data_ptr(), p(sample), self._stream_ptr)
+            if rc:
+                _lib.check(rc)
+
+        if self._emulated:
+            go()
+            return
+        cur = torch.cuda.current_stream(self.device)
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            go()
+        cur.wait_stream(self._stream)
+
+    def _sample_posterior(self, moments: Tensor, noise: Tensor, shape, out_scale: float) -> Tensor:
+        B, L, h, w_ = shape
+        mean = torch.empty(shape, device=moments.device, dtype=torch.float32)
+        logvar, sample = torch.empty_like(mean), torch.empty_like(mean)
+        self._posterior_moments(moments, shape, noise, out_scale, mean, logvar, sample)
         return sample
