@@ -307,10 +307,25 @@ def conv_out3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], B: int, H: int, W:
     return out
 
 
+def _flat_f32(t: Tensor, name: str, numel: Optional[int] = None) -> None:
+    """a contiguous fp32 GPU tensor (of `numel` elements): what the elementwise kernels index as one flat array"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or \
+            (numel is not None and t.numel() != numel):
+        raise ValueError(f"{name}: expected a contiguous fp32 GPU tensor" + (f" of {numel} elements" if numel is not None else ""))
+
+
 def axpby(x: Tensor, y: Tensor, coef: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """out = coef[0] * x + coef[1] * y on flat fp32 tensors of equal size (out may be x: the in-place latent update)."""
     lib = _lib.load()
+    _flat_f32(x, "x")
+    _flat_f32(y, "y", x.numel())
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 2 or \
+            not coef.is_contiguous():
+        raise ValueError("coef: expected a contiguous fp32 GPU tensor (a, b)")
     if out is None:
         out = torch.empty_like(x)
+    else:
+        _flat_f32(out, "out", x.numel())
     check(lib.mi355x_sd_axpby(x.data_ptr(), y.data_ptr(), out.data_ptr(), coef.data_ptr(), x.numel(), _stream()))
     return out
 
@@ -406,7 +421,11 @@ def adaptive_layer_norm(x: Tensor, scale: Tensor, shift: Tensor, weight: Optiona
 
 def patchify(x_nchw: Tensor, patch: int) -> Tensor:
     lib = _lib.load()
+    if not x_nchw.is_cuda or x_nchw.dtype != torch.float32 or x_nchw.dim() != 4 or not x_nchw.is_contiguous():
+        raise ValueError("x: expected a contiguous fp32 NCHW GPU tensor")
     B, C, H, W = x_nchw.shape
+    if patch <= 0 or H % patch or W % patch:
+        raise ValueError(f"x: {H} x {W} is not a whole number of {patch} x {patch} patches")
     out = torch.empty((B * (H // patch) * (W // patch), C * patch * patch), device=x_nchw.device, dtype=_lib.elem_dtype())
     check(lib.mi355x_sd_patchify(x_nchw.data_ptr(), B, C, H, W, patch, out.data_ptr(), out.shape[1], _stream()))
     return out
@@ -414,8 +433,15 @@ def patchify(x_nchw: Tensor, patch: int) -> Tensor:
 
 def unpatchify(x: Tensor, B: int, C: int, H: int, W: int, patch: int) -> Tensor:
     lib = _lib.load()
+    if not x.is_cuda:
+        raise ValueError("x: expected a GPU tensor")
+    ldx = _rows(x, "x")
+    if min(B, C, H, W, patch) <= 0 or H % patch or W % patch or \
+            tuple(x.shape) != (B * (H // patch) * (W // patch), patch * patch * C):
+        raise ValueError(f"x: expected rows [B * (H / p) * (W / p), p * p * C] for B, C, H, W, p = {(B, C, H, W, patch)}, got "
+                         f"{tuple(x.shape)}")
     out = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32)
-    check(lib.mi355x_sd_unpatchify(x.data_ptr(), _rows(x, "x"), B, C, H, W, patch, out.data_ptr(), _stream()))
+    check(lib.mi355x_sd_unpatchify(x.data_ptr(), ldx, B, C, H, W, patch, out.data_ptr(), _stream()))
     return out
 
 
@@ -500,6 +526,9 @@ def softmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     rows, n = x.shape
     if out is None:
         out = torch.empty((rows, n), device=x.device, dtype=_lib.elem_dtype())
+    elif not out.is_cuda or out.dtype != _lib.elem_dtype() or tuple(out.shape) != (rows, n) or out.stride(1) != 1:
+        raise ValueError(f"out: expected {_lib.elem_dtype()} GPU rows {(rows, n)} with unit inner stride, got {out.dtype} "
+                         f"{tuple(out.shape)} strides {out.stride()}")
     check(lib.mi355x_sd_softmax_rows(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), rows, n, _stream()))
     return out
 
@@ -540,6 +569,12 @@ def embed_tokens(ids: Tensor, token_table: Tensor, position_table: Tensor, seq_l
     lib = _lib.load()
     if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous():
         raise ValueError("ids: expected a contiguous int32 GPU tensor")
+    ed = _lib.elem_dtype()
+    for name, t in (("token_table", token_table), ("position_table", position_table)):
+        if not t.is_cuda or t.dtype != ed or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous 2-D {ed} GPU tensor, got {t.dtype} {tuple(t.shape)}")
+    if token_table.shape[1] != position_table.shape[1]:
+        raise ValueError(f"token_table / position_table: widths {token_table.shape[1]} and {position_table.shape[1]} differ")
     V, D = token_table.shape
     if int(ids.min()) < 0 or int(ids.max()) >= V or seq_len > position_table.shape[0]:
         raise ValueError("ids / seq_len out of range of the embedding tables")
@@ -575,8 +610,12 @@ def gated_activation(x: Tensor, kind: str = "gelu_new") -> Tensor:
     """[rows, 2F] -> [rows, F]: act(x[:, :F]) * x[:, F:]."""
     lib = _lib.load()
     kinds = {"quick_gelu": 0, "gelu": 1, "silu": 2, "gelu_new": 3}
+    if not x.is_cuda:
+        raise ValueError("x: expected a GPU tensor")
     ldx = _rows(x, "x")
     rows, F2 = x.shape
+    if F2 % 2:
+        raise ValueError(f"x: the gated width {F2} is odd ([rows, 2F] = [act half | gate half])")
     out = torch.empty((rows, F2 // 2), device=x.device, dtype=_lib.elem_dtype())
     check(lib.mi355x_sd_gated_activation(x.data_ptr(), ldx, out.data_ptr(), F2 // 2, rows, F2 // 2, kinds[kind], _stream()))
     return out
