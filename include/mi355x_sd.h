@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 13
+#define MI355X_SD_ABI_VERSION 14
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -467,6 +467,16 @@ int mi355x_sd_axpby(const float* x, const float* y, float* out, const float* coe
  * UNet output. */
 int mi355x_sd_cfg_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
                         float guidance_scale, int64_t n, void* stream);
+/* The same update with the guidance rescale folded in as well (rescale_noise_cfg, pipeline_stable_diffusion.py:69-80; the
+ * `guidance_rescale` of the SD / SDXL pipelines, used with v-prediction and zero-terminal-SNR checkpoints). Per sample s of `batch`,
+ * over its per_sample = C * H * W elements: c = eps_uncond + guidance_scale * (eps_text - eps_uncond), r[s] = std(eps_text[s]) / std(c[s])
+ * (the unbiased estimator; each variance by two passes, mean first, then the squared deviations),
+ * out = coef[0]*x + coef[1] * c * (guidance_rescale * r[s] + 1 - guidance_rescale). One launch, one block per sample, no scratch; the
+ * reductions are fixed trees without atomics, so equal inputs give equal bits. A sample of zero variance divides as the reference
+ * does (inf / NaN): no epsilon is added. out may be x itself; out overlapping x in any other way, or eps_uncond / eps_text at all, is
+ * MI355X_SD_ERR_INVALID, as are batch <= 0 and per_sample < 2 (the estimator divides by per_sample - 1). */
+int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
+                                float guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

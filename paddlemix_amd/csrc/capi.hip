@@ -582,6 +582,21 @@ int mi355x_sd_cfg_axpby(const float* x, const float* eps_uncond, const float* ep
   return finish(launch_cfg_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, (long)n, S(stream)), "mi355x_sd_cfg_axpby");
 }
 
+int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
+                                float guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream) {
+  const char* who = "mi355x_sd_cfg_rescale_axpby";
+  if (!x || !eps_uncond || !eps_text || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  if (batch <= 0 || per_sample < 2 || per_sample > INT64_MAX / 4 / batch)
+    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 2 (the estimator divides by per_sample - 1)", who);
+  // the block of a sample reads eps_* in three passes and x in the last one while other blocks already write out
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4, o = (uintptr_t)out;
+  auto overlaps = [&](const float* p) { return o < (uintptr_t)p + bytes && (uintptr_t)p < o + bytes; };
+  if (overlaps(eps_uncond) || overlaps(eps_text) || (out != x && overlaps(x)))
+    return fail(SD_ERR_INVALID, "%s: out may be x itself, but must not overlap x in any other way, nor eps_uncond / eps_text", who);
+  return finish(launch_cfg_rescale_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, guidance_rescale, batch, (long)per_sample,
+                                         S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

@@ -159,6 +159,8 @@ int launch_softmax_rows(const float* x, long ldx, bf16* y, long ldy, long rows, 
 int launch_copy_rows(const bf16* x, int ldx, bf16* y, int ldy, long rows, int C, hipStream_t stream);
 int launch_cfg_axpby(const float* x, const float* eu, const float* et, float* out, const float* coef, float gs, long n,
                      hipStream_t stream);
+int launch_cfg_rescale_axpby(const float* x, const float* eu, const float* et, float* out, const float* coef, float gs, float gr,
+                             int batch, long per_sample, hipStream_t stream);
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 

@@ -600,6 +600,117 @@ int launch_cfg_axpby(const float* x, const float* eu, const float* et, float* ou
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
+// The same pass with the guidance rescale folded in (rescale_noise_cfg, pipeline_stable_diffusion.py:69-80): per sample
+//   c = eu + gs * (et - eu),  r = std(et) / std(c) over the sample's n elements,  out = coef[0] * x + coef[1] * c * (gr * r + 1 - gr).
+// One block of 1024 threads per sample, no scratch. Each variance takes two passes (the mean, then the squared deviations from it; a
+// latent with an offset would cancel in sum(v^2) - n mean^2). Every sum is a fixed tree: a lane adds its elements tid, tid + 1024, ...
+// in that order, the 64 lanes of a wave fold by butterfly (wave_sum), the 16 wave partials go through LDS and fold by a second,
+// four-level butterfly -- no atomics, and every lane ends with the same bits. Nothing is added to a zero variance.
+// A block of 1024 threads has 128 registers per lane (16 waves on 4 SIMDs of 512), so a lane keeps CRA_RES = 32 values of et and 32 of
+// c in registers: samples of up to CRA_THREADS * CRA_RES = 32768 elements are read from memory once (RESIDENT); larger ones (the
+// 4 x 128 x 128 SDXL latent is 65536) read eu / et three times, the second and third time from L2 (<= 2 MB per step: latency, not
+// bandwidth). x is read and out written by the same lane in the last pass only, so out may be x.
+constexpr int CRA_THREADS = 1024, CRA_RES = 32;
+
+__device__ __forceinline__ float cfg_mix(float u, float t, float gs) { return fmaf(gs, t - u, u); }
+
+// a, b <- their sums over the block, in every lane; part: LDS [2][16]
+__device__ __forceinline__ void block_sum2(float& a, float& b, float (*part)[CRA_THREADS / 64]) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63;
+  __syncthreads();   // (the readers of the previous call are done with part)
+  if (lane == 0) {
+    part[0][threadIdx.x >> 6] = a;
+    part[1][threadIdx.x >> 6] = b;
+  }
+  __syncthreads();
+  a = part[0][lane & 15];
+  b = part[1][lane & 15];
+  for (int o = 8; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+}
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(CRA_THREADS) void cfg_rescale_axpby_kernel(const float* x, const float* __restrict__ eu,
+                                                                        const float* __restrict__ et, float* out,
+                                                                        const float* __restrict__ coef, float gs, float gr, long n) {
+  __shared__ float part[2][CRA_THREADS / 64];
+  const long base = (long)blockIdx.x * n;
+  x += base, eu += base, et += base, out += base;
+  const float a = coef[0], b = coef[1];
+  const int tid = threadIdx.x;
+  constexpr int R = RESIDENT ? CRA_RES : 1;
+  float tv[R], cv[R];
+  float s_t = 0.f, s_c = 0.f;
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = tid + j * CRA_THREADS;
+      tv[j] = cv[j] = 0.f;
+      if (i < n) {
+        tv[j] = et[i];
+        cv[j] = cfg_mix(eu[i], tv[j], gs);
+        s_t += tv[j];
+        s_c += cv[j];
+      }
+    }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS) {
+      const float t = et[i];
+      s_t += t;
+      s_c += cfg_mix(eu[i], t, gs);
+    }
+  }
+  block_sum2(s_t, s_c, part);
+  const float inv_n = 1.0f / (float)n;
+  const float m_t = s_t * inv_n, m_c = s_c * inv_n;
+  float q_t = 0.f, q_c = 0.f;
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+      if (tid + j * CRA_THREADS < n) {
+        const float dt = tv[j] - m_t, dc = cv[j] - m_c;
+        q_t += dt * dt;
+        q_c += dc * dc;
+      }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS) {
+      const float t = et[i];
+      const float dt = t - m_t, dc = cfg_mix(eu[i], t, gs) - m_c;
+      q_t += dt * dt;
+      q_c += dc * dc;
+    }
+  }
+  block_sum2(q_t, q_c, part);
+  const float inv_nm1 = 1.0f / (float)(n - 1);
+  const float r = sqrtf(q_t * inv_nm1) / sqrtf(q_c * inv_nm1);
+  const float k = gr * r + (1.0f - gr);
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = tid + j * CRA_THREADS;
+      if (i < n) out[i] = a * x[i] + b * (cv[j] * k);
+    }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS) out[i] = a * x[i] + b * (cfg_mix(eu[i], et[i], gs) * k);
+  }
+}
+
+int launch_cfg_rescale_axpby(const float* x, const float* eu, const float* et, float* out, const float* coef, float gs, float gr,
+                             int batch, long per_sample, hipStream_t stream) {
+  if (batch <= 0 || per_sample < 2) return SD_ERR_INVALID;
+  if (per_sample <= (long)CRA_THREADS * CRA_RES)
+    hipLaunchKernelGGL(cfg_rescale_axpby_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, out, coef, gs,
+                       gr, per_sample);
+  else
+    hipLaunchKernelGGL(cfg_rescale_axpby_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, out, coef, gs,
+                       gr, per_sample);
+  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+}
+
 // additive attention bias of a keep-mask: (1 - mask) * -10000 (unet_2d_condition.py:921-927, 1-D masks of 1 = attend, 0 = mask out)
 __global__ void mask_to_bias_kernel(const float* __restrict__ mask, float* __restrict__ bias, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) bias[i] = (1.0f - mask[i]) * -10000.0f;

@@ -330,6 +330,33 @@ def axpby(x: Tensor, y: Tensor, coef: Tensor, out: Optional[Tensor] = None) -> T
     return out
 
 
+def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Tensor, guidance_scale: float,
+                      guidance_rescale: float, out: Optional[Tensor] = None) -> Tensor:
+    """Guidance combine, guidance rescale (``rescale_noise_cfg``) and the linear scheduler update in one launch. x, eps_uncond,
+    eps_text: contiguous fp32 [B, ...] of one shape with at least 2 elements per sample; with c = eps_uncond + guidance_scale *
+    (eps_text - eps_uncond) and r[s] = std(eps_text[s]) / std(c[s]) over everything but the batch axis,
+    out = coef[0] * x + coef[1] * c * (guidance_rescale * r[s] + 1 - guidance_rescale). out may be x."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    if x.dim() < 2 or x.shape[0] < 1 or x.numel() // x.shape[0] < 2:
+        raise ValueError(f"x: expected [B, ...] with at least 2 elements per sample, got {tuple(x.shape)}")
+    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text")):
+        _flat_f32(t, name, x.numel())
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 2 or \
+            not coef.is_contiguous():
+        raise ValueError("coef: expected a contiguous fp32 GPU tensor (a, b)")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _flat_f32(out, "out", x.numel())
+    check(lib.mi355x_sd_cfg_rescale_axpby(x.data_ptr(), eps_uncond.data_ptr(), eps_text.data_ptr(), out.data_ptr(), coef.data_ptr(),
+                                          float(guidance_scale), float(guidance_rescale), x.shape[0], x.numel() // x.shape[0],
+                                          _stream()))
+    return out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

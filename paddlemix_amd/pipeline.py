@@ -88,11 +88,15 @@ class StableDiffusionDenoiser(_VaeSwitches):
                              f"{cfg.projection_class_embeddings_input_dim}, but a vector of {passed} was created.")
         return torch.tensor([ids], dtype=torch.float32, device=device)
 
-    def _fused_plan(self, guidance_rescale: float, device):
+    def _fused_plan(self, rescale: bool, device):
         """(per-step input scales, device table of (a, b), library, stream getter) when the scheduler's step is the
-        linear epsilon update ``prev = a * x + b * eps`` (``step_coefficients``); None -> the generic torch path."""
+        linear update ``prev = a * x + b * model_output`` (``step_coefficients``: epsilon and v prediction); None -> the generic
+        torch path. ``rescale``: the loop will call ``mi355x_sd_cfg_rescale_axpby``. The library always has it (its ABI version
+        is checked at load); a test backend written before that entry keeps the generic path."""
         sch = self.scheduler
-        if guidance_rescale > 0.0 or not hasattr(sch, "step_coefficients") or not hasattr(self.unet, "_lib"):
+        if not hasattr(sch, "step_coefficients") or not hasattr(self.unet, "_lib"):
+            return None
+        if rescale and getattr(self.unet, "_emulated", False) and not hasattr(self.unet._lib, "mi355x_sd_cfg_rescale_axpby"):
             return None
         try:
             scales, coefs = [], []
@@ -332,7 +336,8 @@ class StableDiffusionDenoiser(_VaeSwitches):
         if tc_dim is not None:
             w = torch.full((B,), float(guidance_scale) - 1.0, device=latents.device)
             unet_kw["timestep_cond"] = self.get_guidance_scale_embedding(w, embedding_dim=tc_dim)
-        fused = self._fused_plan(guidance_rescale, latents.device) if fused_update and not eta else None
+        rescale = do_cfg and guidance_rescale > 0.0   # without CFG the reference applies no rescale (:886-888)
+        fused = self._fused_plan(rescale, latents.device) if fused_update and not eta else None
         nine = inp is not None and cfg.in_channels != latents.shape[1]
 
         def control(x_in, t):
@@ -368,8 +373,9 @@ class StableDiffusionDenoiser(_VaeSwitches):
         for i, t in enumerate(timesteps, start=first):
             latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
             if fused is not None:
-                # guidance combine + scheduler update as ONE device pass over the latents (mi355x_sd_cfg_axpby): the
-                # epsilon-prediction step of Euler / DDIM(eta=0) is prev = a*x + b*eps with per-step (a, b) kept in HBM
+                # guidance combine (+ guidance rescale) + scheduler update as ONE device pass over the latents (mi355x_sd_cfg_axpby /
+                # cfg_rescale_axpby): the epsilon- or v-prediction step of Euler / DDIM(eta=0) is prev = a*x + b*model_output with
+                # per-step (a, b) kept in HBM
                 scales, coef, lib, stream = fused
                 scaled = latent_model_input * scales[i]
                 noise_pred = self.unet(extend(scaled), t, encoder_hidden_states=prompt_embeds,
@@ -377,7 +383,11 @@ class StableDiffusionDenoiser(_VaeSwitches):
                 lat = latents.contiguous()
                 out = torch.empty_like(lat)
                 n, cp = lat.numel(), coef.data_ptr() + 8 * i
-                if do_cfg:
+                if rescale:
+                    rc = lib.mi355x_sd_cfg_rescale_axpby(lat.data_ptr(), noise_pred.data_ptr(), noise_pred.data_ptr() + 4 * n,
+                                                         out.data_ptr(), cp, float(guidance_scale), float(guidance_rescale),
+                                                         lat.shape[0], n // lat.shape[0], stream())
+                elif do_cfg:
                     rc = lib.mi355x_sd_cfg_axpby(lat.data_ptr(), noise_pred.data_ptr(), noise_pred.data_ptr() + 4 * n,
                                                  out.data_ptr(), cp, float(guidance_scale), n, stream())
                 else:

@@ -11,7 +11,8 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
-returns (a, b) so the latent update can run as the library's fused ``mi355x_sd_axpby`` inside a captured graph.
+returns (a, b) -- DDIM and Euler, epsilon and v prediction -- so the latent update can run as the library's fused
+``mi355x_sd_axpby`` / ``cfg_axpby`` / ``cfg_rescale_axpby`` inside a captured graph.
 """
 from __future__ import annotations
 
@@ -84,11 +85,15 @@ class DDIMScheduler:
         return (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
 
     def step_coefficients(self, timestep) -> Tuple[float, float]:
-        """(a, b) with prev = a*sample + b*model_output; epsilon prediction, eta = 0, no clipping."""
+        """(a, b) with prev = a*sample + b*model_output; epsilon or v prediction, eta = 0, no clipping."""
         c = self.config
-        if c.prediction_type != "epsilon" or c.clip_sample:
-            raise NotImplementedError("linear-update form needs epsilon prediction without clip_sample")
+        if c.prediction_type not in ("epsilon", "v_prediction") or c.clip_sample:
+            raise NotImplementedError("linear-update form needs epsilon or v prediction without clip_sample")
         a_t, a_prev = (float(v) for v in self._alphas(int(timestep)))
+        if c.prediction_type == "v_prediction":
+            # step(): x0 = sqrt(a_t) x - sqrt(1 - a_t) v, eps = sqrt(a_t) v + sqrt(1 - a_t) x, prev = sqrt(a_prev) x0 + sqrt(1 - a_prev) eps
+            sa, sb, pa, pb = a_t ** 0.5, (1 - a_t) ** 0.5, a_prev ** 0.5, (1 - a_prev) ** 0.5
+            return pa * sa + pb * sb, pb * sa - pa * sb
         a = (a_prev / a_t) ** 0.5
         b = (1 - a_prev) ** 0.5 - (a_prev * (1 - a_t) / a_t) ** 0.5
         return a, b
@@ -348,13 +353,16 @@ class EulerDiscreteScheduler:
         return 1.0 / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
 
     def step_coefficients(self, timestep) -> Tuple[float, float]:
-        """(a, b) with prev = a*sample + b*model_output for epsilon prediction, s_churn = 0; advances the index."""
-        if self.config.prediction_type != "epsilon":
-            raise NotImplementedError("linear-update form is for epsilon prediction")
+        """(a, b) with prev = a*sample + b*model_output for epsilon or v prediction, s_churn = 0; advances the index."""
+        if self.config.prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError("linear-update form is for epsilon or v prediction")
         if self._step_index is None:
             self._init_step_index(timestep)
         s, s_next = float(self.sigmas[self._step_index]), float(self.sigmas[self._step_index + 1])
         self._step_index += 1
+        if self.config.prediction_type == "v_prediction":
+            # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+            return 1.0 + (s_next - s) * s / (s ** 2 + 1), (s_next - s) / (s ** 2 + 1) ** 0.5
         return 1.0, s_next - s
 
     def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0,
