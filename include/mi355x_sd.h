@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 14
+#define MI355X_SD_ABI_VERSION 15
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -477,6 +477,22 @@ int mi355x_sd_cfg_axpby(const float* x, const float* eps_uncond, const float* ep
  * MI355X_SD_ERR_INVALID, as are batch <= 0 and per_sample < 2 (the estimator divides by per_sample - 1). */
 int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
                                 float guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream);
+
+/* One step of DPM-Solver multistep sampling (DPMSolverMultistepScheduler: dpmsolver++ / dpmsolver, solver_order 1 and 2, midpoint /
+ * heun) in one launch: guidance combine, guidance rescale, convert_model_output, the multistep update and its history. coef is 5
+ * fp32 values (p, q, A, B, D) in device memory, read by the kernel (DPMSolverMultistepScheduler.multistep_coefficients), so a
+ * captured graph replays with another row. Per element, with e the guided model output (c of mi355x_sd_cfg_axpby; with
+ * guidance_rescale > 0 times the per-sample factor of mi355x_sd_cfg_rescale_axpby, same statistics, one block per sample):
+ *   m0 = p*x + q*e  -> m_out,      out = A*x + B*m0 + D*(m0 - m_prev)
+ * eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ * coef[4] == 0 (a first-order step) : m_prev is NOT read, so the uninitialised history of a fresh loop is harmless; it must still be
+ * a valid non-null pointer (a captured graph cannot change it between replays).
+ * Aliasing: out may be x itself and m_out may be m_prev itself (one history buffer); each element is read and written by the same
+ * lane in the last pass only. Every other overlap among out, m_out, the inputs and coef is MI355X_SD_ERR_INVALID before any launch, as
+ * are a null x, eps_uncond, m_prev, out, m_out or coef, batch <= 0, per_sample < 1, and per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const float* eps_text, const float* m_prev, float* out,
+                               float* m_out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
+                               int64_t per_sample, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

@@ -597,6 +597,32 @@ int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const f
                                          S(stream)), who);
 }
 
+int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const float* eps_text, const float* m_prev, float* out,
+                               float* m_out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
+                               int64_t per_sample, void* stream) {
+  const char* who = "mi355x_sd_multistep_update";
+  if (!x || !eps_uncond || !m_prev || !out || !m_out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / batch)
+    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
+                "per_sample - 1)", who);
+  // blocks write out and m_out while others still read the inputs: only the same-lane pairs out = x and m_out = m_prev may alias
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  auto overlaps = [&](const void* w, const void* p, uintptr_t len) {
+    return p && (uintptr_t)w < (uintptr_t)p + len && (uintptr_t)p < (uintptr_t)w + bytes;
+  };
+  bool bad = overlaps(out, m_out, bytes);
+  for (const float* w : {(const float*)out, (const float*)m_out}) {
+    bad = bad || overlaps(w, eps_uncond, bytes) || overlaps(w, eps_text, bytes) || overlaps(w, coef, 5 * sizeof(float));
+    bad = bad || (!(w == out && out == x) && overlaps(w, x, bytes)) || (!(w == m_out && m_out == m_prev) && overlaps(w, m_prev, bytes));
+  }
+  if (bad)
+    return fail(SD_ERR_INVALID, "%s: out may be x itself and m_out may be m_prev itself; out and m_out must not overlap each other, "
+                "the inputs or coef in any other way", who);
+  return finish(launch_multistep_update(x, eps_uncond, eps_text, m_prev, out, m_out, coef, guidance_scale,
+                                        rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

@@ -633,17 +633,14 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float (*part)[CRA
   }
 }
 
+// The statistics passes of a sample: k = gr * std(et) / std(c) + (1 - gr), the same bits in every lane. RESIDENT: cv[j] <- c of the
+// lane's element tid + j * CRA_THREADS (0 past n), kept for the caller's last pass.
 template <bool RESIDENT>
-__global__ __launch_bounds__(CRA_THREADS) void cfg_rescale_axpby_kernel(const float* x, const float* __restrict__ eu,
-                                                                        const float* __restrict__ et, float* out,
-                                                                        const float* __restrict__ coef, float gs, float gr, long n) {
-  __shared__ float part[2][CRA_THREADS / 64];
-  const long base = (long)blockIdx.x * n;
-  x += base, eu += base, et += base, out += base;
-  const float a = coef[0], b = coef[1];
+__device__ __forceinline__ float cfg_rescale_factor(const float* __restrict__ eu, const float* __restrict__ et, float gs, float gr,
+                                                    long n, float (&cv)[RESIDENT ? CRA_RES : 1], float (*part)[CRA_THREADS / 64]) {
   const int tid = threadIdx.x;
   constexpr int R = RESIDENT ? CRA_RES : 1;
-  float tv[R], cv[R];
+  float tv[R];
   float s_t = 0.f, s_c = 0.f;
   if (RESIDENT) {
 #pragma unroll
@@ -687,7 +684,21 @@ __global__ __launch_bounds__(CRA_THREADS) void cfg_rescale_axpby_kernel(const fl
   block_sum2(q_t, q_c, part);
   const float inv_nm1 = 1.0f / (float)(n - 1);
   const float r = sqrtf(q_t * inv_nm1) / sqrtf(q_c * inv_nm1);
-  const float k = gr * r + (1.0f - gr);
+  return gr * r + (1.0f - gr);
+}
+
+template <bool RESIDENT>
+__global__ __launch_bounds__(CRA_THREADS) void cfg_rescale_axpby_kernel(const float* x, const float* __restrict__ eu,
+                                                                        const float* __restrict__ et, float* out,
+                                                                        const float* __restrict__ coef, float gs, float gr, long n) {
+  __shared__ float part[2][CRA_THREADS / 64];
+  const long base = (long)blockIdx.x * n;
+  x += base, eu += base, et += base, out += base;
+  const float a = coef[0], b = coef[1];
+  const int tid = threadIdx.x;
+  constexpr int R = RESIDENT ? CRA_RES : 1;
+  float cv[R];
+  const float k = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
   if (RESIDENT) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -708,6 +719,125 @@ int launch_cfg_rescale_axpby(const float* x, const float* eu, const float* et, f
   else
     hipLaunchKernelGGL(cfg_rescale_axpby_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, out, coef, gs,
                        gr, per_sample);
+  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+}
+
+// One step of DPM-Solver multistep sampling (DPMSolverMultistepScheduler: dpmsolver++ / dpmsolver, orders 1 and 2) in one launch:
+// the guidance combine, the guidance rescale, convert_model_output, the multistep update and the history. With coef = (p, q, A, B, D)
+// in device memory, u = eu, t = et, m1 = m_prev, per element and IN THIS ORDER (tests/multistep_bounds.py derives its bound from it;
+// which product fuses with which sum is the compiler's choice):
+//   c   = fma(gs, t - u, u)                      (et == nullptr: c = u)
+//   e   = c * k                                  (rescale form only; k of cfg_rescale_factor)
+//   m0  = p * x + q * e                          -> m_out
+//   out = A * x + B * m0 + D * (m0 - m1)         the difference is formed first, as the reference forms it: D carries 1 / r, and
+//                                                (B + D) * m0 - D * m1 would cancel
+// D == 0 (a first-order step: the first one, solver_order 1, lower_order_final / euler_at_final) is a uniform branch on the device
+// value: m_prev is NOT read then -- a fresh loop's history is uninitialised, and 0 * NaN would poison the latents -- and
+// out = A * x + B * m0. x / out and m_prev / m_out are read and written by the same lane at the same element, in the last pass
+// only: out may be x and m_out may be m_prev (one history buffer).
+struct MsCoef {
+  float p, q, A, B, D;
+};
+
+__device__ __forceinline__ void multistep_elem(const MsCoef& k, bool second, float x, float e, float m1, float& o, float& m0) {
+  m0 = k.p * x + k.q * e;
+  o = k.A * x + k.B * m0;
+  if (second) o += k.D * (m0 - m1);
+}
+
+// gr == 0 (or no guidance): elementwise. nv 16-byte vectors first (0 when a pointer is not 16-byte aligned), then the elements
+// 4 * nv .. n - 1 one by one: nothing past n is read or written.
+template <bool CFG>
+__global__ void multistep_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et, const float* m_prev,
+                                 float* out, float* m_out, const float* __restrict__ coef, float gs, long nv, long n) {
+  const MsCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4]};
+  const bool second = k.D != 0.0f;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et),
+              *p4 = reinterpret_cast<const f32x4*>(m_prev);
+  f32x4 *o4 = reinterpret_cast<f32x4*>(out), *m4 = reinterpret_cast<f32x4*>(m_out);
+  for (long i = gid; i < nv; i += stride) {
+    const f32x4 xv = x4[i], uv = u4[i];
+    f32x4 tv = uv, pv = {0.f, 0.f, 0.f, 0.f}, ov, mv;
+    if (CFG) tv = t4[i];
+    if (second) pv = p4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float o, m0;
+      multistep_elem(k, second, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], pv[j], o, m0);
+      ov[j] = o, mv[j] = m0;
+    }
+    o4[i] = ov;
+    m4[i] = mv;
+  }
+  for (long i = 4 * nv + gid; i < n; i += stride) {
+    const float u = eu[i];
+    float o, m0;
+    multistep_elem(k, second, x[i], CFG ? cfg_mix(u, et[i], gs) : u, second ? m_prev[i] : 0.f, o, m0);
+    out[i] = o;
+    m_out[i] = m0;
+  }
+}
+
+// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the update in the last pass
+template <bool RESIDENT>
+__global__ __launch_bounds__(CRA_THREADS) void multistep_rescale_kernel(const float* x, const float* __restrict__ eu,
+                                                                        const float* __restrict__ et, const float* m_prev, float* out,
+                                                                        float* m_out, const float* __restrict__ coef, float gs, float gr,
+                                                                        long n) {
+  __shared__ float part[2][CRA_THREADS / 64];
+  const long base = (long)blockIdx.x * n;
+  x += base, eu += base, et += base, m_prev += base, out += base, m_out += base;
+  const MsCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4]};
+  const bool second = k.D != 0.0f;
+  const int tid = threadIdx.x;
+  constexpr int R = RESIDENT ? CRA_RES : 1;
+  float cv[R];
+  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = tid + j * CRA_THREADS;
+      if (i < n) {
+        float o, m0;
+        multistep_elem(k, second, x[i], cv[j] * scale, second ? m_prev[i] : 0.f, o, m0);
+        out[i] = o;
+        m_out[i] = m0;
+      }
+    }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS) {
+      float o, m0;
+      multistep_elem(k, second, x[i], cfg_mix(eu[i], et[i], gs) * scale, second ? m_prev[i] : 0.f, o, m0);
+      out[i] = o;
+      m_out[i] = m0;
+    }
+  }
+}
+
+int launch_multistep_update(const float* x, const float* eu, const float* et, const float* m_prev, float* out, float* m_out,
+                            const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  if (batch <= 0 || per_sample < 1) return SD_ERR_INVALID;
+  if (et && gr > 0.0f) {
+    if (per_sample < 2) return SD_ERR_INVALID;
+    if (per_sample <= (long)CRA_THREADS * CRA_RES)
+      hipLaunchKernelGGL(multistep_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, m_prev, out, m_out,
+                         coef, gs, gr, per_sample);
+    else
+      hipLaunchKernelGGL(multistep_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, m_prev, out,
+                         m_out, coef, gs, gr, per_sample);
+    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  }
+  const long n = (long)batch * per_sample;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)m_prev | (uintptr_t)out | (uintptr_t)m_out;
+  const long nv = (bits & 15) ? 0 : n / 4;
+  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
+  long nb = (work + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  if (et)
+    hipLaunchKernelGGL(multistep_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, m_prev, out, m_out, coef, gs, nv, n);
+  else
+    hipLaunchKernelGGL(multistep_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, m_prev, out, m_out, coef, gs, nv, n);
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 

@@ -357,6 +357,36 @@ def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Ten
     return out
 
 
+def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], m_prev: Tensor, coef: Tensor, guidance_scale: float,
+                     guidance_rescale: float = 0.0, out: Optional[Tensor] = None, m_out: Optional[Tensor] = None):
+    """One DPM-Solver multistep step in one launch -> (out, m_out). x, eps_uncond, eps_text (None: no guidance), m_prev: contiguous
+    fp32 [B, ...] of one shape; coef: fp32 GPU (p, q, A, B, D) of ``DPMSolverMultistepScheduler.multistep_coefficients``. With e
+    the guided (and, with guidance_rescale > 0, rescaled) model output: m_out = p x + q e, out = A x + B m_out + D (m_out - m_prev);
+    D == 0 does not read m_prev. out may be x and m_out may be m_prev."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
+        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
+    rescale = eps_text is not None and guidance_rescale > 0.0
+    if rescale and x.numel() // x.shape[0] < 2:
+        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
+    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (m_prev, "m_prev"), (out, "out"), (m_out, "m_out")):
+        if t is None and name in ("eps_text", "out", "m_out"):
+            continue
+        _flat_f32(t, name, x.numel())
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 5 or \
+            not coef.is_contiguous():
+        raise ValueError("coef: expected a contiguous fp32 GPU tensor (p, q, A, B, D)")
+    out = torch.empty_like(x) if out is None else out
+    m_out = torch.empty_like(x) if m_out is None else m_out
+    check(lib.mi355x_sd_multistep_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), m_prev.data_ptr(), out.data_ptr(),
+                                         m_out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale),
+                                         x.shape[0], x.numel() // x.shape[0], _stream()))
+    return out, m_out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

@@ -88,28 +88,45 @@ class StableDiffusionDenoiser(_VaeSwitches):
                              f"{cfg.projection_class_embeddings_input_dim}, but a vector of {passed} was created.")
         return torch.tensor([ids], dtype=torch.float32, device=device)
 
-    def _fused_plan(self, rescale: bool, device):
-        """(per-step input scales, device table of (a, b), library, stream getter) when the scheduler's step is the
-        linear update ``prev = a * x + b * model_output`` (``step_coefficients``: epsilon and v prediction); None -> the generic
-        torch path. ``rescale``: the loop will call ``mi355x_sd_cfg_rescale_axpby``. The library always has it (its ABI version
-        is checked at load); a test backend written before that entry keeps the generic path."""
+    def _fused_plan(self, rescale: bool, device, timesteps=None):
+        """(per-step input scales, device table of coefficients, library, stream getter) when the scheduler's step is a linear
+        update the library runs in one launch; None -> the generic torch path. Two forms:
+        ``step_coefficients`` (DDIM, Euler; epsilon and v prediction): ``prev = a * x + b * model_output``, a table [steps, 2] over
+        the scheduler's whole schedule, with ``rescale`` through ``mi355x_sd_cfg_rescale_axpby``;
+        ``multistep_coefficients`` (DPM-Solver multistep): (p, q, A, B, D) of ``mi355x_sd_multistep_update``, a table [steps, 5]
+        over ``timesteps``, the steps the loop will run (img2img starts inside the schedule with an empty history); scales is None.
+        The library always has both entries (its ABI version is checked at load); a test backend written before one keeps the
+        generic path."""
         sch = self.scheduler
-        if not hasattr(sch, "step_coefficients") or not hasattr(self.unet, "_lib"):
+        if not hasattr(self.unet, "_lib"):
             return None
-        if rescale and getattr(self.unet, "_emulated", False) and not hasattr(self.unet._lib, "mi355x_sd_cfg_rescale_axpby"):
+        emulated = getattr(self.unet, "_emulated", False)
+        if hasattr(sch, "multistep_coefficients"):
+            if emulated and not hasattr(self.unet._lib, "mi355x_sd_multistep_update"):
+                return None
+            try:
+                scales, coefs = None, [tuple(float(v) for v in sch.multistep_coefficients(t)) for t in timesteps]
+            except NotImplementedError:
+                return None
+            finally:   # as set_timesteps left it
+                sch._step_index, sch.lower_order_nums, sch.model_outputs = None, 0, [None] * sch.config.solver_order
+        elif not hasattr(sch, "step_coefficients"):
             return None
-        try:
-            scales, coefs = [], []
-            for t in sch.timesteps:
-                scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
-                coefs.append(tuple(float(v) for v in sch.step_coefficients(t)))   # Euler: advances the step index
-        except NotImplementedError:
+        elif rescale and emulated and not hasattr(self.unet._lib, "mi355x_sd_cfg_rescale_axpby"):
             return None
-        finally:
-            if hasattr(sch, "_step_index"):
-                sch._step_index = None
+        else:
+            try:
+                scales, coefs = [], []
+                for t in sch.timesteps:
+                    scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
+                    coefs.append(tuple(float(v) for v in sch.step_coefficients(t)))   # Euler: advances the step index
+            except NotImplementedError:
+                return None
+            finally:
+                if hasattr(sch, "_step_index"):
+                    sch._step_index = None
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
-        if getattr(self.unet, "_emulated", False):
+        if emulated:
             stream = lambda: 0  # noqa: E731
         else:
             stream = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
@@ -337,7 +354,8 @@ class StableDiffusionDenoiser(_VaeSwitches):
             w = torch.full((B,), float(guidance_scale) - 1.0, device=latents.device)
             unet_kw["timestep_cond"] = self.get_guidance_scale_embedding(w, embedding_dim=tc_dim)
         rescale = do_cfg and guidance_rescale > 0.0   # without CFG the reference applies no rescale (:886-888)
-        fused = self._fused_plan(rescale, latents.device) if fused_update and not eta else None
+        fused = self._fused_plan(rescale, latents.device, timesteps) if fused_update and not eta else None
+        history = None   # DPM-Solver multistep: the previous step's converted model output, kept on the device
         nine = inp is not None and cfg.in_channels != latents.shape[1]
 
         def control(x_in, t):
@@ -374,16 +392,26 @@ class StableDiffusionDenoiser(_VaeSwitches):
             latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
             if fused is not None:
                 # guidance combine (+ guidance rescale) + scheduler update as ONE device pass over the latents (mi355x_sd_cfg_axpby /
-                # cfg_rescale_axpby): the epsilon- or v-prediction step of Euler / DDIM(eta=0) is prev = a*x + b*model_output with
-                # per-step (a, b) kept in HBM
+                # cfg_rescale_axpby / multistep_update): the epsilon- or v-prediction step of Euler / DDIM(eta=0) is
+                # prev = a*x + b*model_output with per-step (a, b) kept in HBM; DPM-Solver multistep adds the history term
                 scales, coef, lib, stream = fused
-                scaled = latent_model_input * scales[i]
+                scaled = latent_model_input if scales is None else latent_model_input * scales[i]
                 noise_pred = self.unet(extend(scaled), t, encoder_hidden_states=prompt_embeds,
                                        added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kw, **control(scaled, t))[0]
                 lat = latents.contiguous()
                 out = torch.empty_like(lat)
                 n, cp = lat.numel(), coef.data_ptr() + 8 * i
-                if rescale:
+                if scales is None:
+                    # DPM-Solver multistep: guidance, rescale, convert_model_output, the update and the history shuffle as one
+                    # launch; row i - first of the (p, q, A, B, D) table. The first row has D = 0: the fresh history is not read.
+                    if history is None:
+                        history = torch.empty_like(lat)
+                    rc = lib.mi355x_sd_multistep_update(lat.data_ptr(), noise_pred.data_ptr(),
+                                                        noise_pred.data_ptr() + 4 * n if do_cfg else None, history.data_ptr(),
+                                                        out.data_ptr(), history.data_ptr(), coef.data_ptr() + 20 * (i - first),
+                                                        float(guidance_scale), float(guidance_rescale) if rescale else 0.0,
+                                                        lat.shape[0], n // lat.shape[0], stream())
+                elif rescale:
                     rc = lib.mi355x_sd_cfg_rescale_axpby(lat.data_ptr(), noise_pred.data_ptr(), noise_pred.data_ptr() + 4 * n,
                                                          out.data_ptr(), cp, float(guidance_scale), float(guidance_rescale),
                                                          lat.shape[0], n // lat.shape[0], stream())

@@ -13,6 +13,9 @@ Schedule tables are float32 numpy like the reference's float32 tensors; ``step``
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
 returns (a, b) -- DDIM and Euler, epsilon and v prediction -- so the latent update can run as the library's fused
 ``mi355x_sd_axpby`` / ``cfg_axpby`` / ``cfg_rescale_axpby`` inside a captured graph.
+The DPM-Solver multistep update is linear in two tensors, the sample and the previous step's converted model output:
+``DPMSolverMultistepScheduler.multistep_coefficients`` returns (p, q, A, B, D) with  m0 = p*sample + q*model_output ,
+prev = A*sample + B*m0 + D*(m0 - m1)  for the library's ``mi355x_sd_multistep_update``.
 """
 from __future__ import annotations
 
@@ -530,6 +533,49 @@ class DPMSolverMultistepScheduler:
             self.lower_order_nums += 1
         self._step_index += 1
         return _out(prev, return_dict)
+
+    def multistep_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
+        """(p, q, A, B, D) of this step's update as a linear map of the sample x, the model output e and the previous step's
+        converted output m1:  m0 = p x + q e  (``convert_model_output``),  prev = A x + B m0 + D (m0 - m1) ; D = 0 on a first-order
+        step. Advances ``_step_index`` and ``lower_order_nums`` as ``step`` does. Every schedule value (alpha_t, sigma_t, lambda, h and
+        the coefficient expressions) is the float32 numpy expression of ``step`` / ``convert_model_output``, so both see the same
+        numbers; the five are composed from them in float64. NotImplementedError when one of them is not finite (heun's 0 / 0 on
+        a Karras schedule's repeated last sigma, where ``step`` itself yields NaN)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        c, n, i = self.config, len(self.timesteps), self._step_index
+        lower_order_final = i == n - 1 and (c.euler_at_final or (c.lower_order_final and n < 15))
+        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[i]))
+        pt, pp, f = c.prediction_type, c.algorithm_type == "dpmsolver++", float
+        if pt not in ("epsilon", "sample", "v_prediction"):
+            raise NotImplementedError(f"prediction_type {pt}")
+        if pp:
+            p, q = (1.0 / a, -s / a) if pt == "epsilon" else (0.0, 1.0) if pt == "sample" else (a, -s)
+        else:
+            p, q = (0.0, 1.0) if pt == "epsilon" else (1.0 / s, -a / s) if pt == "sample" else (s, a)
+        at, st = self._sigma_to_alpha_sigma_t(self.sigmas[i + 1])
+        a0, s0 = self._sigma_to_alpha_sigma_t(self.sigmas[i])
+        lt, l0 = np.log(at) - np.log(st), np.log(a0) - np.log(s0)
+        h = lt - l0
+        A, B = (f(st / s0), -f(at * (np.exp(-h) - 1.0))) if pp else (f(at / a0), -f(st * (np.exp(h) - 1.0)))
+        D = 0.0
+        if not (c.solver_order == 1 or self.lower_order_nums < 1 or lower_order_final):
+            a1, s1 = self._sigma_to_alpha_sigma_t(self.sigmas[i - 1])
+            h_0 = l0 - (np.log(a1) - np.log(s1))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                r_inv = f(1.0 / (h_0 / h))
+                if c.solver_type == "midpoint":
+                    D = -f(0.5 * at * (np.exp(-h) - 1.0)) * r_inv if pp else -f(0.5 * st * (np.exp(h) - 1.0)) * r_inv
+                else:
+                    D = f(at * ((np.exp(-h) - 1.0) / h + 1.0)) * r_inv if pp else -f(st * ((np.exp(h) - 1.0) / h - 1.0)) * r_inv
+        if self.lower_order_nums < c.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
+        if not all(np.isfinite(v) for v in (p, q, A, B, D)):
+            raise NotImplementedError("a multistep coefficient of this step is not finite")
+        return p, q, A, B, D
 
     def add_noise(self, original_samples, noise, timesteps):
         a = torch.as_tensor(self.alphas_cumprod)[timesteps].to(original_samples.device)
