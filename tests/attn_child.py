@@ -7,7 +7,6 @@ line: per case worst err / bound, rel-L2, unwritten / overwritten element counts
 
   python tests/attn_child.py [case ...]     (no names: every case)
 """
-import json
 import math
 import os
 import sys
@@ -19,6 +18,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import attn_bounds as AB  # noqa: E402
 from tests import attn_cases as AC  # noqa: E402
+from tests.gpu_child import Routes, emit  # noqa: E402
 
 CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 CASES = {}        # name: (spec, family the route log must show, aligned O)
@@ -156,25 +156,9 @@ def run_case(name):
     return dict(ratio=ratio, rel=rel, unwritten=unwritten, overwritten=overwritten, same_v=same_v, zero_rows=zero_rows)
 
 
-class Routes:
-    """the lines launch_attention appended to MI355X_SD_ATTN_LOG since the last call (debug build; empty elsewhere)"""
-    def __init__(self):
-        self.path = os.environ.get("MI355X_SD_ATTN_LOG")
-        self.pos = 0
-
-    def take(self):
-        if not self.path or not os.path.exists(self.path):
-            return []
-        with open(self.path) as f:
-            f.seek(self.pos)
-            lines = f.read().splitlines()
-            self.pos = f.tell()
-        return lines
-
-
 def main(names):
     ops.init(0)
-    routes = Routes()
+    routes = Routes("MI355X_SD_ATTN_LOG")
     routes.take()
     res = {}
     for name in names or CASES:
@@ -182,7 +166,7 @@ def main(names):
         r["route"] = routes.take()
         res[name] = r
         torch.cuda.empty_cache()
-    print("ATTN_JSON " + json.dumps(res))
+    emit("ATTN_JSON", res)
 
 
 if __name__ == "__main__":

@@ -7,8 +7,6 @@ build) each case also reports the kernel family launch_gemm logged for it. One l
   python tests/conv_child.py direct              conv_in3x3, conv_out3x3, conv1x1_nchw (csrc/misc.hip)
   python tests/conv_child.py wide                one stride-2 conv whose source spans 6 GiB (32-bit offsets cannot address it)
 """
-import hashlib
-import json
 import math
 import os
 import sys
@@ -20,12 +18,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import conv_bounds as CB  # noqa: E402
 from tests import conv_cases as CC  # noqa: E402
-from tests.gemm_w4_child import Routes  # noqa: E402
-
-
-def sha(t):
-    t = t.contiguous().cpu()
-    return hashlib.sha256(t.view(torch.int32 if t.dtype == torch.float32 else torch.int16).numpy().tobytes()).hexdigest()[:16]
+from tests.gpu_child import Routes, emit, sha  # noqa: E402
 
 
 def run_gemm_case(name, ed):
@@ -43,7 +36,7 @@ def run_gemm_case(name, ed):
 
 def main_gemm(names):
     ed = _lib.elem_dtype()
-    routes = Routes()
+    routes = Routes("MI355X_SD_GEMM_LOG")
     routes.take()
     res = {}
     for name in names or CC.CASES:
@@ -207,7 +200,7 @@ def main_wide():
     x = full[..., 64:64 + Cin]
     w = (torch.randn(Cout, 9 * Cin, device="cuda", generator=g) / 24).to(ed)
     bias = torch.randn(Cout, device="cuda", generator=g)
-    routes = Routes()
+    routes = Routes("MI355X_SD_GEMM_LOG")
     routes.take()
     out = ops.conv3x3(x, CB.to_kb64(w), bias, stride=2, kb64=True)
     torch.cuda.synchronize()
@@ -224,4 +217,4 @@ if __name__ == "__main__":
     ops.init(0)
     mode = sys.argv[1]
     res = main_gemm(sys.argv[2:]) if mode == "gemm" else main_direct() if mode == "direct" else main_wide()
-    print("CONV_JSON " + json.dumps(res))
+    emit("CONV_JSON", res)

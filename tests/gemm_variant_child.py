@@ -1,7 +1,6 @@
 """Child of tests/test_gpu_gemm_variants.py: runs a few GEMM / conv launches under the MI355X_SD_GEMM_* switches of its environment
 (read once per process) and prints one JSON line: sha256 of every output + rel-L2 against fp32 torch math."""
 import hashlib
-import json
 import os
 import sys
 
@@ -11,26 +10,16 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
+from tests.gpu_child import Routes, emit  # noqa: E402
 
 ops.init(0)
 ed = _lib.elem_dtype()
-_log = os.environ.get("MI355X_SD_GEMM_LOG")   # (debug build: launch_gemm appends "M N K family" per launch)
-_log_pos = [0]
-
-
-def _routes():
-    if not _log or not os.path.exists(_log):
-        return []
-    with open(_log) as f:
-        f.seek(_log_pos[0])
-        lines = f.read().splitlines()
-        _log_pos[0] = f.tell()
-    return lines
+routes = Routes("MI355X_SD_GEMM_LOG")   # (debug build: launch_gemm appends "M N K family" per launch)
 
 
 class _Res(dict):   # each case's entry also lists the kernel families its launches took (the lines logged since the last case)
     def __setitem__(self, k, v):
-        super().__setitem__(k, dict(v, route=_routes()))
+        super().__setitem__(k, dict(v, route=routes.take()))
 
 
 res = _Res()
@@ -211,4 +200,4 @@ for M, N, K, kind in ((8200, 1536, 1536, "gate+R"), (4100, 6144, 1536, "gelu"), 
         got = out[rows].float()
     res[f"gemm fp8w {M}x{N}x{K} {kind}"] = dict(sha=hashlib.sha256(out.cpu().view(torch.int16).numpy().tobytes()).hexdigest()[:16],
                                                 rel=((got - ref).norm() / ref.norm()).item())
-print("VARIANT_JSON " + json.dumps(res))
+emit("VARIANT_JSON", res)

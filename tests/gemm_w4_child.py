@@ -5,8 +5,6 @@ launch_gemm logged for it. Prints one JSON line: per case sha256 of the output, 
 
   python tests/gemm_w4_child.py [case ...]     (no names: every case)
 """
-import hashlib
-import json
 import os
 import sys
 
@@ -17,6 +15,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from paddlemix_amd.sd3 import dequantize_fp8_rows, quantize_fp8_rows  # noqa: E402
 from tests import gemm_bounds as GB  # noqa: E402
+from tests.gpu_child import Routes, emit, sha  # noqa: E402
 
 CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 
@@ -65,10 +64,6 @@ CASES = {
     "strided": (8192, 1536, 640, "strided", True),
 }
 EXTRA = 154   # rows of other data between the batches of a remapped operand
-
-
-def sha(t):
-    return hashlib.sha256(t.contiguous().cpu().view(torch.int16).numpy().tobytes()).hexdigest()[:16]
 
 
 def run_case(name, ed):
@@ -138,26 +133,10 @@ def run_case(name, ed):
     return out, GB.bound_check(out, a, w_ref, bias=b, **bk), guard
 
 
-class Routes:
-    """the lines launch_gemm appended to MI355X_SD_GEMM_LOG since the last call (debug build; empty elsewhere)"""
-    def __init__(self):
-        self.path = os.environ.get("MI355X_SD_GEMM_LOG")
-        self.pos = 0
-
-    def take(self):
-        if not self.path or not os.path.exists(self.path):
-            return []
-        with open(self.path) as f:
-            f.seek(self.pos)
-            lines = f.read().splitlines()
-            self.pos = f.tell()
-        return lines
-
-
 def main(names):
     ops.init(0)
     ed = _lib.elem_dtype()
-    routes = Routes()
+    routes = Routes("MI355X_SD_GEMM_LOG")
     routes.take()
     res = {}
     for name in names or CASES:
@@ -165,7 +144,7 @@ def main(names):
         res[name] = dict(sha=sha(out), ratio=ratio, rel=rel, guard=guard, route=routes.take())
         del out
         torch.cuda.empty_cache()
-    print("W4_JSON " + json.dumps(res))
+    emit("W4_JSON", res)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,6 @@ element, the second must equal it bit for bit. Then a torch.cuda.graph replayed 
   python tests/guidance_child.py
 """
 import ctypes
-import json
 import os
 import sys
 
@@ -17,6 +16,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import guidance_bounds as GB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
+from tests.gpu_child import emit  # noqa: E402
 from tests.norm_child import CANARY32, _canary, _counts  # noqa: E402
 from tests.rowmap_child import _flat_in  # noqa: E402
 
@@ -155,7 +155,7 @@ def main():
                 _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
             res[name] = {"error": f"{type(ex).__name__}: {ex}"}
         torch.cuda.empty_cache()
-    print("GUIDANCE_JSON " + json.dumps(res))
+    emit("GUIDANCE_JSON", res)
 
 
 if __name__ == "__main__":

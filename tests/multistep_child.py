@@ -6,7 +6,6 @@ rows (D != 0 and D = 0), the refusals, and a 6-step pipeline run. Prints one JSO
   python tests/multistep_child.py            every case, the graph, the refusals, the pipeline
   python tests/multistep_child.py pipeline   the pipeline alone (the build MI355X_SD_DTYPE selects)
 """
-import json
 import os
 import sys
 import time
@@ -18,6 +17,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import multistep_bounds as MB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
+from tests.gpu_child import emit  # noqa: E402
 from tests.guidance_child import _graph_shape  # noqa: E402
 from tests.norm_child import CANARY32, _canary, _counts  # noqa: E402
 from tests.rowmap_child import _flat_in  # noqa: E402
@@ -184,7 +184,7 @@ def main():
             res[name] = {"error": f"{type(ex).__name__}: {ex}"}
         torch.cuda.empty_cache()
     res["seconds"] = round(time.time() - t0, 1)
-    print("MULTISTEP_JSON " + json.dumps(res))
+    emit("MULTISTEP_JSON", res)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ side outputs), unwritten / overwritten element counts, bit checks, route.
 
   python tests/norm_child.py [case ...]     (no names: every case)
 """
-import json
 import os
 import sys
 
@@ -17,6 +16,7 @@ import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import norm_bounds as NB  # noqa: E402
+from tests.gpu_child import Routes, emit  # noqa: E402
 
 CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 CANARY32 = 0x7FA5A5A5
@@ -440,25 +440,9 @@ def run_case(name):
     return res
 
 
-class Routes:
-    """the lines the launchers appended to MI355X_SD_NORM_LOG since the last call (debug build; empty elsewhere)"""
-    def __init__(self):
-        self.path = os.environ.get("MI355X_SD_NORM_LOG")
-        self.pos = 0
-
-    def take(self):
-        if not self.path or not os.path.exists(self.path):
-            return []
-        with open(self.path) as f:
-            f.seek(self.pos)
-            lines = f.read().splitlines()
-            self.pos = f.tell()
-        return lines
-
-
 def main(names):
     ops.init(0)
-    routes = Routes()
+    routes = Routes("MI355X_SD_NORM_LOG")
     routes.take()
     res = {}
     for name in names or CASES:
@@ -466,7 +450,7 @@ def main(names):
         r["route"] = routes.take()
         res[name] = r
         torch.cuda.empty_cache()
-    print("NORM_JSON " + json.dumps(res))
+    emit("NORM_JSON", res)
 
 
 if __name__ == "__main__":

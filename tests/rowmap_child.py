@@ -8,7 +8,6 @@ case the worst err / bound or the number of differing elements, and the unwritte
 
   python tests/rowmap_child.py [case ...]     (no names: every case)
 """
-import json
 import os
 import sys
 
@@ -18,6 +17,7 @@ import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
+from tests.gpu_child import emit  # noqa: E402
 from tests.norm_child import CANARY, CANARY32, _canary, _counts, _nan_rows  # noqa: E402
 
 CASES = {}   # name: (family, spec)
@@ -365,7 +365,7 @@ def main(names):
             # a refusal or a mistake of the case's own host code: reported as that case's failure (a device error ends the child)
             res[name] = {"error": f"{type(ex).__name__}: {ex}"}
         torch.cuda.empty_cache()
-    print("ROWMAP_JSON " + json.dumps(res))
+    emit("ROWMAP_JSON", res)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,6 @@
 per process) -- attention on the short-key / two-query-tile / wide-store paths, a small-M GEMM that takes split-K slices, GroupNorm
 on the one-launch path -- and a mini-SDXL UNet forward. Prints one JSON line: sha256 of every output + rel-L2 against fp32 math."""
 import hashlib
-import json
 import os
 import sys
 
@@ -11,6 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
+from tests.gpu_child import emit  # noqa: E402
 
 ops.init(0)
 ed = _lib.elem_dtype()
@@ -56,4 +56,4 @@ xf = x.float().reshape(2, 32 * 32, 32, 20)
 mu, var = xf.mean((1, 3), keepdim=True), xf.var((1, 3), unbiased=False, keepdim=True)
 yr = ((xf - mu) / (var + 1e-5).sqrt()).reshape(2, 32 * 32, 640) * gamma + beta
 put("groupnorm_silu 2x1024x640", y, yr * torch.sigmoid(yr))
-print("SWITCH_JSON " + json.dumps(res))
+emit("SWITCH_JSON", res)

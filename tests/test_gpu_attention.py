@@ -3,19 +3,12 @@ tests/attn_bounds.py, on the inputs of tests/attn_cases.py that make that bound 
 selectors, Skv = 1, random data), over the WHOLE output of each case. The case matrix lives in tests/attn_child.py and runs in a
 child process: once on the debug-switch build with MI355X_SD_ATTN_LOG, whose route log proves each case reached the kernel it is
 named for and that the cases together reach every instantiation, once on the IEEE-half build (values only)."""
-import json
-import os
-import subprocess
-import sys
-import tempfile
-
 import pytest
 
 from tests.attn_child import CASES
+from tests.gpu_child import RUNNER
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 
 # every kernel instantiation launch_dp can launch, by its route-log name (the debug build's timing form of the 16x16x32 kernel,
 # MI355X_SD_ATTN_STAMP, excepted: it is the m16+log2 kernel writing clock stamps into q)
@@ -32,30 +25,16 @@ INSTANTIATIONS = [
 NOM16 = [n for n in CASES if n.startswith("nom16")]
 
 
-def _child(env_extra, names):
-    with tempfile.TemporaryDirectory() as td:
-        env = dict(os.environ, **env_extra)
-        if env_extra.get("MI355X_SD_LIB") == "dbg":   # (the route log exists in the debug-switch build only)
-            env.update(MI355X_SD_ATTN_LOG=os.path.join(td, "attn.log"))
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "attn_child.py"), *names], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=900)
-    if p.returncode != 0:
-        return p.stderr[-3000:]
-    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("ATTN_JSON ")][-1][len("ATTN_JSON "):])
+def _child(env_extra, names, dbg):
+    return RUNNER.run("attn_child.py", names, env_extra, tag="ATTN_JSON", timeout=900, dbg=dbg, route_log="MI355X_SD_ATTN_LOG")
 
 
 def _run(dtype):
-    """every case's result; the child runs once per build (a failed child is remembered, not run again per test)"""
-    if dtype not in _CACHE:
-        if dtype == "bf16":
-            got = _child({"MI355X_SD_LIB": "dbg"}, [n for n in CASES if n not in NOM16])
-            more = _child({"MI355X_SD_LIB": "dbg", "MI355X_SD_ATTN_NO_M16": "1"}, NOM16) if isinstance(got, dict) else got
-            _CACHE[dtype] = dict(got, **more) if isinstance(more, dict) else more
-        else:
-            _CACHE[dtype] = _child({"MI355X_SD_DTYPE": dtype}, [])
-    got = _CACHE[dtype]
-    assert isinstance(got, dict), got
-    return got
+    """every case's result; a child runs once (tests/gpu_child.py: a failed child is remembered, not run again per test)"""
+    if dtype == "bf16":
+        got = _child({}, [n for n in CASES if n not in NOM16], True)
+        return dict(got, **_child({"MI355X_SD_ATTN_NO_M16": "1"}, NOM16, True))   # (started only after the first child gave its result)
+    return _child({"MI355X_SD_DTYPE": dtype}, [], False)
 
 
 def _check(name, v, rel_bar):

@@ -7,54 +7,20 @@ tests/conv_bounds.py), stride 1 / 2, upsample, both padding rules, both K orders
 NaN buffer, the output in a canary buffer -- runs under every forced tile family of the debug-switch build, with and without the
 pipelined loops, with and without split-K, and under the picker; the MI355X_SD_GEMM_LOG route of every case must be the family the
 run names or its tabled fallback. The three direct kernels of csrc/misc.hip have their own selectors and bounds."""
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import threading
-import time
-from concurrent.futures import ThreadPoolExecutor
-
 import pytest
 
 from tests.conv_cases import CASES, GEOMS, out_hw
+from tests.gpu_child import RUNNER
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 WS_BYTES = 32 << 20   # the split-K scratch ops.conv3x3 hands over (paddlemix_amd/ops.py _workspace)
 # bias after the sum on both sides, as in tests/test_gpu_gemm_variants.py: then a tile's pipelined and generic loops give the same bits
 FORCED_BASE = {"MI355X_SD_GEMM_NO_BIAS_ACC": "1"}
 
 
-_DEAD = threading.Event()   # set by the worker that sees a child die on the GPU: from then on no child is started
-
-
-def _died(rc):
-    return rc < 0 or rc in (124, 134, 137, 139)   # a signal, a time limit, an abort, a segmentation fault
-
-
-def _child(mode, env_extra, names, dbg):
-    """one child run -> dict(rc, out, err, dt), or None (nothing started) once a child has died on the GPU. A child that exceeds its
-    time limit counts as dead (status 124)."""
-    if _DEAD.is_set():
-        return None
-    t0 = time.time()
-    with tempfile.TemporaryDirectory() as td:
-        env = dict(os.environ, **env_extra)
-        if dbg:   # (the switches and the route log exist in the debug-switch build only)
-            env.update(MI355X_SD_LIB="dbg", MI355X_SD_GEMM_LOG=os.path.join(td, "gemm.log"))
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "conv_child.py"), mode, *names], env=env, cwd=ROOT,
-                               capture_output=True, text=True, timeout=600)
-            got = dict(rc=p.returncode, out=p.stdout, err=p.stderr)
-        except subprocess.TimeoutExpired as e:
-            got = dict(rc=124, out="", err=f"time limit: {e}")
-    if _died(got["rc"]):
-        _DEAD.set()
-    got["dt"] = time.time() - t0
-    return got
+def _spec(mode, env_extra, names=(), dbg=True):
+    return dict(script="conv_child.py", args=(mode, *names), env_extra=env_extra, tag="CONV_JSON", timeout=600, dbg=dbg,
+                route_log="MI355X_SD_GEMM_LOG")
 
 
 def _all_runs():
@@ -63,33 +29,12 @@ def _all_runs():
                ("direct", {"MI355X_SD_DTYPE": "fp16"}, (), False), ("wide", {}, (), True)])
 
 
-def _key(mode, env_extra, names, dbg):
-    return (mode, tuple(sorted(env_extra.items())), tuple(names), dbg)
-
-
 def _run(mode, env_extra, names=(), dbg=True):
     """the child's JSON. The children of this file are independent processes (the switches are read once per process); the first call
-    runs all of them, four at a time, each under its own time limit, and records a result for every one. The worker that sees a child
-    die on the GPU (a signal, an abort, a time limit) sets _DEAD before it returns: no worker starts a child after that, the children
-    not run are recorded as None, and every later call ends the session instead of starting anything."""
-    if not _CACHE:
-        specs = _all_runs()
-        with ThreadPoolExecutor(max_workers=4) as pool:
-            for spec, got in zip(specs, pool.map(lambda sp: _child(*sp), specs)):
-                _CACHE[_key(*spec)] = got
-    key = _key(mode, env_extra, names, dbg)
-    if key not in _CACHE:
-        _CACHE[key] = _child(mode, env_extra, names, dbg)
-    got = _CACHE[key]
-    if got is None:
-        pytest.exit("a conv_child died on the GPU: nothing more is started on it", returncode=3)
-    if "json" not in got:
-        if _died(got["rc"]):
-            pytest.exit(f"conv_child {mode} {env_extra} died with status {got['rc']}: {got['err'][-2000:]}", returncode=3)
-        assert got["rc"] == 0, got["err"][-3000:]
-        got["json"] = json.loads([ln for ln in got["out"].splitlines() if ln.startswith("CONV_JSON ")][-1][len("CONV_JSON "):])
-        print(f"[child {mode} {env_extra} {'dbg' if dbg else 'production'}: {got['dt']:.1f} s]")
-    return got["json"]
+    starts all of them, four at a time, each under its own time limit; after a child that died on the GPU none is started and the
+    session ends (tests/gpu_child.py)."""
+    RUNNER.run_many([_spec(*sp) for sp in _all_runs()], workers=4)
+    return RUNNER.run(**_spec(mode, env_extra, names, dbg))
 
 
 def _mnk(case):

@@ -1,19 +1,11 @@
 """-m gpu: every selectable variant of the software-pipelined GEMM loops (csrc/gemm_pipe.hip) runs on the hardware in the suite, not
 only the default, and the loops are held to an independent implementation: the generic loop of csrc/gemm.hip
 (MI355X_SD_NO_PIPE=1). The variants change WHEN operands are staged and fetched, never the accumulation order: bit-identical."""
-import json
-import os
-import subprocess
-import sys
-import tempfile
-
 import pytest
 
+from tests.gpu_child import RUNNER
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-_CACHE = {}
 W4_REF = {"MI355X_SD_GEMM_TILE": "256", "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_NO_BIAS_ACC": "1", "MI355X_SD_NO_SPLITK": "1",
           "MI355X_SD_NO_W4": "1"}
 
@@ -22,20 +14,8 @@ def _bar(key):   # rel-L2 of a case against its fp32 reference (16-bit stores)
     return 4e-3
 
 
-def _run(env_extra):
-    key = tuple(sorted(env_extra.items()))
-    if key not in _CACHE:
-        _CACHE[key] = _run_child(env_extra)
-    return _CACHE[key]
-
-
-def _run_child(env_extra):
-    with tempfile.TemporaryDirectory() as td:   # (MI355X_SD_GEMM_LOG: the kernel family of every launch, reported per case)
-        env = dict(os.environ, MI355X_SD_LIB="dbg", MI355X_SD_GEMM_LOG=os.path.join(td, "gemm.log"), **env_extra)   # the A/B switches exist in the debug-switch build only
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gemm_variant_child.py")], env=env, cwd=ROOT, capture_output=True,
-                           text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-3000:]
-    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("VARIANT_JSON ")][-1][len("VARIANT_JSON "):])
+def _run(env_extra):   # the A/B switches exist in the debug-switch build only; MI355X_SD_GEMM_LOG: the kernel family of every launch, per case
+    return RUNNER.run("gemm_variant_child.py", (), env_extra, tag="VARIANT_JSON", timeout=600, dbg=True, route_log="MI355X_SD_GEMM_LOG")
 
 
 def test_epilogue_operand_variants():

@@ -6,39 +6,23 @@ bias added after the sum, the epilogue operands in the same order -> the same bi
 (id 258) and 256 x 160 (id 259), and the picker's own choice. Every case of tests/gemm_w4_child.py is also held to the elementwise
 float64 bound of tests/gemm_bounds.py over its whole output (both sides), and its MI355X_SD_GEMM_LOG route proves it reached the
 kernel it is named for (four-wave on the new side, the generic 256 x 256 loop on the reference side)."""
-import json
 import math
-import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
 
 from tests import gemm_bounds as GB
 from tests.gemm_w4_child import CASES
+from tests.gpu_child import RUNNER
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = {"MI355X_SD_GEMM_TILE": "256", "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_NO_BIAS_ACC": "1", "MI355X_SD_NO_SPLITK": "1",
        "MI355X_SD_NO_W4": "1"}
 REL_BAR = 4e-3   # rel-L2 bar of the GEMM variant cases (tests/test_gpu_gemm_variants.py), bf16 stores
-_CACHE = {}
 
 
 def _run(env_extra, names=(), dbg=True):
-    key = (tuple(sorted(env_extra.items())), tuple(names), dbg)
-    if key not in _CACHE:
-        with tempfile.TemporaryDirectory() as td:
-            env = dict(os.environ, **env_extra)
-            if dbg:   # (the switches and the route log exist in the debug-switch build only)
-                env.update(MI355X_SD_LIB="dbg", MI355X_SD_GEMM_LOG=os.path.join(td, "gemm.log"))
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gemm_w4_child.py"), *names], env=env, cwd=ROOT,
-                               capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-3000:]
-        _CACHE[key] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("W4_JSON ")][-1][len("W4_JSON "):])
-    return _CACHE[key]
+    return RUNNER.run("gemm_w4_child.py", names, env_extra, tag="W4_JSON", timeout=600, dbg=dbg, route_log="MI355X_SD_GEMM_LOG")
 
 
 def _family(name, bn):

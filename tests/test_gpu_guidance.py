@@ -3,34 +3,16 @@ tests/guidance_bounds.py. The matrix lives in tests/guidance_child.py and runs o
 every case inside the elementwise float64 bound over the whole output and bit-identical on a second launch, canaries around every
 output; one launch captured in a torch.cuda.graph and replayed with two coefficient rows; the refusals; a 4-step v-prediction Euler
 loop with CFG and guidance_rescale on the tiny SD config, fused against generic to the accumulated bound."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.gpu_child import RUNNER
 from tests.guidance_bounds import CASES
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 
 
 def _run():
-    if "got" not in _CACHE:
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "guidance_child.py")], cwd=ROOT, capture_output=True, text=True,
-                               timeout=240)
-            if p.returncode != 0:
-                _CACHE["got"] = f"the child ended with {p.returncode}\n{p.stderr[-3000:]}"
-            else:
-                _CACHE["got"] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("GUIDANCE_JSON ")][-1][len("GUIDANCE_JSON "):])
-        except subprocess.TimeoutExpired:
-            _CACHE["got"] = "the child ran out of its time limit"
-    got = _CACHE["got"]
-    assert isinstance(got, dict), got
-    return got
+    return RUNNER.run("guidance_child.py", tag="GUIDANCE_JSON", timeout=240)
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -8,37 +8,18 @@ config, fused against generic to the accumulated bound, on both element types (t
 The time limit is that of tests/test_gpu_guidance.py for its 14 entries (240 s) scaled to the 24 entries here: 400 s; the children
 print their own wall time (measured on the MI355X: 1.2 s after the imports for the full matrix, 0.4 s for the pipeline
 alone)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.gpu_child import RUNNER
 from tests.multistep_bounds import CASES
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 
 
 def _run(which="all"):
-    if "dead" in _CACHE and which not in _CACHE:   # nothing is started after a child that died
-        _CACHE[which] = "not started: " + _CACHE["dead"]
-    if which not in _CACHE:
-        args, env = ([], dict(os.environ)) if which == "all" else (["pipeline"], dict(os.environ, MI355X_SD_DTYPE="fp16"))
-        try:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "multistep_child.py")] + args, cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=400 if which == "all" else 240)
-            if p.returncode != 0:
-                _CACHE[which] = _CACHE["dead"] = f"the child ended with {p.returncode}\n{p.stderr[-3000:]}"
-            else:
-                _CACHE[which] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("MULTISTEP_JSON ")][-1][len("MULTISTEP_JSON "):])
-        except subprocess.TimeoutExpired:
-            _CACHE[which] = _CACHE["dead"] = "the child ran out of its time limit"
-    got = _CACHE[which]
-    assert isinstance(got, dict), got
-    return got
+    if which == "all":
+        return RUNNER.run("multistep_child.py", tag="MULTISTEP_JSON", timeout=400)
+    return RUNNER.run("multistep_child.py", ("pipeline",), {"MI355X_SD_DTYPE": "fp16"}, tag="MULTISTEP_JSON", timeout=240)
 
 
 @pytest.mark.parametrize("name", list(CASES))

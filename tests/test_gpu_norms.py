@@ -5,19 +5,12 @@ edges: large mean offsets, 50 sigma outliers at and away from the statistics' pi
 make waves loop, NaN in every row gap. The case matrix lives in tests/norm_child.py and runs in a child process: once on the
 debug-switch build with MI355X_SD_NORM_LOG, whose route log proves each case reached the instantiation it is named for and that the
 cases together reach all 38, once on the IEEE-half build (values only)."""
-import json
-import os
-import subprocess
-import sys
-import tempfile
-
 import pytest
 
+from tests.gpu_child import RUNNER
 from tests.norm_child import CASES
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 
 # every kernel instantiation of the launchers, as "entry NCH ROWS flags" of the route log
 INSTANTIATIONS = (
@@ -33,25 +26,10 @@ INSTANTIATIONS = (
     + [f"fused_adaln {n} 1 {m}" for n in (2, 4, 8) for m in ("m16", "m32")])                          # fused_adaln_scale_residual_kernel<NCH, M16>
 
 
-def _child(env_extra):
-    with tempfile.TemporaryDirectory() as td:
-        env = dict(os.environ, **env_extra)
-        if env_extra.get("MI355X_SD_LIB") == "dbg":   # (the route log exists in the debug-switch build only)
-            env.update(MI355X_SD_NORM_LOG=os.path.join(td, "norm.log"))
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "norm_child.py")], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=900)
-    if p.returncode != 0:
-        return p.stderr[-3000:]
-    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("NORM_JSON ")][-1][len("NORM_JSON "):])
-
-
 def _run(dtype):
-    """every case's result; the child runs once per build (a failed child is remembered, not run again per test)"""
-    if dtype not in _CACHE:
-        _CACHE[dtype] = _child({"MI355X_SD_LIB": "dbg"} if dtype == "bf16" else {"MI355X_SD_DTYPE": dtype})
-    got = _CACHE[dtype]
-    assert isinstance(got, dict), got
-    return got
+    """every case's result; the child runs once per build (tests/gpu_child.py: a failed child is remembered, not run again per test)"""
+    return RUNNER.run("norm_child.py", (), {} if dtype == "bf16" else {"MI355X_SD_DTYPE": dtype}, tag="NORM_JSON", timeout=900,
+                      dbg=dtype == "bf16", route_log="MI355X_SD_NORM_LOG")
 
 
 def _check(name, v):

@@ -5,48 +5,23 @@ unpatchify, split_concat, embed_tokens, add_nchw, mask_to_bias, latent_dist's mo
 coded inputs for the layout kernels. Every output sits in a canary buffer, every input gap holds NaN, every grid-stride loop takes
 a second, ragged trip. The matrix lives in tests/rowmap_child.py and runs in a child process, once on the bf16 library and once
 with MI355X_SD_DTYPE=fp16 (the bounds at fp16's u_out, where the activation bounds are tight enough to separate the GELU forms).
-The children run one after another, each under its own time limit; after one that died of a signal or ran out of time no other
-is started. The wrappers' argument checks are tested here too: each refusal must raise ValueError and leave a canary output
-untouched."""
-import json
-import os
-import subprocess
-import sys
-
+The children run one after another, each under its own time limit; one that dies of a signal or runs out of time ends the whole
+pytest session with status 3 (tests/gpu_child.py). The wrappers' argument checks are tested here too: each refusal must raise
+ValueError and leave a canary output untouched."""
 import pytest
 import torch
 
+from tests.gpu_child import RUNNER
 from tests.rowmap_child import CASES
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 FAMILY = {"silu": "activations", "act": "activations", "gated": "activations", "softmax": "softmax_rows", "temb": "timestep_embedding",
           "axpby": "axpby / cfg_axpby", "cfg": "axpby / cfg_axpby", "latent": "latent_dist"}
 
 
-def _child(dtype):
-    env = dict(os.environ, MI355X_SD_DTYPE=dtype)
-    try:
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "rowmap_child.py")], env=env, cwd=ROOT, capture_output=True,
-                           text=True, timeout=300)
-    except subprocess.TimeoutExpired:
-        return "DEAD: the child ran out of its time limit"
-    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
-        return f"DEAD: the child ended with {p.returncode}\n{p.stderr[-3000:]}"
-    if p.returncode != 0:
-        return p.stderr[-3000:]
-    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("ROWMAP_JSON ")][-1][len("ROWMAP_JSON "):])
-
-
 def _run(dtype):
-    """every case's result on one build; a child runs once, and none is started after one that died"""
-    if dtype not in _CACHE:
-        dead = [v for v in _CACHE.values() if isinstance(v, str) and v.startswith("DEAD")]
-        _CACHE[dtype] = "not started: an earlier child died\n" + dead[0] if dead else _child(dtype)
-    got = _CACHE[dtype]
-    assert isinstance(got, dict), got
-    return got
+    """every case's result on one build; a child runs once"""
+    return RUNNER.run("rowmap_child.py", (), {"MI355X_SD_DTYPE": dtype}, tag="ROWMAP_JSON", timeout=300)
 
 
 def _check(name, v):

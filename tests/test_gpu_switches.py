@@ -12,32 +12,18 @@ result within the kernels' own tolerance; the ones that only change HOW a result
   MI355X_SD_NO_WIDEN_F8    weight-only fp8: e4m3 bytes widened in the generic loop's fragment load (what small-M launches do)
                            instead of once, just in time, in front of the pipelined 16-bit kernels (same products, same K
                            order; the bias enters as the accumulators' initial value there: equal to fp32 rounding)"""
-import json
 import os
-import subprocess
-import sys
 import tempfile
 
 import pytest
 
+from tests.gpu_child import RUNNER
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
 
 
-def _run(env_extra):
-    key = tuple(sorted(env_extra.items()))
-    if key not in _CACHE:
-        env = dict(os.environ)
-        env.update(MI355X_SD_LIB="dbg")
-        env.update(env_extra)
-        if env_extra.get("MI355X_SD_LIB") == "":   # (the production library)
-            env.pop("MI355X_SD_LIB")
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "switch_child.py")], env=env, cwd=ROOT,
-                           capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-3000:]
-        _CACHE[key] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("SWITCH_JSON ")][-1][len("SWITCH_JSON "):])
-    return _CACHE[key]
+def _run(env_extra, dbg=True):   # (dbg=False: the production library)
+    return RUNNER.run("switch_child.py", (), env_extra, tag="SWITCH_JSON", timeout=600, dbg=dbg)
 
 
 M16 = {"MI355X_SD_ATTN_NO_M16": "1"}
@@ -72,7 +58,7 @@ def test_production_library_ignores_the_switches():
              "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_LOG": os.path.join(tempfile.mkdtemp(), "gemm.log"),
              "MI355X_SD_ATTN_LOG": os.path.join(tempfile.mkdtemp(), "attn.log"),
              "MI355X_SD_NORM_LOG": os.path.join(tempfile.mkdtemp(), "norm.log")}
-    prod_clean, prod_env = _run({"MI355X_SD_LIB": ""}), _run(dict(every, MI355X_SD_LIB=""))
+    prod_clean, prod_env = _run({}, dbg=False), _run(every, dbg=False)
     assert not os.path.exists(every["MI355X_SD_GEMM_LOG"])   # (the route logs: debug build only)
     assert not os.path.exists(every["MI355X_SD_ATTN_LOG"])
     assert not os.path.exists(every["MI355X_SD_NORM_LOG"])
