@@ -18,7 +18,7 @@ from typing import Dict, Mapping, Optional
 import torch
 
 from . import _lib
-from .program import WORKSPACE_BYTES
+from .program import WORKSPACE_BYTES, crossing
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
@@ -225,9 +225,7 @@ class CUNet2DConditionModel:
         if added_cond_kwargs is not None:
             te = f32(added_cond_kwargs["text_embeds"]) if "text_embeds" in added_cond_kwargs else None
             ti = f32(added_cond_kwargs["time_ids"]) if "time_ids" in added_cond_kwargs else None
-        cur = torch.cuda.current_stream(self.device)
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
+        with crossing(self._stream, self.device):
             s, tt, e = f32(sample), f32(t.reshape(-1)[:1]), f32(encoder_hidden_states)
             sc = None if in_scale is None else f32(torch.tensor([float(in_scale)]))
             out = torch.empty((B, self.config.__dict__.get("out_channels", 4), H, W), device=self.device, dtype=torch.float32)
@@ -253,7 +251,6 @@ class CUNet2DConditionModel:
             for nm, bound in ((b"class_labels", clt), (b"timestep_cond", tc), (b"image_embeds", ie)):
                 if bound is not None:
                     _lib.check(lib.mi355x_sd_unet_set_input(h, nm, None))
-        cur.wait_stream(self._stream)
         for x in [s, tt, e, te, ti, sc, em, sm, rm, clt, tc, ie] + rs:     # keep the staging tensors alive until the stream has consumed them
             if x is not None:
                 x.record_stream(self._stream)

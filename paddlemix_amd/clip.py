@@ -232,24 +232,14 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
         B, S = ids.shape
         if S > cfg["max_position_embeddings"]:
             raise ValueError(f"sequence length {S} exceeds max_position_embeddings {cfg['max_position_embeddings']}")
-        if not self._emulated and not ids.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(ids)
         if int(ids.min()) < 0 or int(ids.max()) >= cfg["vocab_size"]:
             raise ValueError("input_ids out of range of the token embedding")
         key = (B, S)
         if key not in self._plans:
             self._plans[key] = self._build_plan(B, S)
         plan = self._plans[key]
-        if self._emulated:
-            plan.ids.copy_(ids.reshape(-1).to(torch.int32))
-            self._run_eager(plan)
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=True)
-                self.run(plan)
-            cur.wait_stream(self._stream)
+        self.run_staged(plan, lambda nb: plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=nb))
         D = cfg["hidden_size"]
         last = plan.last.reshape(B, S, D).float()
         pos = ids.argmax(-1) if cfg["eos_token_id"] == 2 else (ids == cfg["eos_token_id"]).int().argmax(-1)
@@ -273,7 +263,7 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
         D = self.cfg["hidden_size"]
         x = hidden.reshape(-1, D).to(_lib.elem_dtype()).contiguous()
         out = torch.empty_like(x)
-        s = 0 if self._emulated else torch.cuda.current_stream(self.device).cuda_stream
+        s = self.caller_stream()
         _lib.check(self._lib.mi355x_sd_layernorm(x.data_ptr(), x.shape[0], D, D, self.w["lnf.g"].data_ptr(), self.w["lnf.b"].data_ptr(),
                                                  float(self.cfg["layer_norm_eps"]), out.data_ptr(), D, s))
         return out.reshape(hidden.shape).float()
@@ -289,7 +279,7 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
         B = pooled.shape[0]
         a = pooled.to(_lib.elem_dtype()).contiguous()
         out = torch.empty((B, N), device=a.device, dtype=torch.float32)
-        s = 0 if self._emulated else torch.cuda.current_stream(self.device).cuda_stream
+        s = self.caller_stream()
         _lib.check(self._lib.mi355x_sd_linear(a.data_ptr(), K, w.data_ptr(), out.data_ptr(), N, B, N, K, None, None, 0, 0,
                                               None, 0, 1.0, _lib.OUT_F32, *self._gemm_ws, s))
         return out
@@ -452,22 +442,12 @@ class CLIPVisionModelWithProjection(DeviceProgram, PretrainedMixin):
         want = (cfg["num_channels"], cfg["image_size"], cfg["image_size"])
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != want:
             raise ValueError(f"pixel_values: expected [B, {want[0]}, {want[1]}, {want[2]}], got {tuple(pixel_values.shape)}")
-        if not self._emulated and not pixel_values.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(pixel_values)
         B = pixel_values.shape[0]
         if B not in self._plans:
             self._plans[B] = self._build_plan(B)
         plan = self._plans[B]
-        if self._emulated:
-            plan.pixels.copy_(pixel_values)
-            self._run_eager(plan)
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                plan.pixels.copy_(pixel_values, non_blocking=True)
-                self.run(plan)
-            cur.wait_stream(self._stream)
+        self.run_staged(plan, lambda nb: plan.pixels.copy_(pixel_values, non_blocking=nb))
         D, S = cfg["hidden_size"], plan.S
         out = CLIPVisionModelOutput(image_embeds=plan.embeds.clone(), last_hidden_state=plan.hidden[-1].reshape(B, S, D).float(),
                                     hidden_states=None)

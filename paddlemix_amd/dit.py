@@ -313,21 +313,12 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
                 raise NotImplementedError(f"Transformer2DModel(mi355x, DiT): `{nm}` is not used on this path")
         if timestep is None or class_labels is None:
             raise ValueError("the ada_norm_zero (DiT) branch needs `timestep` and `class_labels`")
-        if not self._emulated and not hidden_states.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(hidden_states)
         B, _, H, W = hidden_states.shape
         plan = self._get_plan(B, H, W)
-        if self._emulated:
+        with self.on_stream():
             self.stage_inputs(plan, hidden_states, timestep, class_labels)
-            self._run_eager(plan)
-            out = plan.out.clone()
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                self.stage_inputs(plan, hidden_states, timestep, class_labels)
-                out = self.run(plan).clone()
-            cur.wait_stream(self._stream)
+            out = self.run(plan).clone()
         if not return_dict:
             return (out,)
         return Transformer2DModelOutput(sample=out)

@@ -23,6 +23,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from . import _lib
+from .program import crossing
 
 MAGIC, VERSION = b"MI3SDPRG", 1
 A_INT, A_FLOAT, A_PTR, A_NULL, A_STREAM = range(5)
@@ -269,13 +270,10 @@ class ExportedProgram:
         return self
 
     def run(self, **inputs) -> Dict[str, torch.Tensor]:
-        cur = torch.cuda.current_stream(self._buf.device)
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
+        with crossing(self._stream, self._buf.device):
             for k, v in inputs.items():
                 dst = self.tensors[k]
                 dst.copy_(v.reshape(dst.shape).to(dst.dtype), non_blocking=True)
             _lib.check(self._lib.mi355x_sd_program_run(self._h, self._stream.cuda_stream))
             out = {k: self.tensors[k].clone() for k in self._outputs}
-        cur.wait_stream(self._stream)
         return out

@@ -16,6 +16,8 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
+from . import _lib, program
+
 
 def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     dims = list(range(1, noise_pred_text.ndim))
@@ -23,6 +25,71 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     std_cfg = noise_cfg.std(dim=dims, keepdim=True)
     rescaled = noise_cfg * (std_text / std_cfg)
     return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
+
+
+class _GenericTail:
+    """A step of StableDiffusionDenoiser around the UNet: ``scale`` its input for step i, ``update`` the latents from its output (with
+    the call's guidance scale, and its guidance rescale or 0.0). Here: the scheduler's own methods, the guidance combine in torch."""
+
+    def __init__(self, scheduler, extra):
+        self.scheduler, self.extra = scheduler, extra
+
+    def scale(self, x, i, t):
+        return self.scheduler.scale_model_input(x, t)
+
+    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
+        if do_cfg:
+            noise_uncond, noise_text = noise_pred.chunk(2)
+            noise_pred = noise_uncond + guidance_scale * (noise_text - noise_uncond)
+            if guidance_rescale > 0.0:
+                noise_pred = rescale_noise_cfg(noise_pred, noise_text, guidance_rescale)
+        return self.scheduler.step(noise_pred, t, latents, return_dict=False, **self.extra)[0]
+
+
+class _FusedTail:
+    """Guidance combine (+ rescale) and scheduler update as ONE device pass over the latents on the caller's stream, coefficients in a
+    device table. Not through paddlemix_amd.ops: its wrappers refuse the emulator's host tensors and validate every call."""
+
+    def __init__(self, lib, emulated, coef, scales=None):
+        self.lib, self.emulated, self.coef, self.scales, self.history = lib, emulated, coef, scales, None
+
+    def scale(self, x, i, t):
+        return x if self.scales is None else x * self.scales[i]
+
+    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
+        lat = latents.contiguous()
+        out = torch.empty_like(lat)
+        eps = noise_pred.data_ptr()
+        _lib.check(self.launch(lat, eps, eps + 4 * lat.numel() if do_cfg else None, out, i, float(guidance_scale),
+                               float(guidance_rescale), program.caller_stream(self.coef.device, self.emulated)))
+        return out
+
+
+class _LinearTail(_FusedTail):
+    """``step_coefficients`` (DDIM at eta = 0, Euler; epsilon and v prediction): prev = a * x + b * model_output, (a, b) = row i of a
+    table [steps, 2] over the scheduler's WHOLE schedule; ``scales``: that schedule's model-input scales"""
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        n, cp = lat.numel(), self.coef.data_ptr() + 8 * i
+        if gr > 0.0:
+            return self.lib.mi355x_sd_cfg_rescale_axpby(lat.data_ptr(), eps, eps_text, out.data_ptr(), cp, gs, gr, lat.shape[0],
+                                                        n // lat.shape[0], stream)
+        if eps_text is not None:
+            return self.lib.mi355x_sd_cfg_axpby(lat.data_ptr(), eps, eps_text, out.data_ptr(), cp, gs, n, stream)
+        return self.lib.mi355x_sd_axpby(lat.data_ptr(), eps, out.data_ptr(), cp, n, stream)
+
+
+class _MultistepTail(_FusedTail):
+    """``multistep_coefficients`` (DPM-Solver multistep): convert_model_output and the history shuffle ride in the same launch;
+    (p, q, A, B, D) = row i - first of a table [steps, 5] over the steps the loop RUNS (img2img starts inside the schedule)"""
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:   # the previous step's converted model output, fp32; row 0 has D = 0: a fresh one is not read
+            self.history, self.first = torch.empty_like(lat), i
+        h = self.history.data_ptr()
+        return self.lib.mi355x_sd_multistep_update(lat.data_ptr(), eps, eps_text, h, out.data_ptr(), h,
+                                                   self.coef.data_ptr() + 20 * (i - self.first), gs, gr, lat.shape[0],
+                                                   lat.numel() // lat.shape[0], stream)
 
 
 class _VaeSwitches:
@@ -33,6 +100,15 @@ class _VaeSwitches:
         if self.vae is None:
             raise ValueError("this pipeline was built without a `vae`")
         return self.vae
+
+    def _postprocess(self, output_type: str, decode):
+        """VaeImageProcessor.postprocess of ``decode()``, the denoiser's own way of putting its latents through the VAE"""
+        if self.vae is None:
+            raise ValueError("output_type != 'latent' needs a `vae`")
+        if output_type not in ("pt", "np"):
+            raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
+        image = (decode() / 2 + 0.5).clamp(0, 1)
+        return image if output_type == "pt" else image.cpu().permute(0, 2, 3, 1).float().numpy()
 
     def enable_vae_slicing(self) -> None:
         self._vae().enable_slicing()
@@ -89,68 +165,46 @@ class StableDiffusionDenoiser(_VaeSwitches):
         return torch.tensor([ids], dtype=torch.float32, device=device)
 
     def _fused_plan(self, rescale: bool, device, timesteps=None):
-        """(per-step input scales, device table of coefficients, library, stream getter) when the scheduler's step is a linear
-        update the library runs in one launch; None -> the generic torch path. Two forms:
-        ``step_coefficients`` (DDIM, Euler; epsilon and v prediction): ``prev = a * x + b * model_output``, a table [steps, 2] over
-        the scheduler's whole schedule, with ``rescale`` through ``mi355x_sd_cfg_rescale_axpby``;
-        ``multistep_coefficients`` (DPM-Solver multistep): (p, q, A, B, D) of ``mi355x_sd_multistep_update``, a table [steps, 5]
-        over ``timesteps``, the steps the loop will run (img2img starts inside the schedule with an empty history); scales is None.
-        The library always has both entries (its ABI version is checked at load); a test backend written before one keeps the
-        generic path."""
-        sch = self.scheduler
-        if not hasattr(self.unet, "_lib"):
+        """The fused step tail, when the scheduler's step is an update the library runs in one launch; None -> the generic path.
+        The library always has every entry (its ABI version is checked at load); a test backend from before one keeps that path."""
+        sch, multistep = self.scheduler, hasattr(self.scheduler, "multistep_coefficients")
+        lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
+        entry = "mi355x_sd_multistep_update" if multistep else "mi355x_sd_cfg_rescale_axpby" if rescale else None
+        if lib is None or not (multistep or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
             return None
-        emulated = getattr(self.unet, "_emulated", False)
-        if hasattr(sch, "multistep_coefficients"):
-            if emulated and not hasattr(self.unet._lib, "mi355x_sd_multistep_update"):
-                return None
-            try:
-                scales, coefs = None, [tuple(float(v) for v in sch.multistep_coefficients(t)) for t in timesteps]
-            except NotImplementedError:
-                return None
-            finally:   # as set_timesteps left it
-                sch._step_index, sch.lower_order_nums, sch.model_outputs = None, 0, [None] * sch.config.solver_order
-        elif not hasattr(sch, "step_coefficients"):
-            return None
-        elif rescale and emulated and not hasattr(self.unet._lib, "mi355x_sd_cfg_rescale_axpby"):
-            return None
-        else:
-            try:
-                scales, coefs = [], []
-                for t in sch.timesteps:
+        try:
+            scales, coefs = [], []
+            walk = sch.multistep_coefficients if multistep else sch.step_coefficients
+            for t in (timesteps if multistep else sch.timesteps):
+                if not multistep:
                     scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
-                    coefs.append(tuple(float(v) for v in sch.step_coefficients(t)))   # Euler: advances the step index
-            except NotImplementedError:
-                return None
-            finally:
-                if hasattr(sch, "_step_index"):
-                    sch._step_index = None
+                coefs.append(tuple(float(v) for v in walk(t)))   # Euler, DPM-Solver: advances the step index
+        except NotImplementedError:
+            return None
+        finally:   # the walk advanced the scheduler's step state: as set_timesteps left it
+            if hasattr(sch, "_step_index"):
+                sch._step_index = None
+            if multistep:
+                sch.lower_order_nums, sch.model_outputs = 0, [None] * sch.config.solver_order
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
-        if emulated:
-            stream = lambda: 0  # noqa: E731
-        else:
-            stream = lambda: torch.cuda.current_stream(device).cuda_stream  # noqa: E731
-        return scales, coef, self.unet._lib, stream
+        return _MultistepTail(lib, emulated, coef) if multistep else _LinearTail(lib, emulated, coef, scales)
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
         """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1)."""
-        if self.vae is None:
-            raise ValueError("output_type != 'latent' needs a `vae`")
-        if output_type not in ("pt", "np"):
-            raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
-        vc = self.vae.config
-        mean, std = getattr(vc, "latents_mean", None), getattr(vc, "latents_std", None)
-        if mean is not None and std is not None:
+
+        def decode():
+            vc = self.vae.config
+            mean, std = getattr(vc, "latents_mean", None), getattr(vc, "latents_std", None)
+            if mean is None or std is None:
+                return self.vae.decode(latents, return_dict=False, in_scale=1.0 / vc.scaling_factor)[0]
             # StableDiffusionXLPipeline (pipeline_stable_diffusion_xl.py:1105-1110): VAEs that publish per-channel latent statistics
             # are denormalised with them instead of the plain 1 / scaling_factor
             shape = (1, -1, 1, 1)
-            latents = latents * torch.as_tensor(std, dtype=latents.dtype, device=latents.device).reshape(shape) / vc.scaling_factor \
+            z = latents * torch.as_tensor(std, dtype=latents.dtype, device=latents.device).reshape(shape) / vc.scaling_factor \
                 + torch.as_tensor(mean, dtype=latents.dtype, device=latents.device).reshape(shape)
-            image = self.vae.decode(latents, return_dict=False)[0]
-        else:
-            image = self.vae.decode(latents, return_dict=False, in_scale=1.0 / vc.scaling_factor)[0]
-        image = (image / 2 + 0.5).clamp(0, 1)
-        return image if output_type == "pt" else image.cpu().permute(0, 2, 3, 1).float().numpy()
+            return self.vae.decode(z, return_dict=False)[0]
+
+        return self._postprocess(output_type, decode)
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, generator=None, latents=None,
                         device=None):
@@ -354,8 +408,9 @@ class StableDiffusionDenoiser(_VaeSwitches):
             w = torch.full((B,), float(guidance_scale) - 1.0, device=latents.device)
             unet_kw["timestep_cond"] = self.get_guidance_scale_embedding(w, embedding_dim=tc_dim)
         rescale = do_cfg and guidance_rescale > 0.0   # without CFG the reference applies no rescale (:886-888)
-        fused = self._fused_plan(rescale, latents.device, timesteps) if fused_update and not eta else None
-        history = None   # DPM-Solver multistep: the previous step's converted model output, kept on the device
+        tail = (self._fused_plan(rescale, latents.device, timesteps) if fused_update and not eta else None) \
+            or _GenericTail(self.scheduler, extra)
+        guidance = (do_cfg, guidance_scale, guidance_rescale if rescale else 0.0)
         nine = inp is not None and cfg.in_channels != latents.shape[1]
 
         def control(x_in, t):
@@ -389,55 +444,10 @@ class StableDiffusionDenoiser(_VaeSwitches):
             return (1 - inp["mask"]) * proper + inp["mask"] * lat
 
         for i, t in enumerate(timesteps, start=first):
-            latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
-            if fused is not None:
-                # guidance combine (+ guidance rescale) + scheduler update as ONE device pass over the latents (mi355x_sd_cfg_axpby /
-                # cfg_rescale_axpby / multistep_update): the epsilon- or v-prediction step of Euler / DDIM(eta=0) is
-                # prev = a*x + b*model_output with per-step (a, b) kept in HBM; DPM-Solver multistep adds the history term
-                scales, coef, lib, stream = fused
-                scaled = latent_model_input if scales is None else latent_model_input * scales[i]
-                noise_pred = self.unet(extend(scaled), t, encoder_hidden_states=prompt_embeds,
-                                       added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kw, **control(scaled, t))[0]
-                lat = latents.contiguous()
-                out = torch.empty_like(lat)
-                n, cp = lat.numel(), coef.data_ptr() + 8 * i
-                if scales is None:
-                    # DPM-Solver multistep: guidance, rescale, convert_model_output, the update and the history shuffle as one
-                    # launch; row i - first of the (p, q, A, B, D) table. The first row has D = 0: the fresh history is not read.
-                    if history is None:
-                        history = torch.empty_like(lat)
-                    rc = lib.mi355x_sd_multistep_update(lat.data_ptr(), noise_pred.data_ptr(),
-                                                        noise_pred.data_ptr() + 4 * n if do_cfg else None, history.data_ptr(),
-                                                        out.data_ptr(), history.data_ptr(), coef.data_ptr() + 20 * (i - first),
-                                                        float(guidance_scale), float(guidance_rescale) if rescale else 0.0,
-                                                        lat.shape[0], n // lat.shape[0], stream())
-                elif rescale:
-                    rc = lib.mi355x_sd_cfg_rescale_axpby(lat.data_ptr(), noise_pred.data_ptr(), noise_pred.data_ptr() + 4 * n,
-                                                         out.data_ptr(), cp, float(guidance_scale), float(guidance_rescale),
-                                                         lat.shape[0], n // lat.shape[0], stream())
-                elif do_cfg:
-                    rc = lib.mi355x_sd_cfg_axpby(lat.data_ptr(), noise_pred.data_ptr(), noise_pred.data_ptr() + 4 * n,
-                                                 out.data_ptr(), cp, float(guidance_scale), n, stream())
-                else:
-                    rc = lib.mi355x_sd_axpby(lat.data_ptr(), noise_pred.data_ptr(), out.data_ptr(), cp, n, stream())
-                if rc:
-                    from . import _lib
-                    _lib.check(rc)
-                latents = reimpose(out, i - first)
-                if callback_on_step_end is not None:
-                    cb = callback_on_step_end(self, i, t, {"latents": latents})
-                    latents = cb.pop("latents", latents)
-                continue
-            latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
-            noise_pred = self.unet(extend(latent_model_input), t, encoder_hidden_states=prompt_embeds,
-                                   added_cond_kwargs=added_cond_kwargs, return_dict=False, **unet_kw,
-                                   **control(latent_model_input, t))[0]
-            if do_cfg:
-                noise_uncond, noise_text = noise_pred.chunk(2)
-                noise_pred = noise_uncond + guidance_scale * (noise_text - noise_uncond)
-                if guidance_rescale > 0.0:
-                    noise_pred = rescale_noise_cfg(noise_pred, noise_text, guidance_rescale)
-            latents = reimpose(self.scheduler.step(noise_pred, t, latents, return_dict=False, **extra)[0], i - first)
+            model_input = tail.scale(torch.cat([latents] * 2) if do_cfg else latents, i, t)
+            noise_pred = self.unet(extend(model_input), t, encoder_hidden_states=prompt_embeds, added_cond_kwargs=added_cond_kwargs,
+                                   return_dict=False, **unet_kw, **control(model_input, t))[0]
+            latents = reimpose(tail.update(latents, noise_pred, i, t, *guidance), i - first)
             if callback_on_step_end is not None:
                 out = callback_on_step_end(self, i, t, {"latents": latents})
                 latents = out.pop("latents", latents)
@@ -515,14 +525,8 @@ class StableDiffusion3Denoiser(_VaeSwitches):
                 latents = out.pop("latents", latents)
         if output_type == "latent":
             return latents
-        if self.vae is None:
-            raise ValueError("output_type != 'latent' needs a `vae`")
-        if output_type not in ("pt", "np"):
-            raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
-        vc = self.vae.config
-        z = latents / vc.scaling_factor + (getattr(vc, "shift_factor", None) or 0.0)
-        image = (self.vae.decode(z, return_dict=False)[0] / 2 + 0.5).clamp(0, 1)
-        return image if output_type == "pt" else image.cpu().permute(0, 2, 3, 1).float().numpy()
+        return self._postprocess(output_type, lambda: self.vae.decode(
+            latents / self.vae.config.scaling_factor + (getattr(self.vae.config, "shift_factor", None) or 0.0), return_dict=False)[0])
 
 
 class DiTDenoiser(_VaeSwitches):
@@ -571,10 +575,5 @@ class DiTDenoiser(_VaeSwitches):
         latents = x.chunk(2, dim=0)[0] if do_cfg else x
         if output_type == "latent":
             return latents
-        if self.vae is None:
-            raise ValueError("output_type != 'latent' needs a `vae`")
-        if output_type not in ("pt", "np"):
-            raise ValueError(f"output_type must be 'latent', 'pt' or 'np', got {output_type!r}")
-        image = self.vae.decode(latents, return_dict=False, in_scale=1.0 / self.vae.config.scaling_factor)[0]
-        image = (image / 2 + 0.5).clamp(0, 1)
-        return image if output_type == "pt" else image.cpu().permute(0, 2, 3, 1).float().numpy()
+        return self._postprocess(output_type, lambda: self.vae.decode(
+            latents, return_dict=False, in_scale=1.0 / self.vae.config.scaling_factor)[0])

@@ -2,6 +2,7 @@
 launches (eager run with optional per-launch HIP-event timing, hipGraph capture / replay on the model's stream)."""
 from __future__ import annotations
 
+import contextlib
 import contextvars
 
 import ctypes
@@ -50,6 +51,26 @@ class _Plan:
 # A context variable, not a module global: the override is seen by the thread / task that set it and by nobody else (a model built
 # meanwhile on another thread gets the HIP library), and it must be an object that SAYS it is a test backend.
 _BACKEND_OVERRIDE: contextvars.ContextVar = contextvars.ContextVar("mi355x_sd_test_backend", default=None)
+
+
+@contextlib.contextmanager
+def crossing(stream, device):
+    """The body runs with ``stream`` current, ordered after what the caller's current stream on ``device`` holds so far; what the
+    caller enqueues afterwards is ordered after the body. ``stream`` None (the emulated backend): nothing. The trailing wait is not
+    in a ``finally``: an exception in the body propagates with nothing enqueued behind it."""
+    if stream is None:
+        yield
+        return
+    cur = torch.cuda.current_stream(device)
+    stream.wait_stream(cur)
+    with torch.cuda.stream(stream):
+        yield
+    cur.wait_stream(stream)
+
+
+def caller_stream(device, emulated: bool = False) -> int:
+    """the caller's current stream on ``device`` as the C ABI takes it (0 on the emulated backend)"""
+    return 0 if emulated else torch.cuda.current_stream(device).cuda_stream
 
 
 class DeviceProgram:
@@ -136,3 +157,20 @@ class DeviceProgram:
         else:
             self._run_eager(plan)
         return plan.out
+
+    def on_stream(self):
+        """``with self.on_stream():`` -- the body runs on the model's stream, between the caller's work before and after it"""
+        return crossing(self._stream, self.device)
+
+    def run_staged(self, plan: _Plan, stage) -> torch.Tensor:
+        """``stage(non_blocking)`` (the copies into the plan's static inputs), then ``run(plan)``, both on the model's stream"""
+        with self.on_stream():
+            stage(not self._emulated)
+            return self.run(plan)
+
+    def require_gpu(self, *tensors) -> None:
+        if not self._emulated and not all(t.is_cuda for t in tensors):
+            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+
+    def caller_stream(self) -> int:
+        return caller_stream(self.device, self._emulated)

@@ -469,21 +469,12 @@ class SD3Transformer2DModel(DeviceProgram, PretrainedMixin):
                 joint_attention_kwargs=None, return_dict: bool = True):
         if encoder_hidden_states is None or pooled_projections is None or timestep is None:
             raise ValueError("encoder_hidden_states, pooled_projections and timestep are required")
-        if not self._emulated and not hidden_states.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(hidden_states)
         B, _, H, W = hidden_states.shape
         plan = self._get_plan(B, H, W, encoder_hidden_states.shape[1])
-        if self._emulated:
+        with self.on_stream():
             self.stage_inputs(plan, hidden_states, encoder_hidden_states, pooled_projections, timestep)
-            self._run_eager(plan)
-            out = plan.out.clone()
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                self.stage_inputs(plan, hidden_states, encoder_hidden_states, pooled_projections, timestep)
-                out = self.run(plan).clone()
-            cur.wait_stream(self._stream)
+            out = self.run(plan).clone()
         if not return_dict:
             return (out,)
         return Transformer2DModelOutput(sample=out)

@@ -208,24 +208,14 @@ class T5EncoderModel(DeviceProgram, PretrainedMixin):
         cfg = self.cfg
         ids = input_ids.reshape(-1, input_ids.shape[-1])
         B, S = ids.shape
-        if not self._emulated and not ids.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(ids)
         if int(ids.min()) < 0 or int(ids.max()) >= cfg["vocab_size"]:
             raise ValueError("input_ids out of range of the token embedding")
         key = (B, S)
         if key not in self._plans:
             self._plans[key] = self._build_plan(B, S)
         plan = self._plans[key]
-        if self._emulated:
-            plan.ids.copy_(ids.reshape(-1).to(torch.int32))
-            self._run_eager(plan)
-        else:
-            cur = torch.cuda.current_stream(self.device)
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=True)
-                self.run(plan)
-            cur.wait_stream(self._stream)
+        self.run_staged(plan, lambda nb: plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=nb))
         last = plan.last.reshape(B, S, cfg["d_model"]).float()
         if not return_dict:
             return (last,)

@@ -526,19 +526,6 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             return 1
         return max(1, min(B, self._max_batch(h, w_, mode)))
 
-    def _launch(self, plan: _Plan, stage) -> None:
-        """stage the inputs and run the plan on the model's stream, ordered after / before the caller's stream"""
-        if self._emulated:
-            stage(False)
-            self._run_eager(plan)
-            return
-        cur = torch.cuda.current_stream(self.device)
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
-            stage(True)
-            self.run(plan)
-        cur.wait_stream(self._stream)
-
     def decode(self, z: Tensor, return_dict: bool = True, generator=None, *, in_scale: float = 1.0):
         """z [B, latent_channels, h, w] fp32 -> DecoderOutput(sample [B, out_channels, 8h, 8w] fp32).
 
@@ -546,8 +533,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         is the pipelines' ``decode(latents / scaling_factor)`` without the extra pass."""
         if z.dim() != 4 or z.shape[1] != self.cfg["latent_channels"]:
             raise ValueError(f"z: expected [B, {self.cfg['latent_channels']}, h, w], got {tuple(z.shape)}")
-        if not self._emulated and not z.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(z)
         B, _, h, w_ = z.shape
         if self.use_tiling and max(h, w_) > self._tile_sizes()[0]:
             return self.tiled_decode(z, return_dict, in_scale=in_scale)
@@ -558,7 +544,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         for s in range(0, B, step):
             zs = z[s:s + step]
             plan = self._get_plan(zs.shape[0], h, w_, in_scale)
-            self._launch(plan, lambda nb, plan=plan, zs=zs: plan.z.copy_(zs, non_blocking=nb))
+            self.run_staged(plan, lambda nb, plan=plan, zs=zs: plan.z.copy_(zs, non_blocking=nb))
             outs.append(plan.out.clone())
         out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
         if not return_dict:
@@ -572,8 +558,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             raise _lib.MI355XError("this AutoencoderKL was built without encoder parameters (decode-only checkpoint)")
         if x.dim() != 4 or x.shape[1] != self.cfg["in_channels"]:
             raise ValueError(f"x: expected [B, {self.cfg['in_channels']}, H, W], got {tuple(x.shape)}")
-        if not self._emulated and not x.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(x)
         B, _, H, Wd = x.shape
         if self.use_tiling and max(H, Wd) > self._tile_sizes()[1]:
             return self.tiled_encode(x, return_dict)
@@ -587,7 +572,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
         for s in range(0, B, step):
             xs = x[s:s + step].to(torch.float32)
             plan = self._get_plan(xs.shape[0], H, Wd, 1.0, "encode")
-            self._launch(plan, lambda nb, plan=plan, xs=xs: plan.x.copy_(xs, non_blocking=nb))
+            self.run_staged(plan, lambda nb, plan=plan, xs=xs: plan.x.copy_(xs, non_blocking=nb))
             moments.append(plan.moments.clone())
             means.append(plan.mean.clone())
             logvars.append(plan.logvar.clone())
@@ -697,10 +682,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
                                                    c.th, c.tw, first, count, (plan.z if dec else plan.x).data_ptr(), sp)
                     if rc:
                         _lib.check(rc)
-                    if self._emulated:
-                        self._run_eager(plan)
-                    else:
-                        self.run(plan)
+                    self.run(plan)
                     if c.stack is not None:
                         res = plan.out if dec else plan.moments
                         c.stack[first * (res.shape[0] // count):(first + count) * (res.shape[0] // count)].copy_(res, non_blocking=nb)
@@ -710,14 +692,8 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             if rc:
                 _lib.check(rc)
 
-        if self._emulated:
-            body(False)
-            return
-        cur = torch.cuda.current_stream(self.device)
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
-            body(True)
-        cur.wait_stream(self._stream)
+        with self.on_stream():
+            body(not self._emulated)
 
     def tiled_decode(self, z: Tensor, return_dict: bool = True, *, in_scale: float = 1.0):
         """``decode`` over overlapping latent tiles of tile_latent_min_size at stride int(T * (1 - tile_overlap_factor)), each an
@@ -727,8 +703,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             raise NotImplementedError("tiled decode needs post_quant_conv (autoencoder_kl.py:425 applies it to every tile)")
         if z.dim() != 4 or z.shape[1] != self.cfg["latent_channels"]:
             raise ValueError(f"z: expected [B, {self.cfg['latent_channels']}, h, w], got {tuple(z.shape)}")
-        if not self._emulated and not z.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(z)
         B, _, h, w_ = z.shape
         tl = self._get_tiling("decode", B, h, w_, in_scale)
         zc = z.to(device=self.device, dtype=torch.float32).contiguous()
@@ -747,8 +722,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             raise NotImplementedError("tiled encode needs quant_conv (autoencoder_kl.py:376 applies it to every tile)")
         if x.dim() != 4 or x.shape[1] != self.cfg["in_channels"]:
             raise ValueError(f"x: expected [B, {self.cfg['in_channels']}, H, W], got {tuple(x.shape)}")
-        if not self._emulated and not x.is_cuda:
-            raise _lib.MI355XError("inputs must be GPU tensors (no CPU fallback)")
+        self.require_gpu(x)
         B, _, H, Wd = x.shape
         tl = self._get_tiling("encode", B, H, Wd, 1.0)
         L, dev = self.cfg["latent_channels"], self.device
@@ -774,14 +748,8 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             if rc:
                 _lib.check(rc)
 
-        if self._emulated:
+        with self.on_stream():
             go()
-            return
-        cur = torch.cuda.current_stream(self.device)
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
-            go()
-        cur.wait_stream(self._stream)
 
     def _sample_posterior(self, moments: Tensor, noise: Tensor, shape, out_scale: float) -> Tensor:
         B, L, h, w_ = shape

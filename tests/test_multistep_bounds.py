@@ -142,10 +142,10 @@ def test_fused_plan_leaves_the_scheduler_as_set_timesteps_left_it():
     sch.set_timesteps(8)
     fresh.set_timesteps(8)
     plan = _pipe(sch, MultistepEmulator())._fused_plan(False, "cpu", sch.timesteps[3:])
-    assert plan is not None and plan[0] is None and tuple(plan[1].shape) == (5, 5) and plan[1].dtype == torch.float32
+    assert plan is not None and plan.scales is None and tuple(plan.coef.shape) == (5, 5) and plan.coef.dtype == torch.float32
     assert _state(sch) == _state(fresh)
     # the history starts empty at the first step RUN; 8 < 15 steps: lower_order_final
-    assert plan[1][0, 4] == 0.0 and (plan[1][1:-1, 4] != 0.0).all() and plan[1][-1, 4] == 0.0
+    assert plan.coef[0, 4] == 0.0 and (plan.coef[1:-1, 4] != 0.0).all() and plan.coef[-1, 4] == 0.0
 
 
 def test_heun_on_a_long_karras_schedule_keeps_the_generic_path():
