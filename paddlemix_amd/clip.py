@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .checkpoint import PretrainedMixin, Table
-from .program import DeviceProgram, _Plan, _Ref, _V
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
 Tensor = torch.Tensor
 
@@ -101,41 +101,23 @@ def _encoder_layer_shapes(S: Dict[str, tuple], tower: str, n_layers: int, D: int
         S[b + ".layer_norm2.weight"], S[b + ".layer_norm2.bias"] = (D,), (D,)
 
 
-def _emit_encoder_layers(model, emit, persist, hidden: List[Tensor], B: int, S: int, mask_ptr: Optional[int]) -> None:
+def _emit_encoder_layers(pb: PlanBuilder, hidden: List[Tensor], S: int, mask_ptr: Optional[int]) -> None:
     """CLIPEncoder.forward: pre-LayerNorm attention + MLP blocks, hidden[i] -> hidden[i + 1] (modeling.py CLIPEncoderLayer).
     mask_ptr: fp32 [S, S] additive mask shared by batch items and heads (the text tower's causal mask) or None."""
-    cfg, lib, W, stream, gemm_ws = model.cfg, model._lib, model.w, model._stream_ptr, model._gemm_ws
+    cfg, lib, stream = pb.model.cfg, pb.lib, pb.stream
     D, H, I, n = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"], cfg["num_hidden_layers"]
-    d, eps, rows = D // H, float(cfg["layer_norm_eps"]), B * S
-
-    def linear(a: Tensor, lda, wkey, out: Tensor, ldc, R: Optional[Tensor] = None):
-        w = W[wkey + ".w"]
-        N, K = w.shape
-        emit(lib.mi355x_sd_linear, (a.data_ptr(), lda, w.data_ptr(), out.data_ptr(), ldc, rows, N, K, W[wkey + ".b"].data_ptr(),
-                                    None, 0, 0, R.data_ptr() if R is not None else None, N if R is not None else 0, 1.0, 0,
-                                    *gemm_ws, stream), "gemm", 2.0 * rows * N * K, f"{rows}x{N}x{K}")
-
-    def lnorm(x: Tensor, key, out: Tensor):
-        emit(lib.mi355x_sd_layernorm, (x.data_ptr(), rows, D, D, W[key + ".g"].data_ptr(), W[key + ".b"].data_ptr(), eps,
-                                       out.data_ptr(), D, stream), "ln")
-
-    ln, ao = persist((rows, D), _lib.elem_dtype()), persist((rows, D), _lib.elem_dtype())
-    qkv = persist((rows, 3 * D), _lib.elem_dtype())
-    f1, f2 = persist((rows, I), _lib.elem_dtype()), persist((rows, I), _lib.elem_dtype())
-    mid = persist((rows, D), _lib.elem_dtype())
+    eps, rows = float(cfg["layer_norm_eps"]), pb.B * S
+    ln, ao, qkv, f1, f2, mid = (_V.of(pb.persist((rows, C), _lib.elem_dtype())) for C in (D, D, 3 * D, I, I, D))
     for i in range(n):
-        x, y = hidden[i], hidden[i + 1]
-        lnorm(x, f"l{i}.ln1", ln)
-        linear(ln, D, f"l{i}.qkv", qkv, 3 * D)
-        qp = qkv.data_ptr()
-        emit(lib.mi355x_sd_sdpa, (qp, qp + 2 * D, qp + 4 * D, mask_ptr, ao.data_ptr(), B, H, S, S, d,
-                                  S * 3 * D, 3 * D, S * 3 * D, 3 * D, S * 3 * D, 3 * D, S * D, D, 0, 0, S if mask_ptr else 0,
-                                  d ** -0.5, stream), "attn", 4.0 * B * H * S * S * d, f"{B}x{H}x{S}x{S}x{d}")
-        linear(ao, D, f"l{i}.out", mid, D, R=x)
-        lnorm(mid, f"l{i}.ln2", ln)
-        linear(ln, D, f"l{i}.fc1", f1, I)
-        emit(lib.mi355x_sd_activation, (f1.data_ptr(), f2.data_ptr(), rows * I, _ACT_KIND[cfg["hidden_act"]], stream), "misc")
-        linear(f2, I, f"l{i}.fc2", y, D, R=mid)
+        x, y = _V.of(hidden[i]), _V.of(hidden[i + 1])
+        pb.lnorm(x, f"l{i}.ln1", ln, eps)
+        pb.linear(ln, f"l{i}.qkv", qkv)
+        pb.sdpa(qkv.cols(0, D), qkv.cols(D, D), qkv.cols(2 * D, D), ao, H, S, S, mask_ptr, (0, 0, S if mask_ptr else 0))
+        pb.linear(ao, f"l{i}.out", mid, R=x)
+        pb.lnorm(mid, f"l{i}.ln2", ln, eps)
+        pb.linear(ln, f"l{i}.fc1", f1)
+        pb.emit(lib.mi355x_sd_activation, (f1.p, f2.p, rows * I, _ACT_KIND[cfg["hidden_act"]], stream), "misc")
+        pb.linear(f2, f"l{i}.fc2", y, R=mid)
 
 
 class CLIPTextModelOutput(SimpleNamespace):
@@ -184,27 +166,11 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
 
     # ------------------------------------------------------------------ plan
     def _build_plan(self, B: int, S: int) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
-        stream = self._stream_ptr
-        D, H, I, n = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"], cfg["num_hidden_layers"]
-        d, eps = D // H, float(cfg["layer_norm_eps"])
+        cfg, lib, W = self.cfg, self._lib, self.w
+        D, n = cfg["hidden_size"], cfg["num_hidden_layers"]
         rows = B * S
-        plan = _Plan()
-        prog: List[tuple] = []
-        keep: List[Tensor] = []
-
-        def persist(shape, dtype) -> Tensor:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, tuple(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def lnorm(x: Tensor, key, out: Tensor):
-            emit(lib.mi355x_sd_layernorm, (x.data_ptr(), rows, D, D, W[key + ".g"].data_ptr(), W[key + ".b"].data_ptr(), eps,
-                                           out.data_ptr(), D, stream), "ln")
-
+        pb = PlanBuilder(self, B)
+        plan, persist = pb.plan, pb.persist
         plan.ids = persist((rows,), torch.int32)
         # causal mask as the attention kernel's additive bias: [S, S] shared by every batch item and head
         mask = persist((S, S), torch.float32)
@@ -212,14 +178,17 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
         plan.consts = [mask]       # filled here, read by every run (paddlemix_amd/export.py ships its contents)
         plan.hidden = [persist((rows, D), _lib.elem_dtype()) for _ in range(n + 1)]   # encoder hidden_states tuple
         plan.last = persist((rows, D), _lib.elem_dtype())
-        emit(lib.mi355x_sd_embed_tokens, (plan.ids.data_ptr(), rows, S, W["tok"].data_ptr(), W["pos"].data_ptr(), D,
-                                          plan.hidden[0].data_ptr(), D, stream), "misc")
-        _emit_encoder_layers(self, emit, persist, plan.hidden, B, S, mask.data_ptr())
-        lnorm(plan.hidden[n], "lnf", plan.last)
-        plan.prog, plan.keep, plan.graph = prog, keep, None
+        pb.emit(lib.mi355x_sd_embed_tokens, (plan.ids.data_ptr(), rows, S, W["tok"].data_ptr(), W["pos"].data_ptr(), D,
+                                             plan.hidden[0].data_ptr(), D, pb.stream), "misc")
+        _emit_encoder_layers(pb, plan.hidden, S, mask.data_ptr())
+        pb.lnorm(_V.of(plan.hidden[n]), "lnf", _V.of(plan.last), float(cfg["layer_norm_eps"]))
+        pb.finish()
         plan.out = plan.last
         plan.B, plan.S = B, S
         return plan
+
+    def _get_plan(self, B, S) -> _Plan:
+        return self.plan_for((B, S), lambda: self._build_plan(B, S))
 
     def forward(self, input_ids: Tensor, attention_mask=None, position_ids=None, output_attentions=None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = True):
@@ -235,10 +204,7 @@ class CLIPTextModel(DeviceProgram, PretrainedMixin):
         self.require_gpu(ids)
         if int(ids.min()) < 0 or int(ids.max()) >= cfg["vocab_size"]:
             raise ValueError("input_ids out of range of the token embedding")
-        key = (B, S)
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, S)
-        plan = self._plans[key]
+        plan = self._get_plan(B, S)
         self.run_staged(plan, lambda nb: plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=nb))
         D = cfg["hidden_size"]
         last = plan.last.reshape(B, S, D).float()
@@ -383,23 +349,13 @@ class CLIPVisionModelWithProjection(DeviceProgram, PretrainedMixin):
         W["proj.w"] = bf(get("visual_projection.weight").t())
 
     def _build_plan(self, B: int) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
-        stream = self._stream_ptr
+        cfg, lib, W = self.cfg, self._lib, self.w
         D, n, p, C = cfg["hidden_size"], cfg["num_hidden_layers"], cfg["patch_size"], cfg["num_channels"]
         side = cfg["image_size"]
         N = (side // p) ** 2
         S, eps, Kp = N + 1, float(cfg["layer_norm_eps"]), self._kpad
-        plan = _Plan()
-        prog: List[tuple] = []
-        keep: List[Tensor] = []
-
-        def persist(shape, dtype) -> Tensor:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, tuple(args), kind if not desc else f"{kind}:{desc}", flops))
+        pb = PlanBuilder(self, B)
+        plan, persist = pb.plan, pb.persist
 
         plan.pixels = persist((B, C, side, side), torch.float32)
         cols = persist((B * N, Kp), _lib.elem_dtype())
@@ -409,27 +365,24 @@ class CLIPVisionModelWithProjection(DeviceProgram, PretrainedMixin):
         pos_t = persist((B * N, D), _lib.elem_dtype())
         pos_t.reshape(B, N, D).copy_(W["pos_patches"])
         plan.consts = [cols, emb, pos_t]   # initialised here (paddlemix_amd/export.py ships their contents)
-        emit(lib.mi355x_sd_patchify, (plan.pixels.data_ptr(), B, C, side, side, p, cols.data_ptr(), Kp, stream), "misc")
+        pb.emit(lib.mi355x_sd_patchify, (plan.pixels.data_ptr(), B, C, side, side, p, cols.data_ptr(), Kp, pb.stream), "misc")
         # patch rows of image b land at token rows b * S + 1 ..: C row remap (rows_per_batch N, batch stride S * D)
-        emit(lib.mi355x_sd_linear_ex, (cols.data_ptr(), Kp, 0, 0, W["patch.w"].data_ptr(), None, emb.data_ptr() + 2 * D, D, N,
-                                       S * D, B * N, D, Kp, None, None, 0, None, 0, 0, pos_t.data_ptr(), D, 1.0, 0, *self._gemm_ws, stream),
-             "gemm", 2.0 * B * N * D * Kp, f"{B * N}x{D}x{Kp}")
+        pb.linear_ex(_V.of(cols), "patch", _V(emb.data_ptr() + 2 * D, B * N, D), R=_V.of(pos_t), c_rpb=N, c_bs=S * D, bias=False)
         plan.hidden = [persist((B * S, D), _lib.elem_dtype()) for _ in range(n + 1)]
-        emit(lib.mi355x_sd_layernorm, (emb.data_ptr(), B * S, D, D, W["pre.g"].data_ptr(), W["pre.b"].data_ptr(), eps,
-                                       plan.hidden[0].data_ptr(), D, stream), "ln")
-        _emit_encoder_layers(self, emit, persist, plan.hidden, B, S, None)
+        pb.lnorm(_V.of(emb), "pre", _V.of(plan.hidden[0]), eps)
+        _emit_encoder_layers(pb, plan.hidden, S, None)
         plan.pooled = persist((B, D), _lib.elem_dtype())
         # post_layernorm of the class-token rows only: B rows at stride S * D
-        emit(lib.mi355x_sd_layernorm, (plan.hidden[n].data_ptr(), B, D, S * D, W["post.g"].data_ptr(), W["post.b"].data_ptr(), eps,
-                                       plan.pooled.data_ptr(), D, stream), "ln")
+        pb.lnorm(_V(plan.hidden[n].data_ptr(), B, D, S * D), "post", _V.of(plan.pooled), eps)
         plan.embeds = persist((B, W["proj.w"].shape[0]), torch.float32)
-        emit(lib.mi355x_sd_linear, (plan.pooled.data_ptr(), D, W["proj.w"].data_ptr(), plan.embeds.data_ptr(),
-                                    W["proj.w"].shape[0], B, W["proj.w"].shape[0], D, None, None, 0, 0, None, 0, 1.0,
-                                    _lib.OUT_F32, *self._gemm_ws, stream), "gemm", 2.0 * B * D * W["proj.w"].shape[0])
-        plan.prog, plan.keep, plan.graph = prog, keep, None
+        pb.linear(_V.of(plan.pooled), "proj", _V.of(plan.embeds), bias=False, desc="")   # (recorded under the bare "gemm" kind)
+        pb.finish()
         plan.out = plan.embeds
         plan.B, plan.S = B, S
         return plan
+
+    def _get_plan(self, B) -> _Plan:
+        return self.plan_for(B, lambda: self._build_plan(B))
 
     def forward(self, pixel_values: Tensor, output_attentions=None, output_hidden_states: Optional[bool] = None,
                 return_dict: Optional[bool] = True):
@@ -444,9 +397,7 @@ class CLIPVisionModelWithProjection(DeviceProgram, PretrainedMixin):
             raise ValueError(f"pixel_values: expected [B, {want[0]}, {want[1]}, {want[2]}], got {tuple(pixel_values.shape)}")
         self.require_gpu(pixel_values)
         B = pixel_values.shape[0]
-        if B not in self._plans:
-            self._plans[B] = self._build_plan(B)
-        plan = self._plans[B]
+        plan = self._get_plan(B)
         self.run_staged(plan, lambda nb: plan.pixels.copy_(pixel_values, non_blocking=nb))
         D, S = cfg["hidden_size"], plan.S
         out = CLIPVisionModelOutput(image_embeds=plan.embeds.clone(), last_hidden_state=plan.hidden[-1].reshape(B, S, D).float(),

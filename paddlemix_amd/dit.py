@@ -16,9 +16,10 @@ null class, out_channels 8 (learned sigma). Built from the kernels of the SD3 pa
 """
 from __future__ import annotations
 
+import functools
 import math
 from types import SimpleNamespace
-from typing import Dict, List, Mapping, Optional
+from typing import Dict, Mapping
 
 import numpy as np
 import torch
@@ -26,7 +27,7 @@ import torch
 from . import _lib
 from ._lib import GELU_TANH, OUT_F32, SILU
 from .checkpoint import PretrainedMixin, Table
-from .program import DeviceProgram, _Plan, _Ref, _V
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 from .sd3 import Transformer2DModelOutput
 
 Tensor = torch.Tensor
@@ -169,7 +170,7 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
 
     # ------------------------------------------------------------------ plan
     def _build_plan(self, B: int, H: int, Wd: int) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
+        cfg, lib, W = self.cfg, self._lib, self.w
         stream = self._stream_ptr
         D, heads, p, n = cfg["inner_dim"], cfg["num_attention_heads"], cfg["patch_size"], cfg["num_layers"]
         if H % p or Wd % p or H != Wd:
@@ -177,32 +178,11 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
                              f"with int(sqrt(tokens)), transformer_2d.py:495-496), got {H}x{Wd}")
         hp = H // p
         S = hp * hp
-        plan = _Plan()
-        prog: List[tuple] = []
-        scratch: Dict[str, int] = {}
-        keep: List[Tensor] = []
+        pb = PlanBuilder(self, B)
+        plan, sc, persist, emit = pb.plan, pb.sc, pb.persist, pb.emit
         ET = _lib.elem_dtype()
-
-        def sc(name, nbytes):
-            scratch[name] = max(scratch.get(name, 0), nbytes)
-            return _Ref(name)
-
-        def persist(shape, dtype):
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, list(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def linear(a: _V, wkey: str, out: _V, *, flags=0, R: Optional[_V] = None, gate=None, ld_gate=0, rpb=0):
-            w = W[wkey + ".w"]
-            N, K = w.shape
-            assert K == a.C, (wkey, K, a.C)
-            emit(lib.mi355x_sd_linear_ex,
-                 (a.p, a.ld, 0, 0, w.data_ptr(), None, out.p, out.ld, 0, 0, a.rows, N, K, W[wkey + ".b"].data_ptr(), None, 0,
-                  gate, ld_gate, rpb, R.p if R else None, R.ld if R else 0, 1.0, flags, *self._gemm_ws, stream), "gemm",
-                 2.0 * a.rows * N * K, f"{a.rows}x{N}x{K}")
+        LDM = 6 * D
+        linear = functools.partial(pb.linear_ex, ld_gate=LDM)   # (the row stride of the modulation table, where a launch is gated)
 
         def adaln(x: _V, scale_ptr, shift_ptr, ld_mod, eps, out: _V):
             emit(lib.mi355x_sd_adaln, (x.p, x.rows, x.C, x.ld, scale_ptr, shift_ptr, ld_mod, S, eps, out.p, out.ld, stream),
@@ -244,8 +224,7 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
                    R=_V(cls.data_ptr() + 2 * i * B * D, B, D))
         scond = persist((n * B, D), ET)
         emit(lib.mi355x_sd_silu, (cond.data_ptr(), scond.data_ptr(), n * B * D, 0, 0, stream), "misc")
-        mod = persist((n + 1, B, 6 * D), torch.float32)   # [block][batch][shift_msa scale_msa gate_msa shift_mlp scale_mlp gate_mlp]
-        LDM = 6 * D
+        mod = persist((n + 1, B, LDM), torch.float32)   # [block][batch][shift_msa scale_msa gate_msa shift_mlp scale_mlp gate_mlp]
         for i in range(n):
             linear(_V(scond.data_ptr() + 2 * i * B * D, B, D), f"transformer_blocks.{i}.mod",
                    _V(mod.data_ptr() + 4 * i * B * LDM, B, LDM), flags=OUT_F32)
@@ -255,21 +234,18 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
 
         # ---- blocks (attention.py:376-490, ada_norm_zero path) ----
         nx = _V(sc("nx", 2 * B * S * D), B * S, D)
-        qkv = sc("qkv", 2 * B * S * 3 * D)
+        qkv = _V(sc("qkv", 2 * B * S * 3 * D), B * S, 3 * D)
         ao = _V(sc("attn_out", 2 * B * S * D), B * S, D)
         ff = _V(sc("ff", 2 * B * S * 4 * D), B * S, 4 * D)
-        d = D // heads
         for i in range(n):
             b = f"transformer_blocks.{i}"
             adaln(x, m_at(i, 1), m_at(i, 0), LDM, 1e-6, nx)                      # norm1: LN * (1 + scale_msa) + shift_msa
-            linear(nx, b + ".qkv", _V(qkv, B * S, 3 * D))
-            emit(lib.mi355x_sd_sdpa, (qkv, qkv + 2 * D, qkv + 4 * D, None, ao.p, B, heads, S, S, d, S * 3 * D, 3 * D,
-                                      S * 3 * D, 3 * D, S * 3 * D, 3 * D, S * D, D, 0, 0, 0, d ** -0.5, stream),
-                 "attn", 4.0 * B * heads * S * S * d, f"{B}x{heads}x{S}x{S}x{d}")
-            linear(ao, b + ".out", x, R=x, gate=m_at(i, 2), ld_gate=LDM, rpb=S)   # x += gate_msa * attn
+            linear(nx, b + ".qkv", qkv)
+            pb.sdpa(qkv.cols(0, D), qkv.cols(D, D), qkv.cols(2 * D, D), ao, heads, S, S)
+            linear(ao, b + ".out", x, R=x, gate=m_at(i, 2), rpb=S)               # x += gate_msa * attn
             adaln(x, m_at(i, 4), m_at(i, 3), LDM, float(cfg["norm_eps"]), nx)     # norm3 + (1 + scale_mlp), shift_mlp
             linear(nx, b + ".ff1", ff, flags=GELU_TANH)
-            linear(ff, b + ".ff2", x, R=x, gate=m_at(i, 5), ld_gate=LDM, rpb=S)   # x += gate_mlp * ff
+            linear(ff, b + ".ff2", x, R=x, gate=m_at(i, 5), rpb=S)               # x += gate_mlp * ff
 
         # ---- output (transformer_2d.py:478-503) ----
         adaln(x, m_at(n, 1), m_at(n, 0), LDM, 1e-6, nx)
@@ -279,19 +255,12 @@ class DiTTransformer2DModel(DeviceProgram, PretrainedMixin):
         emit(lib.mi355x_sd_unpatchify, (proj.data_ptr(), po, B, cfg["out_channels"], H, Wd, p, plan.out.data_ptr(), stream),
              "misc")
 
-        bufs = {nm: persist((max(nb, 16),), torch.uint8) for nm, nb in scratch.items()}
-        basep = {nm: t.data_ptr() for nm, t in bufs.items()}
-        res = lambda a: basep[a.buf] + a.off if isinstance(a, _Ref) else a  # noqa: E731
-        plan.prog = [(fn, tuple(res(a) for a in args), kind, fl) for fn, args, kind, fl in prog]
-        plan.keep, plan.graph = keep, None
+        pb.finish()
         plan.B, plan.H, plan.W = B, H, Wd
         return plan
 
     def _get_plan(self, B, H, W) -> _Plan:
-        key = (B, H, W)
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, H, W)
-        return self._plans[key]
+        return self.plan_for((B, H, W), lambda: self._build_plan(B, H, W))
 
     def stage_inputs(self, plan: _Plan, hidden_states, timestep, class_labels) -> None:
         n, B = self.cfg["num_layers"], plan.B

@@ -7,7 +7,7 @@ inputs, static program + parameters on disk), then run it behind a predictor obj
 
     model = SD3Transformer2DModel(cfg, params)          # or UNet2DConditionModel, AutoencoderKL, CLIPTextModel, ...
     model(x, enc, pooled, t)                            # builds (and, for lazily completed plans, finishes) the plan
-    export_program(model, model.plan_for(...), "sd3_b2_128.mi3prg")
+    export_program(model, model._get_plan(...), "sd3_b2_128.mi3prg")
 
 File layout (little endian): magic "MI3SDPRG", u32 version, ABI version, element type, counts, u64 split-K workspace bytes; the
 region table (kind weight | const | scratch | io, bytes, file offset of the initial contents or 0, name); the I/O table (region,

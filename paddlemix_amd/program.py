@@ -6,11 +6,12 @@ import contextlib
 import contextvars
 
 import ctypes
-from typing import Dict
+from typing import Callable, Dict, List, Optional
 
 import torch
 
 from . import _lib
+from ._lib import CONV_KB64, GEGLU, OUT_F32, PAD_BR, R_F32
 
 WORKSPACE_BYTES = 32 << 20   # split-K partial sums (the planner shrinks the split count to fit) AND the just-in-time widened copy of a
                              # weight-only-fp8 matrix (2 * N * K bytes, <= ~19 MB for SD3-medium): the `ws, ws_bytes` arguments of the
@@ -39,9 +40,147 @@ class _V:
     def cols(self, off: int, C: int) -> "_V":
         return _V(self.p + self.es * off, self.rows, C, self.ld, self.es)
 
+    @classmethod
+    def of(cls, t: torch.Tensor) -> "_V":
+        """the rows of a 2-D tensor"""
+        return cls(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0), t.element_size())
+
 
 class _Plan:
     pass
+
+
+class PlanBuilder:
+    """What a model's ``_build_plan`` writes its launch plan with: the new ``plan``, the buffers it will own, and one method per launch
+    form that two or more model families emit (a form only one family emits is a local function over ``emit`` next to that family).
+    ``B`` is the batch every batched launch of the plan runs over."""
+
+    def __init__(self, model: "DeviceProgram", B: int):
+        self.model, self.B = model, B
+        self.lib, self.W, self.device = model._lib, model.w, model.device
+        self.stream, self.gemm_ws = model._stream_ptr, model._gemm_ws
+        self.plan = _Plan()
+        self.prog: List[tuple] = []          # (cfunc, args (list with _Ref placeholders), kind, flops)
+        self.scratch: Dict[str, int] = {}
+        self.keep: List[torch.Tensor] = []
+
+    def sc(self, name: str, nbytes: int) -> _Ref:
+        """the named scratch buffer, at least ``nbytes`` large (one buffer per name, sized by its largest request)"""
+        self.scratch[name] = max(self.scratch.get(name, 0), nbytes)
+        return _Ref(name)
+
+    def persist(self, shape, dtype) -> torch.Tensor:
+        t = torch.empty(shape, device=self.device, dtype=dtype)
+        self.keep.append(t)
+        return t
+
+    def wp(self, key: str) -> int:
+        return self.W[key].data_ptr()
+
+    def emit(self, fn, args, kind, flops=0.0, desc="") -> None:
+        self.prog.append((fn, list(args), kind if not desc else f"{kind}:{desc}", flops))
+
+    def finish(self) -> _Plan:
+        """allocate the scratch buffers (after everything persisted so far), resolve every _Ref, hand the plan over"""
+        base = {n: self.persist((max(nb, 16),), torch.uint8).data_ptr() for n, nb in self.scratch.items()}
+        plan = self.plan
+        plan.prog = [(fn, tuple(base[a.buf] + a.off if isinstance(a, _Ref) else a for a in args), kind, fl)
+                     for fn, args, kind, fl in self.prog]
+        plan.keep, plan.graph = self.keep, None
+        return plan
+
+    # ---- launch forms shared by two or more families (`ws, ws_bytes` of the GEMM-class calls: ABI 12) ----
+    def linear(self, a: _V, w, out: _V, bias=True, R: Optional[_V] = None, flags=0, out_scale=1.0, rowbias=None, rpb=0, ld_rb=0,
+               bkey=None, desc=None) -> None:
+        """out = (a W^T + bias + row bias) * out_scale + R with the epilogue ``flags``. ``w``: a weight key (matrix ``w.w``, bias ``w.b``
+        or ``bkey``) or, for activations times activations, the _V of the [N, K] operand (``bias=False``)."""
+        if isinstance(w, _V):
+            assert not bias and w.ld == w.C, "an activation operand is dense and has no bias"
+            wptr, N, K = w.p, w.rows, w.C
+        else:
+            (N, K), wptr = self.W[w + ".w"].shape, self.wp(w + ".w")
+        assert K == a.C, (w, K, a.C)
+        assert a.es == 2, (w, "fp32 rows cannot be an MFMA operand")
+        flags |= (OUT_F32 if out.es == 4 else 0) | (R_F32 if (R is not None and R.es == 4) else 0)
+        self.emit(self.lib.mi355x_sd_linear,
+                  (a.p, a.ld, wptr, out.p, out.ld, a.rows, N, K, self.wp(bkey or w + ".b") if bias else None, rowbias, rpb, ld_rb,
+                   R.p if R else None, R.ld if R else 0, out_scale, flags, *self.gemm_ws, self.stream), "gemm", 2.0 * a.rows * N * K,
+                  f"{a.rows}x{N}x{K}" + ("g" if flags & GEGLU else "") if desc is None else desc)
+
+    def linear_ex(self, a: _V, wkey: str, out: _V, *, flags=0, R: Optional[_V] = None, gate=None, ld_gate=0, rpb=0, a_rpb=0, a_bs=0,
+                  c_rpb=0, c_bs=0, bias=True) -> None:
+        """mi355x_sd_linear_ex: ``linear`` with a row remap of A (a_rpb rows per batch, batch stride a_bs) and of C, a per-row-block
+        ``gate`` (row stride ld_gate, rpb rows per batch) on the product, and the weight's per-channel scale ``wkey.s`` if it has one"""
+        w = self.W[wkey + ".w"]
+        N, K = w.shape
+        assert K == a.C, (wkey, K, a.C)
+        ws = self.W.get(wkey + ".s")
+        self.emit(self.lib.mi355x_sd_linear_ex,
+                  (a.p, a.ld, a_rpb, a_bs, w.data_ptr(), ws.data_ptr() if ws is not None else None, out.p, out.ld, c_rpb, c_bs,
+                   a.rows, N, K, self.wp(wkey + ".b") if bias else None, None, 0, gate, ld_gate if gate is not None else 0, rpb,
+                   R.p if R else None, R.ld if R else 0, 1.0, flags, *self.gemm_ws, self.stream), "gemm", 2.0 * a.rows * N * K,
+                  f"{a.rows}x{N}x{K}")
+
+    def conv3(self, x: _V, h, w_, wkey, out: _V, stride=1, up=0, rowbias=None, ld_rb=0, R: Optional[_V] = None, out_scale=1.0,
+              flags=0) -> None:
+        """3x3 conv of B images of h x w (x2 nearest upsampling folded in with ``up``); MI355X_SD_PAD_BR in ``flags`` pads bottom / right
+        only (one zero row and column instead of two)"""
+        B, w = self.B, self.W[wkey + ".w"]
+        Cout = w.shape[0]
+        pad2 = 1 if flags & PAD_BR else 2
+        ho, wo = ((h << up) + pad2 - 3) // stride + 1, ((w_ << up) + pad2 - 3) // stride + 1
+        assert x.es == 2, (wkey, "fp32 rows cannot be an MFMA operand")
+        flags |= (OUT_F32 if out.es == 4 else 0) | (R_F32 if (R is not None and R.es == 4) else 0)
+        flags |= CONV_KB64 if wkey in getattr(self.model, "_kb64", ()) else 0
+        self.emit(self.lib.mi355x_sd_conv3x3,
+                  (x.p, x.ld, B, h, w_, x.C, stride, up, w.data_ptr(), out.p, out.ld, Cout, self.wp(wkey + ".b"), rowbias,
+                   ld_rb if rowbias is not None else 0, R.p if R else None, R.ld if R else 0, out_scale, flags, *self.gemm_ws,
+                   self.stream), "conv", 2.0 * B * ho * wo * Cout * 9 * x.C,
+                  f"{B * ho * wo}x{Cout}x{9 * x.C}" + ("s2" if stride == 2 else "") + ("up" if up else ""))
+
+    def gnorm(self, x: _V, hw, nkey, eps, silu, raw16: Optional[_V] = None) -> _V:
+        """GroupNorm (+SiLU) of x -> 16-bit rows. fp32-residual mode: x is fp32; `raw16` (optional) receives the 16-bit
+        rounding of the raw x rows in the same pass (the operand of a conv_shortcut GEMM)."""
+        lib, sc, emit, wp, B, stream = self.lib, self.sc, self.emit, self.wp, self.B, self.stream
+        groups = self.model.cfg["norm_num_groups"]
+        ws = sc("gn_ws", 4 * lib.mi355x_sd_groupnorm_workspace_floats(B, hw, x.C))
+        ss = sc("gn_ss", 4 * B * 2 * x.C)
+        y = _V(sc("gn", 2 * x.rows * x.C), x.rows, x.C)
+        silu = 1 if silu else 0
+        if x.es == 2 and lib.mi355x_sd_groupnorm_act_fits(hw, x.C, groups):
+            # small (batch, group) chunks: statistics + affine (+SiLU) in one launch (csrc/norm.hip gn_fused_kernel)
+            assert raw16 is None
+            emit(lib.mi355x_sd_groupnorm_act, (x.p, B, hw, x.C, x.ld, groups, eps, wp(nkey + ".g"), wp(nkey + ".b"), silu, y.p, y.ld,
+                                               stream), "gn_fused")
+        elif x.es == 2:
+            assert raw16 is None
+            emit(lib.mi355x_sd_groupnorm_stats, (x.p, B, hw, x.C, x.ld, groups, eps, wp(nkey + ".g"), wp(nkey + ".b"), ws, ss, stream),
+                 "gn_stats")
+            emit(lib.mi355x_sd_scale_shift_act, (x.p, B, hw, x.C, x.ld, ss, silu, y.p, y.ld, stream), "gn_apply")
+        else:
+            emit(lib.mi355x_sd_groupnorm_stats_ex, (x.p, B, hw, x.C, x.ld, groups, eps, wp(nkey + ".g"), wp(nkey + ".b"), ws, ss, 1,
+                                                    stream), "gn_stats")
+            emit(lib.mi355x_sd_scale_shift_act_ex, (x.p, B, hw, x.C, x.ld, ss, silu, y.p, y.ld, 1, raw16.p if raw16 else None,
+                                                    raw16.ld if raw16 else 0, stream), "gn_apply")
+        return y
+
+    def lnorm(self, x: _V, nkey, out: _V, eps=1e-5) -> None:
+        """LayerNorm of 16-bit or fp32 rows -> 16-bit rows (gamma ``nkey.g``, beta ``nkey.b``)"""
+        args = (x.p, x.rows, x.C, x.ld, self.wp(nkey + ".g"), self.wp(nkey + ".b"), eps, out.p, out.ld)
+        if x.es == 2:
+            self.emit(self.lib.mi355x_sd_layernorm, args + (self.stream,), "ln")
+        else:
+            self.emit(self.lib.mi355x_sd_layernorm_ex, args + (1, self.stream), "ln")
+
+    def sdpa(self, q: _V, k: _V, v: _V, out: _V, heads, sq, skv, bias=None, bias_strides=(0, 0, 0), scale=None,
+             fn: Optional[Callable] = None, tail=(), suffix="") -> None:
+        """softmax(q k^T * scale + bias) v per (batch, head); sq / skv rows per batch item. ``bias``: fp32, element strides (batch, head,
+        query). ``scale``: head_dim^-0.5 unless given. ``fn`` + ``tail``: mi355x_sd_sdpa_ex / _accum and what they take before the stream."""
+        B, d = self.B, q.C // heads
+        self.emit(fn or self.lib.mi355x_sd_sdpa,
+                  (q.p, k.p, v.p, bias, out.p, B, heads, sq, skv, d, sq * q.ld, q.ld, skv * k.ld, k.ld, skv * v.ld, v.ld, sq * out.ld,
+                   out.ld, *bias_strides, d ** -0.5 if scale is None else scale, *tail, self.stream), "attn",
+                  4.0 * B * heads * sq * skv * d, f"{B}x{heads}x{sq}x{skv}x{d}{suffix}")
 
 
 # Test plumbing, ONE place: while a backend object is pushed here (tests/abi_emulator.py ``on_emulator`` does that around a
@@ -108,6 +247,12 @@ class DeviceProgram:
         self._plans: Dict[tuple, _Plan] = {}
         self.w: Dict[str, torch.Tensor] = {}
         self.kernel_times: Dict[str, list] = {}
+
+    def plan_for(self, key, build: Callable[[], _Plan]) -> _Plan:
+        """the cached plan of ``key``, built by ``build()`` the first time it is asked for"""
+        if key not in self._plans:
+            self._plans[key] = build()
+        return self._plans[key]
 
     def weight_bytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.w.values())

@@ -18,6 +18,7 @@ Block matrices: bf16, weight-only fp8 (``weight_dtype="fp8"``, BASELINE.json con
 """
 from __future__ import annotations
 
+import functools
 import math
 from types import SimpleNamespace
 from typing import Dict, List, Mapping, Optional
@@ -28,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import GELU_TANH, OUT_F32, SILU
 from .checkpoint import PretrainedMixin
-from .program import DeviceProgram, _Plan, _Ref, _V
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
 Tensor = torch.Tensor
 
@@ -259,41 +260,15 @@ class SD3Transformer2DModel(DeviceProgram, PretrainedMixin):
 
     # ------------------------------------------------------------------ plan
     def _build_plan(self, B: int, H: int, Wd: int, L: int) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
+        cfg, lib, W = self.cfg, self._lib, self.w
         stream = self._stream_ptr
         D, heads, p, n = cfg["inner_dim"], cfg["num_attention_heads"], cfg["patch_size"], cfg["num_layers"]
         hp, wp = H // p, Wd // p
         S1, S2, ST = hp * wp, L, hp * wp + L
         MT = self._mod_total
-        plan = _Plan()
-        prog: List[tuple] = []
-        scratch: Dict[str, int] = {}
-        keep: List[Tensor] = []
-
-        def sc(name, nbytes):
-            scratch[name] = max(scratch.get(name, 0), nbytes)
-            return _Ref(name)
-
-        def persist(shape, dtype):
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, list(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def linear(a: _V, wkey: str, out: _V, *, flags=0, R: Optional[_V] = None, gate=None, rpb=0, a_rpb=0, a_bs=0,
-                   c_rpb=0, c_bs=0, bias=True):
-            w = W[wkey + ".w"]
-            N, K = w.shape
-            assert K == a.C, (wkey, K, a.C)
-            ws = W.get(wkey + ".s")
-            emit(lib.mi355x_sd_linear_ex,
-                 (a.p, a.ld, a_rpb, a_bs, w.data_ptr(), ws.data_ptr() if ws is not None else None, out.p, out.ld, c_rpb,
-                  c_bs, a.rows, N, K,
-                  W[wkey + ".b"].data_ptr() if bias else None, None, 0, gate, MT if gate is not None else 0, rpb,
-                  R.p if R else None, R.ld if R else 0, 1.0, flags, *self._gemm_ws, stream), "gemm", 2.0 * a.rows * N * K,
-                 f"{a.rows}x{N}x{K}")
+        pb = PlanBuilder(self, B)
+        plan, sc, persist, emit = pb.plan, pb.sc, pb.persist, pb.emit
+        linear = functools.partial(pb.linear_ex, ld_gate=MT)   # (the row stride of the modulation table, where a launch is gated)
 
         def adaln(x: _V, scale_ptr, shift_ptr, rpb, out: _V):
             emit(lib.mi355x_sd_adaln, (x.p, x.rows, x.C, x.ld, scale_ptr, shift_ptr, MT, rpb, 1e-6, out.p, out.ld,
@@ -379,11 +354,10 @@ class SD3Transformer2DModel(DeviceProgram, PretrainedMixin):
 
         nx = _V(sc("nx", 2 * B * S1 * D), B * S1, D)
         nc = _V(sc("nc", 2 * B * S2 * D), B * S2, D)
-        jq = sc("joint_qkv", 2 * B * ST * 3 * D)
-        ao = sc("joint_out", 2 * B * ST * D)
+        jqkv = _V(sc("joint_qkv", 2 * B * ST * 3 * D), B * ST, 3 * D)
+        jq, ao = jqkv.p, sc("joint_out", 2 * B * ST * D)
         ffx = _V(sc("ff_x", 2 * B * S1 * 4 * D), B * S1, 4 * D)
         ffc = _V(sc("ff_c", 2 * B * S2 * 4 * D), B * S2, 4 * D)
-        d = D // heads
         if w8a8:
             nx8, nc8 = _Q("nx", B * S1, D), _Q("nc", B * S2, D)
             ax8 = _Q("ax", B * S1, D)
@@ -405,9 +379,7 @@ class SD3Transformer2DModel(DeviceProgram, PretrainedMixin):
             # fused QKV of both streams into the joint [B, S1+S2, 3D] buffer (split_concat folded into the epilogue)
             lin(ax, b + ".qkv", _V(jq, B * S1, 3 * D), c_rpb=S1, c_bs=ST * 3 * D)
             lin(ac, b + ".qkv_c", _V(jq + 2 * S1 * 3 * D, B * S2, 3 * D), c_rpb=S2, c_bs=ST * 3 * D)
-            emit(lib.mi355x_sd_sdpa, (jq, jq + 2 * D, jq + 4 * D, None, ao, B, heads, ST, ST, d, ST * 3 * D, 3 * D,
-                                      ST * 3 * D, 3 * D, ST * 3 * D, 3 * D, ST * D, D, 0, 0, 0, d ** -0.5, stream),
-                 "attn", 4.0 * B * heads * ST * ST * d, f"{B}x{heads}x{ST}x{ST}x{d}")
+            pb.sdpa(jqkv.cols(0, D), jqkv.cols(D, D), jqkv.cols(2 * D, D), _V(ao, B * ST, D), heads, ST, ST)
             # to_out with the gated residual: x += gate_msa * (attn @ Wo + b)
             if w8a8:   # the rows of each stream are gathered out of the joint buffer by the quantiser
                 quant8(_V(ao, B * S1, D), ax8, x_rpb=S1, x_bs=ST * D)
@@ -442,19 +414,12 @@ class SD3Transformer2DModel(DeviceProgram, PretrainedMixin):
         emit(lib.mi355x_sd_unpatchify, (proj.data_ptr(), po, B, cfg["out_channels"], H, Wd, p, plan.out.data_ptr(),
                                         stream), "misc")
 
-        bufs = {nm: persist((max(nb, 16),), torch.uint8) for nm, nb in scratch.items()}
-        base = {nm: t.data_ptr() for nm, t in bufs.items()}
-        res = lambda a: base[a.buf] + a.off if isinstance(a, _Ref) else a  # noqa: E731
-        plan.prog = [(fn, tuple(res(a) for a in args), kind, fl) for fn, args, kind, fl in prog]
-        plan.keep, plan.graph = keep, None
+        pb.finish()
         plan.B, plan.H, plan.W, plan.L = B, H, Wd, L
         return plan
 
     def _get_plan(self, B, H, W, L) -> _Plan:
-        key = (B, H, W, L)
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, H, W, L)
-        return self._plans[key]
+        return self.plan_for((B, H, W, L), lambda: self._build_plan(B, H, W, L))
 
     def stage_inputs(self, plan: _Plan, hidden_states, encoder_hidden_states, pooled_projections, timestep) -> None:
         if torch.is_tensor(timestep):

@@ -12,13 +12,13 @@ from __future__ import annotations
 
 import math
 from types import SimpleNamespace
-from typing import Dict, List, Mapping, Optional
+from typing import Dict, Mapping, Optional
 
 import torch
 
 from . import _lib
 from .checkpoint import PretrainedMixin, Table
-from .program import DeviceProgram, _Plan
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
 Tensor = torch.Tensor
 
@@ -142,63 +142,44 @@ class T5EncoderModel(DeviceProgram, PretrainedMixin):
         return self.w["rel_bias"][bucket].permute(2, 0, 1).contiguous()   # [heads, S, S] fp32
 
     def _build_plan(self, B: int, S: int) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
-        stream = self._stream_ptr
+        cfg, lib, W = self.cfg, self._lib, self.w
         D, H, dk, Fd, n = cfg["d_model"], cfg["num_heads"], cfg["d_kv"], cfg["d_ff"], cfg["num_layers"]
         inner, eps = H * dk, float(cfg["layer_norm_epsilon"])
         rows = B * S
-        plan = _Plan()
-        prog: List[tuple] = []
-        keep: List[Tensor] = []
+        pb = PlanBuilder(self, B)
+        plan, persist, emit, stream = pb.plan, pb.persist, pb.emit, pb.stream
 
-        def persist(shape, dtype) -> Tensor:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
+        def linear(a: _V, wkey, out: _V, R: Optional[_V] = None):
+            pb.linear(a, wkey, out, bias=False, R=R)
 
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, tuple(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def linear(a: Tensor, lda, wkey, out: Tensor, ldc, R: Optional[Tensor] = None):
-            w = W[wkey]
-            N, K = w.shape
-            emit(lib.mi355x_sd_linear, (a.data_ptr(), lda, w.data_ptr(), out.data_ptr(), ldc, rows, N, K, None, None, 0, 0,
-                                        R.data_ptr() if R is not None else None, N if R is not None else 0, 1.0, 0, *self._gemm_ws, stream),
-                 "gemm", 2.0 * rows * N * K, f"{rows}x{N}x{K}")
-
-        def rms(x: Tensor, wkey, out: Tensor):
-            emit(lib.mi355x_sd_rmsnorm, (x.data_ptr(), rows, D, D, W[wkey].data_ptr(), eps, out.data_ptr(), D, stream), "ln")
+        def rms(x: _V, wkey, out: _V):
+            emit(lib.mi355x_sd_rmsnorm, (x.p, rows, D, D, W[wkey].data_ptr(), eps, out.p, D, stream), "ln")
 
         plan.ids = persist((rows,), torch.int32)
         bias = persist((H, S, S), torch.float32)
         bias.copy_(self._position_bias(S))
         plan.consts = [bias]       # filled here, read by every run (paddlemix_amd/export.py ships its contents)
-        xa, xb = persist((rows, D), _lib.elem_dtype()), persist((rows, D), _lib.elem_dtype())
-        h = persist((rows, D), _lib.elem_dtype())
-        qkv = persist((rows, 3 * inner), _lib.elem_dtype())
-        ao = persist((rows, inner), _lib.elem_dtype())
-        wi = persist((rows, 2 * Fd), _lib.elem_dtype())
-        ff = persist((rows, Fd), _lib.elem_dtype())
+        xa, xb, h, qkv, ao, wi, ff = (_V.of(persist((rows, C), _lib.elem_dtype())) for C in (D, D, D, 3 * inner, inner, 2 * Fd, Fd))
         plan.last = persist((rows, D), _lib.elem_dtype())
-        emit(lib.mi355x_sd_embed_tokens, (plan.ids.data_ptr(), rows, S, W["tok"].data_ptr(), None, D, xa.data_ptr(), D,
-                                          stream), "misc")
+        emit(lib.mi355x_sd_embed_tokens, (plan.ids.data_ptr(), rows, S, W["tok"].data_ptr(), None, D, xa.p, D, stream), "misc")
         for i in range(n):
             rms(xa, f"l{i}.ln0", h)
-            linear(h, D, f"l{i}.qkv.w", qkv, 3 * inner)
-            qp = qkv.data_ptr()
-            emit(lib.mi355x_sd_sdpa, (qp, qp + 2 * inner, qp + 4 * inner, bias.data_ptr(), ao.data_ptr(), B, H, S, S, dk,
-                                      S * 3 * inner, 3 * inner, S * 3 * inner, 3 * inner, S * 3 * inner, 3 * inner,
-                                      S * inner, inner, 0, S * S, S, 1.0, stream),
-                 "attn", 4.0 * B * H * S * S * dk, f"{B}x{H}x{S}x{S}x{dk}")
-            linear(ao, inner, f"l{i}.o.w", xb, D, R=xa)
+            linear(h, f"l{i}.qkv", qkv)
+            # T5 attention: no 1/sqrt(d) scaling, the relative-position bias [heads, S, S] shared by the batch items
+            pb.sdpa(qkv.cols(0, inner), qkv.cols(inner, inner), qkv.cols(2 * inner, inner), ao, H, S, S, bias.data_ptr(), (0, S * S, S),
+                    scale=1.0)
+            linear(ao, f"l{i}.o", xb, R=xa)
             rms(xb, f"l{i}.ln1", h)
-            linear(h, D, f"l{i}.wi.w", wi, 2 * Fd)
-            emit(lib.mi355x_sd_gated_activation, (wi.data_ptr(), 2 * Fd, ff.data_ptr(), Fd, rows, Fd, 3, stream), "misc")
-            linear(ff, Fd, f"l{i}.wo.w", xa, D, R=xb)
-        rms(xa, "lnf", plan.last)
-        plan.prog, plan.keep, plan.graph = prog, keep, None
+            linear(h, f"l{i}.wi", wi)
+            emit(lib.mi355x_sd_gated_activation, (wi.p, 2 * Fd, ff.p, Fd, rows, Fd, 3, stream), "misc")
+            linear(ff, f"l{i}.wo", xa, R=xb)
+        rms(xa, "lnf", _V.of(plan.last))
+        pb.finish()
         plan.out = plan.last
         return plan
+
+    def _get_plan(self, B, S) -> _Plan:
+        return self.plan_for((B, S), lambda: self._build_plan(B, S))
 
     def forward(self, input_ids: Tensor, attention_mask=None, output_hidden_states=None, return_dict: Optional[bool] = True):
         if input_ids is None:
@@ -211,10 +192,7 @@ class T5EncoderModel(DeviceProgram, PretrainedMixin):
         self.require_gpu(ids)
         if int(ids.min()) < 0 or int(ids.max()) >= cfg["vocab_size"]:
             raise ValueError("input_ids out of range of the token embedding")
-        key = (B, S)
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, S)
-        plan = self._plans[key]
+        plan = self._get_plan(B, S)
         self.run_staged(plan, lambda nb: plan.ids.copy_(ids.reshape(-1).to(torch.int32), non_blocking=nb))
         last = plan.last.reshape(B, S, cfg["d_model"]).float()
         if not return_dict:

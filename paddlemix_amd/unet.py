@@ -28,9 +28,9 @@ from typing import Dict, List, Mapping, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import CONV_KB64, GEGLU, OUT_F32, R_F32, SILU
+from ._lib import GEGLU, OUT_F32, SILU
 from .checkpoint import PretrainedMixin, Table
-from .program import DeviceProgram, _Plan, _Ref, _V
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
 Tensor = torch.Tensor
 
@@ -504,84 +504,14 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
     # ------------------------------------------------------------------ plan
     def _build_plan(self, B: int, H: int, Wd: int, L: int, masked: bool = False, controlnet: bool = False,
                     self_mask_len: int = 0) -> _Plan:
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
+        cfg, lib = self.cfg, self._lib
         stream = self._stream_ptr
         boc = cfg["block_out_channels"]
-        groups, eps = cfg["norm_num_groups"], float(cfg["norm_eps"])
+        eps = float(cfg["norm_eps"])
         ted = boc[0] * 4
-        plan = _Plan()
-        prog: List[tuple] = []     # (cfunc, args(list with _Ref placeholders), kind, flops)
-        scratch: Dict[str, int] = {}
-        keep: List[Tensor] = []
-
-        def sc(name: str, nbytes: int) -> _Ref:
-            scratch[name] = max(scratch.get(name, 0), nbytes)
-            return _Ref(name)
-
-        def persist(shape, dtype) -> Tensor:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def wp(key):
-            return W[key].data_ptr()
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, list(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def linear(a: _V, wkey: str, out: _V, bias=True, R: Optional[_V] = None, flags=0, out_scale=1.0,
-                   rowbias=None, rpb=0, ld_rb=0, bkey=None):
-            w = W[wkey + ".w"]
-            N, K = w.shape
-            assert K == a.C, (wkey, K, a.C)
-            b = (W[bkey] if bkey else W[wkey + ".b"]).data_ptr() if bias else None
-            assert a.es == 2, (wkey, "fp32 rows cannot be an MFMA operand")
-            flags |= (OUT_F32 if out.es == 4 else 0) | (R_F32 if (R is not None and R.es == 4) else 0)
-            emit(lib.mi355x_sd_linear,
-                 (a.p, a.ld, w.data_ptr(), out.p, out.ld, a.rows, N, K, b, rowbias, rpb, ld_rb,
-                  R.p if R else None, R.ld if R else 0, out_scale, flags, *self._gemm_ws, stream), "gemm", 2.0 * a.rows * N * K,
-                 f"{a.rows}x{N}x{K}" + ("g" if flags & GEGLU else ""))
-
-        def conv3(x: _V, h, w_, wkey, out: _V, stride=1, up=0, rowbias=None, R: Optional[_V] = None, out_scale=1.0, flags=0):
-            w = W[wkey + ".w"]
-            Cout = w.shape[0]
-            ho = ((h << up) + 2 - 3) // stride + 1
-            wo = ((w_ << up) + 2 - 3) // stride + 1
-            assert x.es == 2, (wkey, "fp32 rows cannot be an MFMA operand")
-            flags |= (OUT_F32 if out.es == 4 else 0) | (R_F32 if (R is not None and R.es == 4) else 0)
-            flags |= CONV_KB64 if wkey in self._kb64 else 0
-            emit(lib.mi355x_sd_conv3x3,
-                 (x.p, x.ld, B, h, w_, x.C, stride, up, w.data_ptr(), out.p, out.ld, Cout, W[wkey + ".b"].data_ptr(),
-                  rowbias, self._temb_total if rowbias is not None else 0, R.p if R else None, R.ld if R else 0,
-                  out_scale, flags, *self._gemm_ws, stream), "conv", 2.0 * B * ho * wo * Cout * 9 * x.C,
-                 f"{B * ho * wo}x{Cout}x{9 * x.C}" + ("s2" if stride == 2 else "") + ("up" if up else ""))
-
-        def gnorm(x: _V, hw, nkey, eps_, silu, raw16: Optional[_V] = None) -> _V:
-            """GroupNorm (+SiLU) of x -> 16-bit rows. fp32-residual mode: x is fp32; `raw16` (optional) receives the 16-bit
-            rounding of the raw x rows in the same pass (the operand of a conv_shortcut GEMM)."""
-            nws = lib.mi355x_sd_groupnorm_workspace_floats(B, hw, x.C)
-            ws = sc("gn_ws", 4 * nws)
-            ss = sc("gn_ss", 4 * B * 2 * x.C)
-            y = _V(sc("gn", 2 * x.rows * x.C), x.rows, x.C)
-            if x.es == 2 and lib.mi355x_sd_groupnorm_act_fits(hw, x.C, groups):
-                # small (batch, group) chunks: statistics + affine (+SiLU) in one launch (csrc/norm.hip gn_fused_kernel)
-                assert raw16 is None
-                emit(lib.mi355x_sd_groupnorm_act, (x.p, B, hw, x.C, x.ld, groups, eps_, wp(nkey + ".g"), wp(nkey + ".b"),
-                                                   1 if silu else 0, y.p, y.ld, stream), "gn_fused")
-                return y
-            if x.es == 2:
-                assert raw16 is None
-                emit(lib.mi355x_sd_groupnorm_stats, (x.p, B, hw, x.C, x.ld, groups, eps_, wp(nkey + ".g"), wp(nkey + ".b"),
-                                                     ws, ss, stream), "gn_stats")
-                emit(lib.mi355x_sd_scale_shift_act, (x.p, B, hw, x.C, x.ld, ss, 1 if silu else 0, y.p, y.ld, stream),
-                     "gn_apply")
-            else:
-                emit(lib.mi355x_sd_groupnorm_stats_ex, (x.p, B, hw, x.C, x.ld, groups, eps_, wp(nkey + ".g"),
-                                                        wp(nkey + ".b"), ws, ss, 1, stream), "gn_stats")
-                emit(lib.mi355x_sd_scale_shift_act_ex, (x.p, B, hw, x.C, x.ld, ss, 1 if silu else 0, y.p, y.ld, 1,
-                                                        raw16.p if raw16 else None, raw16.ld if raw16 else 0, stream),
-                     "gn_apply")
-            return y
+        pb = PlanBuilder(self, B)
+        plan, sc, persist, emit, wp = pb.plan, pb.sc, pb.persist, pb.emit, pb.wp
+        linear, conv3, gnorm, lnorm = pb.linear, pb.conv3, pb.gnorm, pb.lnorm
 
         def cast16(x: _V, name: str) -> _V:
             """16-bit copy of fp32 rows (operand of the down / upsampling convs in the fp32-residual mode)"""
@@ -591,50 +521,31 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
             emit(lib.mi355x_sd_cast_rows, (x.p, x.ld, y.p, y.ld, x.rows, x.C, stream), "misc")
             return y
 
-        def lnorm(x: _V, nkey, out: _V):
-            if x.es == 2:
-                emit(lib.mi355x_sd_layernorm, (x.p, x.rows, x.C, x.ld, wp(nkey + ".g"), wp(nkey + ".b"), 1e-5, out.p,
-                                               out.ld, stream), "ln")
-            else:
-                emit(lib.mi355x_sd_layernorm_ex, (x.p, x.rows, x.C, x.ld, wp(nkey + ".g"), wp(nkey + ".b"), 1e-5, out.p,
-                                                  out.ld, 1, stream), "ln")
-
         def ln_linear(x: _V, wkey: str, out: _V, flags=0):
             """LayerNorm(eps 1e-5, attention.py:318-331) folded into the projection: statistics pass + raw-row GEMM"""
-            w = W[wkey + ".w"]
-            N, K = w.shape
+            N, K = self.w[wkey + ".w"].shape
             assert K == x.C, (wkey, K, x.C)
             st = sc("t_stats", 8 * x.rows)
             emit(lib.mi355x_sd_row_stats, (x.p, x.rows, x.C, x.ld, 1e-5, st, stream), "ln")
-            emit(lib.mi355x_sd_linear_ln, (x.p, x.ld, st, w.data_ptr(), wp(wkey + ".ws"), out.p, out.ld, x.rows, N, K,
+            emit(lib.mi355x_sd_linear_ln, (x.p, x.ld, st, wp(wkey + ".w"), wp(wkey + ".ws"), out.p, out.ld, x.rows, N, K,
                                            wp(wkey + ".b"), flags, *self._gemm_ws, stream), "gemm", 2.0 * x.rows * N * K,
                  f"{x.rows}x{N}x{K}" + ("g" if flags & GEGLU else ""))
 
         def attention(q: _V, k: _V, v: _V, out: _V, heads, sq, skv, bias=None, accum: Optional[float] = None, log2=False):
-            d = q.C // heads
             if log2 and bias is not None:
                 # q already carries head_dim^-0.5 * log2(e) (folded into to_q at load) but the masked kernel exponentiates
                 # exp2((q.k + bias / scale) * scale * log2(e)): scale = ln 2 makes that exp2(q.k + bias * log2(e)) -- the same softmax
                 assert accum is None
-                args = (q.p, k.p, v.p, bias, out.p, B, heads, sq, skv, d, sq * q.ld, q.ld, skv * k.ld, k.ld, skv * v.ld, v.ld,
-                        sq * out.ld, out.ld, skv, 0, 0, math.log(2.0))
-                emit(lib.mi355x_sd_sdpa, args + (stream,), "attn", 4.0 * B * heads * sq * skv * d, f"{B}x{heads}x{sq}x{skv}x{d}m")
-                return
-            if log2:
-                assert bias is None and accum is None and d == 64
-                emit(lib.mi355x_sd_sdpa_ex, (q.p, k.p, v.p, None, out.p, B, heads, sq, skv, d, sq * q.ld, q.ld, skv * k.ld, k.ld,
-                                             skv * v.ld, v.ld, sq * out.ld, out.ld, 0, 0, 0, 1.0, _lib.SDPA_LOG2, stream), "attn",
-                     4.0 * B * heads * sq * skv * d, f"{B}x{heads}x{sq}x{skv}x{d}")
-                return
-            # bias: additive encoder mask [B, skv] broadcast over heads and queries (unet_2d_condition.py:921-927)
-            args = (q.p, k.p, v.p, bias, out.p, B, heads, sq, skv, d, sq * q.ld, q.ld, skv * k.ld, k.ld, skv * v.ld, v.ld,
-                    sq * out.ld, out.ld, skv if bias else 0, 0, 0, d ** -0.5)
-            if accum is None:
-                emit(lib.mi355x_sd_sdpa, args + (stream,), "attn", 4.0 * B * heads * sq * skv * d,
-                     f"{B}x{heads}x{sq}x{skv}x{d}")
+                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv, 0, 0), math.log(2.0), suffix="m")
+            elif log2:
+                assert accum is None and q.C // heads == 64
+                pb.sdpa(q, k, v, out, heads, sq, skv, scale=1.0, fn=lib.mi355x_sd_sdpa_ex, tail=(_lib.SDPA_LOG2,))
+            elif accum is None:
+                # bias: additive encoder mask [B, skv] broadcast over heads and queries (unet_2d_condition.py:921-927)
+                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0))
             else:   # out += accum * attention (the image-token half of IPAdapterAttnProcessor)
-                emit(lib.mi355x_sd_sdpa_accum, args + (float(accum), stream), "attn", 4.0 * B * heads * sq * skv * d,
-                     f"{B}x{heads}x{sq}x{skv}x{d}+")
+                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0), fn=lib.mi355x_sd_sdpa_accum,
+                        tail=(float(accum),), suffix="+")
 
         # ---- inputs (static buffers; staged by __call__) ----
         plan.sample = persist((B, cfg["in_channels"], H, Wd), torch.float32)
@@ -715,7 +626,7 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
             plan.text_dim = None  # widths of text_embeds / time_ids are only known at the first call
             plan._pdim, plan._atd = pdim, atd
             a1 = persist((B, ted), _lib.elem_dtype())
-            plan._add_emit_index = len(prog)  # the time_ids embedding op is inserted here once widths are known
+            plan._add_emit_index = len(pb.prog)  # the time_ids embedding op is inserted here once widths are known
             linear(_V(plan.add_in.data_ptr(), B, pdim), "add_embedding.linear_1", _V(a1.data_ptr(), B, ted),
                    flags=SILU)
             linear(_V(a1.data_ptr(), B, ted), "add_embedding.linear_2", emb, R=emb)
@@ -796,7 +707,7 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
             g1 = gnorm(x, hw, name + ".norm1", eps, True, raw16=x16)
             h1 = _V(sc("h1", RES * rows * cout), rows, cout, es=RES)   # fp32 mode: GroupNorm 2 reads the unrounded conv1 output
             rb = temb_all.data_ptr() + 4 * self._temb_off[name]
-            conv3(g1, h, w_, name + ".conv1", h1, rowbias=rb)
+            conv3(g1, h, w_, name + ".conv1", h1, rowbias=rb, ld_rb=self._temb_total)
             g2 = gnorm(h1, hw, name + ".norm2", eps, True)
             if need_short:
                 short = _V(sc("short", RES * rows * cout), rows, cout, es=RES)
@@ -866,7 +777,7 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
                                                wp("conv_in.b"), cur.p, B, cfg["in_channels"], H, Wd, boc[0], cur.ld, 1,
                                                stream), "misc")
         if self._encoder_only:
-            self._emit_pre(plan, cur, B, H, Wd, persist, emit, conv3)
+            self._emit_pre(pb, cur, H, Wd)
         k = 1
         tmp_i = 0
 
@@ -951,25 +862,16 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
         assert k == len(skips) and u == len(ups) and ((h, w_) == (H, Wd) or self._encoder_only)
 
         if self._encoder_only:
-            self._emit_post(plan, [skip_slot(kk) for kk in range(len(skips))], skips, cur, h, w_, B, persist, emit, linear, sc)
+            self._emit_post(pb, [skip_slot(kk) for kk in range(len(skips))], skips, cur, h, w_)
         else:
             # ---- post (unet_2d_condition.py:1193-1196) ----
             g = gnorm(cur, H * Wd, "conv_norm_out", eps, True)
             emit(lib.mi355x_sd_conv_out3x3, (g.p, g.ld, wp("conv_out.w"), wp("conv_out.b"), plan.out.data_ptr(), B, g.C, H,
                                              Wd, cfg["out_channels"], stream), "misc")
 
-        # ---- allocate scratch, resolve addresses ----
-        bufs = {n: persist((max(nb, 16),), torch.uint8) for n, nb in scratch.items()}
-        base = {n: t.data_ptr() for n, t in bufs.items()}
-
-        def res(a):
-            return base[a.buf] + a.off if isinstance(a, _Ref) else a
-
-        plan.prog = [(fn, tuple(res(a) for a in args), kind, fl) for fn, args, kind, fl in prog]
-        plan.keep = keep
-        plan.graph = None
+        pb.finish()
         plan.B, plan.H, plan.W, plan.L = B, H, Wd, L
-        plan.scratch_bytes = sum(t.numel() * t.element_size() for t in keep)
+        plan.scratch_bytes = sum(t.numel() * t.element_size() for t in plan.keep)
         plan.emb_tensors = dict(t0=t0, emb=emb_t, temb_all=temb_all)
         return plan
 
@@ -1001,10 +903,8 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
     def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False, self_mask_len: int = 0) -> _Plan:
         if masked and self._ip:
             raise NotImplementedError("encoder_attention_mask together with IP-Adapter image tokens")
-        key = (B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len)
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, H, W, L, masked, controlnet, self_mask_len)
-        return self._plans[key]
+        return self.plan_for((B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len),
+                             lambda: self._build_plan(B, H, W, L, masked, controlnet, self_mask_len))
 
     def stage_inputs(self, plan: _Plan, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
                      in_scale: Optional[float] = None, encoder_attention_mask=None,
@@ -1237,17 +1137,18 @@ class ControlNetModel(UNet2DConditionModel):
         self._n_down = k
         put_conv("cn.mid", "controlnet_mid_block")
 
-    def _emit_pre(self, plan, x0: _V, B, H, Wd, persist, emit, conv3) -> None:
+    def _emit_pre(self, pb: PlanBuilder, x0: _V, H, Wd) -> None:
         """ControlNetConditioningEmbedding.forward (controlnet.py:103-113) + ``sample = conv_in(sample) + cond`` (:807-810)"""
-        lib, W, stream = self._lib, self.w, self._stream_ptr
+        lib, stream = self._lib, self._stream_ptr
+        plan, B, persist, emit, wp, conv3 = pb.plan, pb.B, pb.persist, pb.emit, pb.wp, pb.conv3
         ch = self._extra["conditioning_embedding_out_channels"]
         f = 1 << (len(ch) - 1)
         hc, wc = H * f, Wd * f
         plan.cond = persist((B, self._extra["conditioning_channels"], hc, wc), torch.float32)
         bufs = [persist((B * hc * wc * ch[0],), _lib.elem_dtype()), persist((B * hc * wc * ch[0],), _lib.elem_dtype())]
         e = _V(bufs[0].data_ptr(), B * hc * wc, ch[0])
-        emit(lib.mi355x_sd_conv_in3x3, (plan.cond.data_ptr(), None, W["cn.conv_in.w"].data_ptr(), W["cn.conv_in.b"].data_ptr(),
-                                        e.p, B, self._extra["conditioning_channels"], hc, wc, ch[0], e.ld, stream), "misc")
+        emit(lib.mi355x_sd_conv_in3x3, (plan.cond.data_ptr(), None, wp("cn.conv_in.w"), wp("cn.conv_in.b"), e.p, B,
+                                        self._extra["conditioning_channels"], hc, wc, ch[0], e.ld, stream), "misc")
         emit(lib.mi355x_sd_silu, (e.p, e.p, B * hc * wc * ch[0], 0, 0, stream), "misc")
         which = 0
         for i in range(len(ch) - 1):
@@ -1260,9 +1161,9 @@ class ControlNetModel(UNet2DConditionModel):
         assert (hc, wc) == (H, Wd)
         conv3(e, hc, wc, "cn.conv_out", x0, R=x0)
 
-    def _emit_post(self, plan, slots, skips, mid: _V, hm, wm, B, persist, emit, linear, sc) -> None:
+    def _emit_post(self, pb: PlanBuilder, slots, skips, mid: _V, hm, wm) -> None:
         """zero convolutions + scaling (controlnet.py:842-869) -> fp32 NCHW residuals"""
-        lib, stream = self._lib, self._stream_ptr
+        lib, stream, plan, B = self._lib, self._stream_ptr, pb.plan, pb.B
         scale, guess = self._cn_key
         n = len(slots)
         if n != self._n_down:
@@ -1273,17 +1174,14 @@ class ControlNetModel(UNet2DConditionModel):
         plan.ctrl_out = []
         for k, (sl, (cs, hs, ws_)) in enumerate(list(zip(slots, skips)) + [(mid, (mid.C, hm, wm))]):
             key = f"cn.down.{k}" if k < n else "cn.mid"
-            rows = _V(sc("cn_rows", 2 * sl.rows * cs), sl.rows, cs)
-            linear(sl, key, rows, out_scale=scales[k])
-            out = persist((B, cs, hs, ws_), torch.float32)
-            emit(lib.mi355x_sd_unpatchify, (rows.p, rows.ld, B, cs, hs, ws_, 1, out.data_ptr(), stream), "misc")
+            rows = _V(pb.sc("cn_rows", 2 * sl.rows * cs), sl.rows, cs)
+            pb.linear(sl, key, rows, out_scale=scales[k])
+            out = pb.persist((B, cs, hs, ws_), torch.float32)
+            pb.emit(lib.mi355x_sd_unpatchify, (rows.p, rows.ld, B, cs, hs, ws_, 1, out.data_ptr(), stream), "misc")
             plan.ctrl_out.append(out)
 
     def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False) -> _Plan:
-        key = (B, H, W, L, masked) + self._cn_key
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, H, W, L, masked, False)
-        return self._plans[key]
+        return self.plan_for((B, H, W, L, masked) + self._cn_key, lambda: self._build_plan(B, H, W, L, masked, False))
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale: float = 1.0,
                 class_labels=None, timestep_cond=None, attention_mask=None, added_cond_kwargs=None,

@@ -37,14 +37,14 @@ The training-only ``kl`` / ``nll`` are not built. There is no CPU fallback.
 from __future__ import annotations
 
 from types import SimpleNamespace
-from typing import Dict, List, Mapping, Optional
+from typing import Dict, Mapping, Optional
 
 import torch
 
 from . import _lib
 from ._lib import OUT_F32, PAD_BR
 from .checkpoint import PretrainedMixin, load_pretrained
-from .program import DeviceProgram, _Plan, _Ref, _V
+from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
 Tensor = torch.Tensor
 
@@ -343,59 +343,13 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
     # ------------------------------------------------------------------ plan
     def _build_plan(self, B: int, h: int, w_: int, in_scale: float, mode: str = "decode") -> _Plan:
         """``mode="decode"``: h x w is the latent grid; ``mode="encode"``: the image."""
-        cfg, lib, dev, W = self.cfg, self._lib, self.device, self.w
+        cfg, lib, W = self.cfg, self._lib, self.w
         stream = self._stream_ptr
-        boc, lc, groups = cfg["block_out_channels"], cfg["latent_channels"], cfg["norm_num_groups"]
+        boc, lc = cfg["block_out_channels"], cfg["latent_channels"]
         nlev = len(boc)
-        plan = _Plan()
-        prog: List[tuple] = []
-        scratch: Dict[str, int] = {}
-        keep: List[Tensor] = []
-
-        def sc(name, nbytes):
-            scratch[name] = max(scratch.get(name, 0), nbytes)
-            return _Ref(name)
-
-        def persist(shape, dtype) -> Tensor:
-            t = torch.empty(shape, device=dev, dtype=dtype)
-            keep.append(t)
-            return t
-
-        def wp(key):
-            return W[key].data_ptr()
-
-        def emit(fn, args, kind, flops=0.0, desc=""):
-            prog.append((fn, list(args), kind if not desc else f"{kind}:{desc}", flops))
-
-        def gemm(a_p, lda, w_p, c_p, ldc, M, N, K, bias=None, R: Optional[_V] = None, out_scale=1.0, flags=0):
-            emit(lib.mi355x_sd_linear, (a_p, lda, w_p, c_p, ldc, M, N, K, bias, None, 0, 0, R.p if R else None,
-                                        R.ld if R else 0, out_scale, flags, *self._gemm_ws, stream), "gemm", 2.0 * M * N * K,
-                 f"{M}x{N}x{K}")
-
-        def conv3(x: _V, hh, ww, wkey, out: _V, up=0, R: Optional[_V] = None, stride=1, flags=0):
-            cout = W[wkey + ".w"].shape[0]
-            pad2 = 1 if flags & PAD_BR else 2
-            ho, wo = ((hh << up) + pad2 - 3) // stride + 1, ((ww << up) + pad2 - 3) // stride + 1
-            emit(lib.mi355x_sd_conv3x3, (x.p, x.ld, B, hh, ww, x.C, stride, up, wp(wkey + ".w"), out.p, out.ld, cout,
-                                         wp(wkey + ".b"), None, 0, R.p if R else None, R.ld if R else 0, 1.0, flags,
-                                         *self._gemm_ws, stream),
-                 "conv", 2.0 * B * ho * wo * cout * 9 * x.C,
-                 f"{B * ho * wo}x{cout}x{9 * x.C}" + ("up" if up else "") + ("s2" if stride == 2 else ""))
-
-        def gnorm(x: _V, hw, nkey, silu) -> _V:
-            nws = lib.mi355x_sd_groupnorm_workspace_floats(B, hw, x.C)
-            ws = sc("gn_ws", 4 * nws)
-            ss = sc("gn_ss", 4 * B * 2 * x.C)
-            y = _V(sc("gn", 2 * x.rows * x.C), x.rows, x.C)
-            if lib.mi355x_sd_groupnorm_act_fits(hw, x.C, groups):   # small (batch, group) chunks: one launch (csrc/norm.hip gn_fused_kernel)
-                emit(lib.mi355x_sd_groupnorm_act, (x.p, B, hw, x.C, x.ld, groups, 1e-6, wp(nkey + ".g"), wp(nkey + ".b"),
-                                                   1 if silu else 0, y.p, y.ld, stream), "gn_fused")
-                return y
-            emit(lib.mi355x_sd_groupnorm_stats, (x.p, B, hw, x.C, x.ld, groups, 1e-6, wp(nkey + ".g"), wp(nkey + ".b"),
-                                                 ws, ss, stream), "gn_stats")
-            emit(lib.mi355x_sd_scale_shift_act, (x.p, B, hw, x.C, x.ld, ss, 1 if silu else 0, y.p, y.ld, stream),
-                 "gn_apply")
-            return y
+        pb = PlanBuilder(self, B)
+        plan, sc, persist, emit, wp, linear, conv3 = pb.plan, pb.sc, pb.persist, pb.emit, pb.wp, pb.linear, pb.conv3
+        gnorm = lambda x, hw, nkey, silu: pb.gnorm(x, hw, nkey, 1e-6, silu)  # noqa: E731
 
         flip = [0]
 
@@ -412,8 +366,7 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             R = x
             if (name + ".conv_shortcut.w") in W:
                 R = _V(sc("sc", 2 * x.rows * cout), x.rows, cout)
-                gemm(x.p, x.ld, wp(name + ".conv_shortcut.w"), R.p, R.ld, x.rows, cout, x.C,
-                     bias=wp(name + ".conv_shortcut.b"))
+                linear(x, name + ".conv_shortcut", R)
             out = main_buf(x.rows, cout)
             conv3(g2, hh, ww, name + ".conv2", out, R=R)
             return out
@@ -427,19 +380,20 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             q = _V(sc("att_q", 2 * rows * C), rows, C)
             k = _V(sc("att_k", 2 * rows * C), rows, C)
             o = _V(sc("att_o", 2 * rows * C), rows, C)
-            gemm(y.p, y.ld, wp(a + ".to_q.w"), q.p, q.ld, rows, C, C, bias=wp(a + ".to_q.b"))
-            gemm(y.p, y.ld, wp(a + ".to_k.w"), k.p, k.ld, rows, C, C, bias=wp(a + ".to_k.b"))
-            vt = sc("att_vt", 2 * C * S)
-            scores = sc("att_s", 4 * S * S)
-            probs = sc("att_p", 2 * S * S)
-            for b in range(B):
-                r0 = 2 * b * S * C   # byte offset of image b's rows
-                gemm(wp(a + ".to_v.w"), C, y.p + r0, vt, S, C, S, C)                     # V^T [C][S] = Wv X^T
-                gemm(q.p + r0, q.ld, k.p + r0, scores, S, S, S, C, out_scale=C ** -0.5, flags=OUT_F32)
-                emit(lib.mi355x_sd_softmax_rows, (scores, S, probs, S, S, S, stream), "attn_softmax")
-                gemm(probs, S, vt, o.p + r0, o.ld, S, C, S)
+            linear(y, a + ".to_q", q)
+            linear(y, a + ".to_k", k)
+            wv = _V(wp(a + ".to_v.w"), C, C)
+            vt = _V(sc("att_vt", 2 * C * S), C, S)
+            scores = _V(sc("att_s", 4 * S * S), S, S, es=4)
+            probs = _V(sc("att_p", 2 * S * S), S, S)
+            img = lambda v, b: _V(v.p + 2 * b * S * C, S, C, v.ld)  # noqa: E731  (image b's rows of y / q / k / o)
+            for b in range(B):   # activations times activations
+                linear(wv, img(y, b), vt, bias=False)                                     # V^T [C][S] = Wv X^T
+                linear(img(q, b), img(k, b), scores, bias=False, out_scale=C ** -0.5)
+                emit(lib.mi355x_sd_softmax_rows, (scores.p, S, probs.p, S, S, S, stream), "attn_softmax")
+                linear(probs, vt, img(o, b), bias=False)
             x2 = main_buf(rows, C)
-            gemm(o.p, o.ld, wp(a + ".to_out.0.w"), x2.p, x2.ld, rows, C, C, bias=wp(a + ".to_out.0.b"), R=x)
+            linear(o, a + ".to_out.0", x2, R=x)
             return resnet(x2, side + ".mid_block.resnets.1", hh, ww)
 
         if mode == "encode":
@@ -498,19 +452,12 @@ class AutoencoderKL(DeviceProgram, PretrainedMixin):
             emit(lib.mi355x_sd_conv_out3x3, (g.p, g.ld, wp("decoder.conv_out.w"), wp("decoder.conv_out.b"),
                                              plan.out.data_ptr(), B, g.C, hh, ww, cfg["out_channels"], stream), "misc")
 
-        bufs = {nm: persist((max(nb, 16),), torch.uint8) for nm, nb in scratch.items()}
-        base = {nm: t.data_ptr() for nm, t in bufs.items()}
-        res = lambda v: base[v.buf] + v.off if isinstance(v, _Ref) else v  # noqa: E731
-        plan.prog = [(fn, tuple(res(v) for v in args), kind, fl) for fn, args, kind, fl in prog]
-        plan.keep, plan.graph = keep, None
+        pb.finish()
         plan.B = B
         return plan
 
     def _get_plan(self, B, h, w_, in_scale, mode: str = "decode") -> _Plan:
-        key = (mode, B, h, w_, float(in_scale))
-        if key not in self._plans:
-            self._plans[key] = self._build_plan(B, h, w_, in_scale, mode)
-        return self._plans[key]
+        return self.plan_for((mode, B, h, w_, float(in_scale)), lambda: self._build_plan(B, h, w_, in_scale, mode))
 
     def _max_batch(self, h: int, w_: int, mode: str = "decode") -> int:
         """images of h x w one launch sequence may hold (the _MAX_ELEMS rule on the widest activation)"""
