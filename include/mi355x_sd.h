@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 15
+#define MI355X_SD_ABI_VERSION 16
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -493,6 +493,37 @@ int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const f
 int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const float* eps_text, const float* m_prev, float* out,
                                float* m_out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
                                int64_t per_sample, void* stream);
+
+/* One step of UniPC sampling (UniPCMultistepScheduler: solver_order 1-3, bh1 / bh2, predict_x0 or not) in one launch: guidance
+ * combine, guidance rescale, convert_model_output, the B(h) corrector, the B(h) predictor, last_sample and the history shift.
+ * State the caller owns for the duration of a loop, fp32 device memory: `last`, one plane of batch * per_sample floats, and `hist`,
+ * `order` such planes, plane 0 the newest converted model output. Per element, with e the guided (and rescaled) model output as in
+ * mi355x_sd_multistep_update, L = last and h1, h2, h3 = planes 0, 1, 2 before this call:
+ *   m_t = p*x + q*e
+ *   x_c = Ac*L + Bc*h1 + C2*(h2 - h1) + C3*(h3 - h1) + Ct*(m_t - h1)   if corr != 0, else x_c = x          -> last
+ *   out = Ap*x_c + Bp*m_t + D1*(h1 - m_t) + D2*(h2 - m_t)
+ *   plane[k] <- plane[k-1] for k = order-1 .. 1, plane[0] <- m_t
+ * Rules:
+ *  - coef is 12 fp32 values (p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr) in device memory, 16-byte aligned, read by the kernel
+ *    (UniPCMultistepScheduler.unipc_coefficients): every pointer stays fixed from step to step and a captured graph of one node
+ *    replays a whole loop with only the row changing.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - a term whose coefficient is 0.0 is not formed and its operand does not enter the arithmetic: L, each plane inside a difference,
+ *    the whole corrector when corr == 0. These are wave-uniform branches on the values of the row. The uninitialised last / hist of a
+ *    fresh loop, or of an img2img start inside the schedule, therefore never reach out. Planes at or past `order` are never touched.
+ *  - the shift may copy uninitialised planes, bit for bit; that is harmless.
+ *  - operation order: each difference is formed first and then multiplied; the corrector's terms are summed left to right as written,
+ *    the predictor's likewise; which product contracts into which sum is the compiler's choice, as in mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when every pointer and plane is 16-byte aligned, and a scalar tail. No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap among out, last, hist, the inputs and coef is MI355X_SD_ERR_INVALID before any
+ *    launch, as are a null pointer (except eps_text), a coef that is not 16-byte aligned, order outside 1..3, batch <= 0,
+ *    per_sample < 1, and per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float* eps_text, float* last, float* hist, int order,
+                           float* out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
+                           int64_t per_sample, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

@@ -623,6 +623,38 @@ int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const fl
                                         rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
 }
 
+int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float* eps_text, float* last, float* hist, int order,
+                           float* out, const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                           void* stream) {
+  const char* who = "mi355x_sd_unipc_update";
+  if (!x || !eps_uncond || !last || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  if (order < 1 || order > 3) return fail(SD_ERR_INVALID, "%s: order must be 1, 2 or 3 (the planes of hist)", who);
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / order / batch)
+    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
+                "per_sample - 1)", who);
+  if ((uintptr_t)coef & 15) return fail(SD_ERR_INVALID, "%s: coef must be 16-byte aligned", who);
+  // blocks write out, last and hist while others still read the inputs: only the same-lane pair out = x may alias
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  struct Span {
+    const void* p;
+    uintptr_t len;
+  };
+  const Span written[3] = {{out, bytes}, {last, bytes}, {hist, bytes * (uintptr_t)order}};
+  const Span read[4] = {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 12 * sizeof(float)}};
+  auto overlaps = [](const Span& a, const Span& b) {
+    return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.len && (uintptr_t)b.p < (uintptr_t)a.p + a.len;
+  };
+  bool bad = overlaps(written[0], written[1]) || overlaps(written[0], written[2]) || overlaps(written[1], written[2]);
+  for (const Span& w : written)
+    for (const Span& r : read) bad = bad || (!(w.p == out && r.p == x && out == x) && overlaps(w, r));
+  if (bad)
+    return fail(SD_ERR_INVALID, "%s: out may be x itself; out, last and hist must not overlap each other, the inputs or coef in any "
+                "other way", who);
+  return finish(launch_unipc_update(x, eps_uncond, eps_text, last, hist, order, out, coef, guidance_scale,
+                                    rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

@@ -841,6 +841,171 @@ int launch_multistep_update(const float* x, const float* eu, const float* et, co
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
+// One step of UniPC sampling (UniPCMultistepScheduler: B(h) corrector then B(h) predictor, orders 1-3) in one launch: the guidance
+// combine, the guidance rescale, convert_model_output, the corrector, the predictor, last_sample and the history shift. With
+// coef = (p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr) in device memory (12 fp32, 16-byte aligned), L = last, h1 / h2 / h3 = the
+// history planes 0 / 1 / 2 BEFORE this step's shift (plane 0 newest), per element and IN THIS ORDER (tests/unipc_bounds.py derives
+// its bound from it; which product fuses with which sum is the compiler's choice, as in multistep_elem):
+//   e   = the guided (and rescaled) model output, as in the multistep kernels
+//   m_t = p * x + q * e                                                           convert_model_output on the UNCORRECTED x
+//   x_c = Ac * L + Bc * h1 + C2 * (h2 - h1) + C3 * (h3 - h1) + Ct * (m_t - h1)    corr != 0; corr == 0: x_c = x         -> last
+//   out = Ap * x_c + Bp * m_t + D1 * (h1 - m_t) + D2 * (h2 - m_t)
+//   plane[k] <- plane[k - 1] for k = order - 1 .. 1, plane[0] <- m_t
+// Every difference is formed first and then multiplied (C_k and D_k carry 1 / r_k: the regrouped form would cancel); the terms are
+// summed left to right as written. A term whose coefficient is 0.0 is not formed and its operand does not enter the arithmetic: L, each
+// plane inside a difference, the whole corrector at corr == 0 -- uniform branches on the device values (UpPlan), so the
+// uninitialised last / hist of a fresh loop or of an img2img start never reach out (0 * NaN). A plane a term needs is also never read
+// past `order`. The shift copies planes bit for bit whatever they hold. Every element of x / out, last and the planes is read and
+// then written by the same lane in the last pass only: out may be x, and all pointers stay fixed from step to step.
+struct UpCoef {
+  float p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr;
+};
+struct UpPlan {   // which terms are formed, which planes are read (for a term or as the shift's source)
+  bool corr, cL, cB, c2, c3, ct, d1, d2, rd1, rd2, rd3;
+};
+
+__device__ __forceinline__ UpCoef unipc_coef(const float* __restrict__ c) {
+  return {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11]};
+}
+
+__device__ __forceinline__ UpPlan unipc_plan(const UpCoef& k, int order) {
+  UpPlan f;
+  f.corr = k.corr != 0.0f;
+  f.cL = f.corr && k.Ac != 0.0f;
+  f.cB = f.corr && k.Bc != 0.0f;
+  f.c2 = f.corr && order >= 2 && k.C2 != 0.0f;
+  f.c3 = f.corr && order >= 3 && k.C3 != 0.0f;
+  f.ct = f.corr && k.Ct != 0.0f;
+  f.d1 = k.D1 != 0.0f;
+  f.d2 = order >= 2 && k.D2 != 0.0f;
+  f.rd1 = order >= 2 || f.cB || f.c2 || f.c3 || f.ct || f.d1;
+  f.rd2 = order >= 3 || f.c2 || f.d2;
+  f.rd3 = f.c3;
+  return f;
+}
+
+__device__ __forceinline__ void unipc_elem(const UpCoef& k, const UpPlan& f, float x, float e, float L, float h1, float h2, float h3,
+                                           float& o, float& xc, float& mt) {
+  mt = k.p * x + k.q * e;
+  xc = x;
+  if (f.corr) {
+    float a = 0.f;
+    if (f.cL) a = k.Ac * L;
+    if (f.cB) a += k.Bc * h1;
+    if (f.c2) a += k.C2 * (h2 - h1);
+    if (f.c3) a += k.C3 * (h3 - h1);
+    if (f.ct) a += k.Ct * (mt - h1);
+    xc = a;
+  }
+  o = k.Ap * xc + k.Bp * mt;
+  if (f.d1) o += k.D1 * (h1 - mt);
+  if (f.d2) o += k.D2 * (h2 - mt);
+}
+
+// element i of one step: x, last, hist (planes `plane` elements apart), out already offset to the sample or the batch
+__device__ __forceinline__ void unipc_at(const UpCoef& k, const UpPlan& f, int order, const float* x, float* last, float* hist,
+                                         long plane, float* out, long i, float e) {
+  const float h1 = f.rd1 ? hist[i] : 0.f, h2 = f.rd2 ? hist[plane + i] : 0.f, h3 = f.rd3 ? hist[2 * plane + i] : 0.f;
+  const float L = f.cL ? last[i] : 0.f;
+  float o, xc, mt;
+  unipc_elem(k, f, x[i], e, L, h1, h2, h3, o, xc, mt);
+  out[i] = o;
+  last[i] = xc;
+  if (order >= 3) hist[2 * plane + i] = h2;
+  if (order >= 2) hist[plane + i] = h1;
+  hist[i] = mt;
+}
+
+// gr == 0 (or no guidance): elementwise over the n = batch * per_sample elements (the planes are n apart). nv 16-byte vectors first
+// (0 when a pointer or a plane is not 16-byte aligned), then the elements 4 * nv .. n - 1 one by one: nothing past n is touched.
+template <bool CFG>
+__global__ void unipc_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et, float* last, float* hist,
+                             int order, float* out, const float* __restrict__ coef, float gs, long nv, long n) {
+  const UpCoef k = unipc_coef(coef);
+  const UpPlan f = unipc_plan(k, order);
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et);
+  f32x4 *o4 = reinterpret_cast<f32x4*>(out), *l4 = reinterpret_cast<f32x4*>(last), *p0 = reinterpret_cast<f32x4*>(hist),
+        *p1 = reinterpret_cast<f32x4*>(hist + n), *p2 = reinterpret_cast<f32x4*>(hist + 2 * n);   // (p1, p2: used below `order` only)
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (long i = gid; i < nv; i += stride) {
+    const f32x4 xv = x4[i], uv = u4[i];
+    f32x4 tv = uv, Lv = zero, h1 = zero, h2 = zero, h3 = zero, ov, cv, mv;
+    if (CFG) tv = t4[i];
+    if (f.cL) Lv = l4[i];
+    if (f.rd1) h1 = p0[i];
+    if (f.rd2) h2 = p1[i];
+    if (f.rd3) h3 = p2[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float o, xc, mt;
+      unipc_elem(k, f, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], Lv[j], h1[j], h2[j], h3[j], o, xc, mt);
+      ov[j] = o, cv[j] = xc, mv[j] = mt;
+    }
+    o4[i] = ov;
+    l4[i] = cv;
+    if (order >= 3) p2[i] = h2;
+    if (order >= 2) p1[i] = h1;
+    p0[i] = mv;
+  }
+  for (long i = 4 * nv + gid; i < n; i += stride) {
+    const float u = eu[i];
+    unipc_at(k, f, order, x, last, hist, n, out, i, CFG ? cfg_mix(u, et[i], gs) : u);
+  }
+}
+
+// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the step in the last pass
+template <bool RESIDENT>
+__global__ __launch_bounds__(CRA_THREADS) void unipc_rescale_kernel(const float* x, const float* __restrict__ eu,
+                                                                    const float* __restrict__ et, float* last, float* hist, int order,
+                                                                    float* out, const float* __restrict__ coef, float gs, float gr, long n,
+                                                                    long plane) {
+  __shared__ float part[2][CRA_THREADS / 64];
+  const long base = (long)blockIdx.x * n;
+  x += base, eu += base, et += base, last += base, hist += base, out += base;
+  const UpCoef k = unipc_coef(coef);
+  const UpPlan f = unipc_plan(k, order);
+  const int tid = threadIdx.x;
+  constexpr int R = RESIDENT ? CRA_RES : 1;
+  float cv[R];
+  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = tid + j * CRA_THREADS;
+      if (i < n) unipc_at(k, f, order, x, last, hist, plane, out, i, cv[j] * scale);
+    }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS) unipc_at(k, f, order, x, last, hist, plane, out, i, cfg_mix(eu[i], et[i], gs) * scale);
+  }
+}
+
+int launch_unipc_update(const float* x, const float* eu, const float* et, float* last, float* hist, int order, float* out,
+                        const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  if (batch <= 0 || per_sample < 1 || order < 1 || order > 3) return SD_ERR_INVALID;
+  const long n = (long)batch * per_sample;
+  if (et && gr > 0.0f) {
+    if (per_sample < 2) return SD_ERR_INVALID;
+    if (per_sample <= (long)CRA_THREADS * CRA_RES)
+      hipLaunchKernelGGL(unipc_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, last, hist, order, out,
+                         coef, gs, gr, per_sample, n);
+    else
+      hipLaunchKernelGGL(unipc_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, last, hist, order, out,
+                         coef, gs, gr, per_sample, n);
+    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  }
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)last | (uintptr_t)hist | (uintptr_t)out;
+  const long nv = ((bits & 15) || (order > 1 && (n & 3))) ? 0 : n / 4;   // (the planes are n elements apart)
+  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
+  long nb = (work + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  if (et)
+    hipLaunchKernelGGL(unipc_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, last, hist, order, out, coef, gs, nv, n);
+  else
+    hipLaunchKernelGGL(unipc_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, last, hist, order, out, coef, gs, nv, n);
+  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+}
+
 // additive attention bias of a keep-mask: (1 - mask) * -10000 (unet_2d_condition.py:921-927, 1-D masks of 1 = attend, 0 = mask out)
 __global__ void mask_to_bias_kernel(const float* __restrict__ mask, float* __restrict__ bias, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) bias[i] = (1.0f - mask[i]) * -10000.0f;

@@ -387,6 +387,41 @@ def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     return out, m_out
 
 
+def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
+                 guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),
+    last: contiguous fp32 [B, ...] of one shape; hist: contiguous fp32 [order, B, ...], order 1-3, plane 0 the newest converted model
+    output; coef: fp32 GPU, 16-byte aligned (p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr) of
+    ``UniPCMultistepScheduler.unipc_coefficients``. With e the guided (and rescaled) model output, L = last, h_k = hist[k - 1]:
+    m_t = p x + q e, x_c = Ac L + Bc h1 + C2 (h2 - h1) + C3 (h3 - h1) + Ct (m_t - h1) (corr == 0: x_c = x),
+    out = Ap x_c + Bp m_t + D1 (h1 - m_t) + D2 (h2 - m_t); then last = x_c and hist = [m_t, h1, h2][:order]. A term with a zero
+    coefficient does not read its operand. out may be x."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
+        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
+    rescale = eps_text is not None and guidance_rescale > 0.0
+    if rescale and x.numel() // x.shape[0] < 2:
+        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
+    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (last, "last"), (out, "out")):
+        if t is None and name in ("eps_text", "out"):
+            continue
+        _flat_f32(t, name, x.numel())
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] not in (1, 2, 3) or hist.shape[1:] != x.shape:
+        raise ValueError(f"hist: expected [order, {', '.join(map(str, x.shape))}] with order 1-3")
+    _flat_f32(hist, "hist")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 12 or \
+            not coef.is_contiguous() or coef.data_ptr() % 16:
+        raise ValueError("coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients")
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_unipc_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), last.data_ptr(), hist.data_ptr(),
+                                     hist.shape[0], out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale),
+                                     x.shape[0], x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

@@ -92,6 +92,23 @@ class _MultistepTail(_FusedTail):
                                                    lat.numel() // lat.shape[0], stream)
 
 
+class _UniPCTail(_FusedTail):
+    """``unipc_coefficients`` (UniPC): convert_model_output, the corrector, the predictor, last_sample and the history shift ride in
+    the same launch; the 12 coefficients = row i - first of a table [steps, 12] over the steps the loop RUNS. The tail owns ``last``
+    and the ``order`` planes of ``hist``; the first row forms no term that reads them, so fresh ones are not initialised"""
+
+    def __init__(self, lib, emulated, coef, order):
+        super().__init__(lib, emulated, coef)
+        self.order, self.last = order, None
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:
+            self.history, self.last, self.first = lat.new_empty((self.order,) + tuple(lat.shape)), torch.empty_like(lat), i
+        return self.lib.mi355x_sd_unipc_update(lat.data_ptr(), eps, eps_text, self.last.data_ptr(), self.history.data_ptr(), self.order,
+                                               out.data_ptr(), self.coef.data_ptr() + 48 * (i - self.first), gs, gr, lat.shape[0],
+                                               lat.numel() // lat.shape[0], stream)
+
+
 class _VaeSwitches:
     """``enable_vae_tiling`` / ``enable_vae_slicing`` of the reference's pipelines (pipeline_stable_diffusion.py enable_vae_slicing /
     enable_vae_tiling and their disable_ twins): forwarded to the ``vae`` the pipeline owns."""
@@ -167,18 +184,23 @@ class StableDiffusionDenoiser(_VaeSwitches):
     def _fused_plan(self, rescale: bool, device, timesteps=None):
         """The fused step tail, when the scheduler's step is an update the library runs in one launch; None -> the generic path.
         The library always has every entry (its ABI version is checked at load); a test backend from before one keeps that path."""
-        sch, multistep = self.scheduler, hasattr(self.scheduler, "multistep_coefficients")
+        sch = self.scheduler
+        unipc, multistep = hasattr(sch, "unipc_coefficients"), hasattr(sch, "multistep_coefficients")
+        stateful = unipc or multistep   # the row depends on the steps before it: the walk covers the timesteps the loop RUNS
         lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
-        entry = "mi355x_sd_multistep_update" if multistep else "mi355x_sd_cfg_rescale_axpby" if rescale else None
-        if lib is None or not (multistep or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
+        entry = "mi355x_sd_unipc_update" if unipc else "mi355x_sd_multistep_update" if multistep else \
+            "mi355x_sd_cfg_rescale_axpby" if rescale else None
+        if lib is None or not (stateful or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
             return None
+        unipc_state = ("_step_index", "lower_order_nums", "model_outputs", "timestep_list", "last_sample", "this_order")
+        saved = {k: (list(v) if isinstance(v, list) else v) for k, v in ((k, getattr(sch, k)) for k in unipc_state)} if unipc else {}
         try:
             scales, coefs = [], []
-            walk = sch.multistep_coefficients if multistep else sch.step_coefficients
-            for t in (timesteps if multistep else sch.timesteps):
-                if not multistep:
+            walk = sch.unipc_coefficients if unipc else sch.multistep_coefficients if multistep else sch.step_coefficients
+            for t in (timesteps if stateful else sch.timesteps):
+                if not stateful:
                     scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
-                coefs.append(tuple(float(v) for v in walk(t)))   # Euler, DPM-Solver: advances the step index
+                coefs.append(tuple(float(v) for v in walk(t)))   # Euler, DPM-Solver, UniPC: advances the step index
         except NotImplementedError:
             return None
         finally:   # the walk advanced the scheduler's step state: as set_timesteps left it
@@ -186,7 +208,11 @@ class StableDiffusionDenoiser(_VaeSwitches):
                 sch._step_index = None
             if multistep:
                 sch.lower_order_nums, sch.model_outputs = 0, [None] * sch.config.solver_order
+            for k, v in saved.items():
+                setattr(sch, k, v)
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
+        if unipc:
+            return _UniPCTail(lib, emulated, coef, sch.config.solver_order)
         return _MultistepTail(lib, emulated, coef) if multistep else _LinearTail(lib, emulated, coef, scales)
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):

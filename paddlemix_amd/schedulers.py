@@ -8,6 +8,7 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
   PNDMScheduler                      scheduling_pndm.py:69 (set_timesteps :178-235, step_prk :260-320, step_plms :322-395)
   DPMSolverMultistepScheduler        scheduling_dpmsolver_multistep.py:66 (deterministic variants, orders 1-2; step :802-878)
   LCMScheduler                       scheduling_lcm.py:140 (set_timesteps :330-466, step :476-566) -- 2-8 step latent-consistency sampling
+  UniPCMultistepScheduler            scheduling_unipc_multistep.py:31 (predictor :438-565, corrector :567-701, step :720-804), orders 1-3
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
@@ -16,6 +17,8 @@ returns (a, b) -- DDIM and Euler, epsilon and v prediction -- so the latent upda
 The DPM-Solver multistep update is linear in two tensors, the sample and the previous step's converted model output:
 ``DPMSolverMultistepScheduler.multistep_coefficients`` returns (p, q, A, B, D) with  m0 = p*sample + q*model_output ,
 prev = A*sample + B*m0 + D*(m0 - m1)  for the library's ``mi355x_sd_multistep_update``.
+The UniPC step -- corrector, then predictor -- is linear in the sample, the model output, ``last_sample`` and up to three history
+entries: ``UniPCMultistepScheduler.unipc_coefficients`` returns its 12 scalars for the library's ``mi355x_sd_unipc_update``.
 """
 from __future__ import annotations
 
@@ -582,6 +585,269 @@ class DPMSolverMultistepScheduler:
         while a.dim() < original_samples.dim():
             a = a.unsqueeze(-1)
         return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+_WALKED = object()   # UniPCMultistepScheduler.last_sample after unipc_coefficients: "a predictor has run", without its tensor
+
+
+class UniPCMultistepScheduler:
+    """UniPC (scheduling_unipc_multistep.py:31-846): a B(h) predictor of order 1-3 (``multistep_uni_p_bh_update``) whose output the
+    next step corrects with the model output it was evaluated at (``multistep_uni_c_bh_update``), usable at 8-15 steps. Implemented:
+    ``solver_order`` 1-3, "bh1" / "bh2" ("midpoint" / "heun" / "logrho" become "bh2"), ``predict_x0``, epsilon / sample / v_prediction,
+    ``lower_order_final``, ``disable_corrector``, Karras sigmas, the three spacings. Not implemented (NotImplementedError):
+    thresholding, ``solver_p``, ``trained_betas``.
+    Both halves are linear in the tensors with scalars of the schedule alone: ``unipc_coefficients`` returns them as one row for the
+    library's ``mi355x_sd_unipc_update``."""
+    order = 1
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", trained_betas=None, solver_order: int = 2, prediction_type: str = "epsilon",
+                 thresholding: bool = False, dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0,
+                 predict_x0: bool = True, solver_type: str = "bh2", lower_order_final: bool = True, disable_corrector=(),
+                 solver_p=None, use_karras_sigmas: bool = False, timestep_spacing: str = "linspace", steps_offset: int = 0):
+        disable_corrector = list(disable_corrector)
+        if solver_type not in ("bh1", "bh2"):
+            if solver_type not in ("midpoint", "heun", "logrho"):
+                raise NotImplementedError(f"{solver_type} is not implemented for {self.__class__}")
+            solver_type = "bh2"
+        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        if thresholding or solver_p is not None or trained_betas is not None or solver_order not in (1, 2, 3):
+            raise NotImplementedError("UniPCMultistepScheduler(mi355x): thresholding, solver_p, trained_betas and solver_order "
+                                      "outside 1-3 are not implemented")
+        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
+        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
+        self.init_noise_sigma = 1.0
+        self.predict_x0, self.disable_corrector, self.solver_p = predict_x0, disable_corrector, None
+        self.num_inference_steps = None
+        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy().astype(np.int64)
+        self.model_outputs = [None] * solver_order
+        self.timestep_list = [None] * solver_order
+        self.lower_order_nums = 0
+        self.last_sample = None
+        self.this_order = None
+        self._step_index = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: int):
+        c, n, T = self.config, num_inference_steps, self.config.num_train_timesteps
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64) - 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        sigmas = np.array(((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5)
+        if c.use_karras_sigmas:
+            log_sigmas = np.log(sigmas)
+            s = np.flip(sigmas).copy()
+            rho, ramp = 7.0, np.linspace(0, 1, n)
+            lo, hi = s[-1].item() ** (1 / rho), s[0].item() ** (1 / rho)
+            s = (hi + ramp * (lo - hi)) ** rho
+            ts = np.array([EulerDiscreteScheduler._sigma_to_t(x, log_sigmas) for x in s]).round()
+            sigmas = np.concatenate([s, s[-1:]]).astype(np.float32)
+        else:
+            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+            sigma_last = ((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5
+            sigmas = np.concatenate([sigmas, [sigma_last]]).astype(np.float32)
+        self.sigmas, self.timesteps = sigmas, ts.astype(np.int64)
+        self.num_inference_steps = len(ts)
+        self.model_outputs = [None] * c.solver_order
+        self.lower_order_nums = 0
+        self.last_sample = None
+        self._step_index = None
+
+    def scale_model_input(self, sample, *args, **kwargs):
+        return sample
+
+    _sigma_to_alpha_sigma_t = staticmethod(DPMSolverMultistepScheduler._sigma_to_alpha_sigma_t)
+
+    def _convert_pq(self):
+        """(p, q) with convert_model_output = p * sample + q * model_output, from this step's float32 alpha_t and sigma_t"""
+        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[self._step_index]))
+        pt = self.config.prediction_type
+        if pt not in ("epsilon", "sample", "v_prediction"):
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction` for the "
+                             "UniPCMultistepScheduler.")
+        if self.predict_x0:
+            return (1.0 / a, -s / a) if pt == "epsilon" else (0.0, 1.0) if pt == "sample" else (a, -s)
+        return (0.0, 1.0) if pt == "epsilon" else (1.0 / s, -a / s) if pt == "sample" else (s, a)
+
+    def convert_model_output(self, model_output, *args, sample=None, **kwargs):
+        """model output -> x0 prediction (predict_x0) or epsilon prediction, :368-436"""
+        if sample is None:
+            if len(args) < 2:
+                raise ValueError("missing `sample` as a required keyward argument")
+            sample = args[1]
+        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[self._step_index]))
+        pt = self.config.prediction_type
+        self._convert_pq()   # (the prediction_type check)
+        if self.predict_x0:
+            return (sample - s * model_output) / a if pt == "epsilon" else model_output if pt == "sample" else a * sample - s * model_output
+        return model_output if pt == "epsilon" else (sample - a * model_output) / s if pt == "sample" else a * model_output + s * sample
+
+    def _bh_scalars(self, i_t: int, i_s0: int, older, order: int, corrector: bool):
+        """The float32 scalars of one B(h) update from sigma index i_s0 to i_t (:490-546 / :625-683), ``older`` the sigma indices of
+        the history entries behind m0 -> (A, B, G, rks, rhos):  x_t = A x - B m0 - G (sum_k rhos[k] (m_k - m0) / rks[k] [+ rhos[-1]
+        (m_t - m0)]). The predictor solves for ``order - 1`` rhos (0.5 at order 2), the corrector for ``order`` (0.5 at order 1), in
+        float32 like the reference's linalg.solve. A repeated sigma (h = 0) gives what the reference gets: inf and nan."""
+        f32 = np.float32
+        with np.errstate(divide="ignore", invalid="ignore"):
+            at, st = self._sigma_to_alpha_sigma_t(self.sigmas[i_t])
+            a0, s0 = self._sigma_to_alpha_sigma_t(self.sigmas[i_s0])
+            l0 = np.log(a0) - np.log(s0)
+            h = (np.log(at) - np.log(st)) - l0
+            rks = []
+            for si in older:
+                ai, s_i = self._sigma_to_alpha_sigma_t(self.sigmas[si])
+                rks.append(((np.log(ai) - np.log(s_i)) - l0) / h)
+            rk_all = np.array(rks + [1.0], dtype=np.float32)
+            hh = -h if self.predict_x0 else h
+            h_phi_1 = np.expm1(hh)
+            h_phi_k = h_phi_1 / hh - f32(1)
+            B_h = hh if self.config.solver_type == "bh1" else np.expm1(hh)
+            R, b, factorial_i = [], [], 1
+            for i in range(1, order + 1):
+                R.append(rk_all ** (i - 1))
+                b.append(h_phi_k * f32(factorial_i) / B_h)
+                factorial_i *= i + 1
+                h_phi_k = h_phi_k / hh - f32(1 / factorial_i)
+            R, b = np.stack(R).astype(np.float32), np.array(b, dtype=np.float32)
+            if corrector:
+                rhos = np.array([0.5], dtype=np.float32) if order == 1 else self._solve(R, b)
+            else:
+                rhos = np.zeros(0, np.float32) if order == 1 else np.array([0.5], dtype=np.float32) if order == 2 else \
+                    self._solve(R[:-1, :-1], b[:-1])
+            if self.predict_x0:
+                return st / s0, at * h_phi_1, at * B_h, rks, rhos
+            return at / a0, st * h_phi_1, st * B_h, rks, rhos
+
+    @staticmethod
+    def _solve(R, b):
+        try:
+            return np.linalg.solve(R, b).astype(np.float32)   # float32 in, LAPACK's single-precision solve
+        except np.linalg.LinAlgError:
+            return np.full(len(b), np.nan, dtype=np.float32)
+
+    def _bh_update(self, x, m0, older_outputs, model_t, scalars):
+        A, B, G, rks, rhos = scalars
+        f = float
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res = 0
+            for k, (mk, rk) in enumerate(zip(older_outputs, rks)):
+                res = res + f(rhos[k]) * ((mk - m0) / f(rk))
+            if model_t is not None:
+                res = res + f(rhos[-1]) * (model_t - m0)
+        return f(A) * x - f(B) * m0 - f(G) * res
+
+    def multistep_uni_p_bh_update(self, model_output, *args, sample=None, order=None, **kwargs):
+        """UniP, the B(h) predictor (:438-565): ``sample`` at sigma index step_index -> step_index + 1"""
+        if sample is None or order is None:
+            raise ValueError(" missing `sample` / `order` as a required keyward argument")
+        i = self._step_index
+        sc = self._bh_scalars(i + 1, i, [i - k for k in range(1, order)], order, corrector=False)
+        return self._bh_update(sample, self.model_outputs[-1], [self.model_outputs[-(k + 1)] for k in range(1, order)], None, sc)
+
+    def multistep_uni_c_bh_update(self, this_model_output, *args, last_sample=None, this_sample=None, order=None, **kwargs):
+        """UniC, the B(h) corrector (:567-701): ``last_sample`` at sigma index step_index - 1 -> step_index, with the model output
+        converted at ``this_sample``"""
+        if last_sample is None or this_sample is None or order is None:
+            raise ValueError(" missing `last_sample` / `this_sample` / `order` as a required keyward argument")
+        i = self._step_index
+        sc = self._bh_scalars(i, i - 1, [i - (k + 1) for k in range(1, order)], order, corrector=True)
+        return self._bh_update(last_sample, self.model_outputs[-1], [self.model_outputs[-(k + 1)] for k in range(1, order)],
+                               this_model_output, sc)
+
+    def _init_step_index(self, timestep):
+        c = np.nonzero(self.timesteps == int(timestep))[0]
+        # "the sigma index that is taken for the **very** first `step` is always the second index": an img2img start on a
+        # duplicated timestep must not skip a sigma
+        self._step_index = len(self.timesteps) - 1 if len(c) == 0 else int(c[1] if len(c) > 1 else c[0])
+
+    def _use_corrector(self):
+        return self._step_index > 0 and self._step_index - 1 not in self.disable_corrector and self.last_sample is not None
+
+    def _next_order(self):
+        c = self.config
+        this_order = min(c.solver_order, len(self.timesteps) - self._step_index) if c.lower_order_final else c.solver_order
+        return min(this_order, self.lower_order_nums + 1)   # warm-up of the multistep history
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        m = self.convert_model_output(model_output, sample=sample)   # at the UNCORRECTED sample, as the reference does
+        if self._use_corrector():
+            sample = self.multistep_uni_c_bh_update(this_model_output=m, last_sample=self.last_sample, this_sample=sample,
+                                                    order=self.this_order)
+        self.model_outputs = self.model_outputs[1:] + [m]
+        self.timestep_list = self.timestep_list[1:] + [timestep]
+        self.this_order = self._next_order()
+        self.last_sample = sample
+        prev = self.multistep_uni_p_bh_update(model_output=model_output, sample=sample, order=self.this_order)
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
+        return _out(prev, return_dict)
+
+    def unipc_coefficients(self, timestep) -> Tuple[float, ...]:
+        """This step as a linear map of the sample x the loop holds, the model output e, ``last_sample`` L and the history h1, h2, h3 =
+        ``model_outputs[-1], [-2], [-3]`` before the step's shift -> (p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr):
+            m_t  = p x + q e
+            x_c  = Ac L + Bc h1 + C2 (h2 - h1) + C3 (h3 - h1) + Ct (m_t - h1)      corr == 1.0; corr == 0.0: x_c = x
+            prev = Ap x_c + Bp m_t + D1 (h1 - m_t) + D2 (h2 - m_t)
+        and afterwards last_sample = x_c, model_outputs = [.., h2, h1, m_t]. A term the step's order does not form has the
+        coefficient 0.0. Advances ``_step_index``, ``lower_order_nums``, ``this_order`` and marks ``last_sample`` as ``step`` does.
+        Every schedule value is the float32 numpy expression of ``step``; the row is composed from them in float64.
+        NotImplementedError when a coefficient is not finite (a third-order solve on a Karras schedule's repeated last sigma,
+        where ``step`` itself yields NaN)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        i, f = self._step_index, float
+        p, q = self._convert_pq()
+        row = [p, q] + [0.0] * 10
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if self._use_corrector():
+                o = self.this_order
+                A, B, G, rks, rhos = self._bh_scalars(i, i - 1, [i - (k + 1) for k in range(1, o)], o, corrector=True)
+                row[2], row[3], row[6], row[11] = f(A), -f(B), -f(G) * f(rhos[-1]), 1.0
+                for k, rk in enumerate(rks):
+                    row[4 + k] = -f(G) * f(rhos[k]) / f(rk)
+            self.this_order = o = self._next_order()
+            A, B, G, rks, rhos = self._bh_scalars(i + 1, i, [i - k for k in range(1, o)], o, corrector=False)
+            row[7], row[8] = f(A), -f(B)
+            for k, rk in enumerate(rks):
+                row[9 + k] = -f(G) * f(rhos[k]) / f(rk)
+        if self.last_sample is None:
+            self.last_sample = _WALKED
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
+        if not all(np.isfinite(v) for v in row):
+            raise NotImplementedError("a UniPC coefficient of this step is not finite")
+        return tuple(row)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """:822-843: alpha_t x + sigma_t noise with the sigma of each timestep's index in the CURRENT schedule"""
+        ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps)).astype(np.int64)
+        idx = [int(np.nonzero(self.timesteps == t)[0].item()) for t in ts]
+        alpha_t, sigma_t = self._sigma_to_alpha_sigma_t(np.asarray(self.sigmas, dtype=np.float32)[idx])
+        alpha_t = torch.as_tensor(alpha_t).to(original_samples.device, original_samples.dtype)
+        sigma_t = torch.as_tensor(sigma_t).to(original_samples.device, original_samples.dtype)
+        while alpha_t.dim() < original_samples.dim():
+            alpha_t, sigma_t = alpha_t.unsqueeze(-1), sigma_t.unsqueeze(-1)
+        return alpha_t * original_samples + sigma_t * noise
 
     def __len__(self):
         return self.config.num_train_timesteps
