@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 16
+#define MI355X_SD_ABI_VERSION 17
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -524,6 +524,32 @@ int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const fl
 int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float* eps_text, float* last, float* hist, int order,
                            float* out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
                            int64_t per_sample, void* stream);
+
+/* One step of ancestral sampling (EulerAncestralDiscreteScheduler, "Euler a": a deterministic move plus fresh noise every step) in one
+ * launch: guidance combine, guidance rescale and the update. `noise` is a plane of batch * per_sample fp32 values z ~ N(0, I) the
+ * caller draws once per step; the kernel draws nothing. Per element, with e the guided (and rescaled) model output as in
+ * mi355x_sd_multistep_update:
+ *   out = a*x + b*e
+ *   out = out + c*noise        only if c != 0
+ * Rules:
+ *  - coef is 3 fp32 values (a, b, c) in device memory, read by the kernel (EulerAncestralDiscreteScheduler.ancestral_coefficients):
+ *    a captured graph of one node replays a whole loop with only the row changing and the noise plane rewritten in place.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - c == 0.0 (the last row of every schedule, where sigma_up = 0) is a wave-uniform branch on the device value: noise is NOT
+ *    dereferenced, so a stale or NaN plane cannot reach the final latents. The entry cannot see a device value, so it accepts
+ *    noise == NULL; that is valid ONLY for a row the caller knows to have c == 0. A caller that replays one graph passes a real plane.
+ *  - operation order: as written above; which product contracts into which sum is the compiler's choice, as in
+ *    mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when every pointer is 16-byte aligned, and a scalar tail. No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap of out with x, eps_uncond, eps_text, noise or coef is MI355X_SD_ERR_INVALID
+ *    before any launch, as are a null x, eps_uncond, out or coef, batch <= 0, per_sample < 1, and per_sample < 2 with
+ *    guidance_rescale > 0. */
+int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* out,
+                               const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                               void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

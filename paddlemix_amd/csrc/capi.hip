@@ -655,6 +655,28 @@ int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float*
                                     rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
 }
 
+int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* out,
+                               const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                               void* stream) {
+  const char* who = "mi355x_sd_ancestral_update";
+  if (!x || !eps_uncond || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);   // (noise: see the header)
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / batch)
+    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
+                "per_sample - 1)", who);
+  // blocks write out while others still read the inputs: only the same-lane pair out = x may alias
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  auto overlaps = [&](const void* p, uintptr_t len) {
+    return p && (uintptr_t)out < (uintptr_t)p + len && (uintptr_t)p < (uintptr_t)out + bytes;
+  };
+  if (overlaps(eps_uncond, bytes) || overlaps(eps_text, bytes) || overlaps(noise, bytes) || overlaps(coef, 3 * sizeof(float)) ||
+      (out != x && overlaps(x, bytes)))
+    return fail(SD_ERR_INVALID, "%s: out may be x itself; it must not overlap x in any other way, nor eps_uncond, eps_text, noise or "
+                "coef", who);
+  return finish(launch_ancestral_update(x, eps_uncond, eps_text, noise, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
+                                        batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

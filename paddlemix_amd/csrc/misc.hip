@@ -1006,6 +1006,108 @@ int launch_unipc_update(const float* x, const float* eu, const float* et, float*
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
+// One step of ancestral sampling (EulerAncestralDiscreteScheduler: a deterministic move plus fresh noise) in one launch: the guidance
+// combine, the guidance rescale and prev = a x + b e + c z. With coef = (a, b, c) in device memory and z the noise plane the host
+// drew, per element and IN THIS ORDER (tests/ancestral_bounds.py derives its bound from it; which product fuses with which sum is the
+// compiler's choice, as in multistep_elem):
+//   e   = u                                      (et == nullptr)
+//       = fma(gs, t - u, u)                      (cfg_mix)
+//   e   = e * k                                  (rescale form only; k of cfg_rescale_factor)
+//   out = a * x + b * e
+//   out = out + c * z                            only if c != 0
+// c == 0 (the last row of every schedule: sigma_up = 0) is a uniform branch on the device value: noise is NOT read then, so a stale or
+// NaN plane cannot reach the final latents (0 * NaN), and a caller that knows the row may pass a null noise. x is read and out written
+// by the same lane at the same element, in the last pass only: out may be x.
+struct AnCoef {
+  float a, b, c;
+};
+
+__device__ __forceinline__ float ancestral_elem(const AnCoef& k, bool noisy, float x, float e, float z) {
+  float o = k.a * x + k.b * e;
+  if (noisy) o += k.c * z;
+  return o;
+}
+
+// gr == 0 (or no guidance): elementwise. nv 16-byte vectors first (0 when a pointer is not 16-byte aligned), then the elements
+// 4 * nv .. n - 1 one by one: nothing past n is read or written.
+template <bool CFG>
+__global__ void ancestral_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et,
+                                 const float* __restrict__ noise, float* out, const float* __restrict__ coef, float gs, long nv, long n) {
+  const AnCoef k = {coef[0], coef[1], coef[2]};
+  const bool noisy = k.c != 0.0f;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et),
+              *z4 = reinterpret_cast<const f32x4*>(noise);
+  f32x4* o4 = reinterpret_cast<f32x4*>(out);
+  for (long i = gid; i < nv; i += stride) {
+    const f32x4 xv = x4[i], uv = u4[i];
+    f32x4 tv = uv, zv = {0.f, 0.f, 0.f, 0.f}, ov;
+    if (CFG) tv = t4[i];
+    if (noisy) zv = z4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = ancestral_elem(k, noisy, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], zv[j]);
+    o4[i] = ov;
+  }
+  for (long i = 4 * nv + gid; i < n; i += stride) {
+    const float u = eu[i];
+    out[i] = ancestral_elem(k, noisy, x[i], CFG ? cfg_mix(u, et[i], gs) : u, noisy ? noise[i] : 0.f);
+  }
+}
+
+// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the update in the last pass
+template <bool RESIDENT>
+__global__ __launch_bounds__(CRA_THREADS) void ancestral_rescale_kernel(const float* x, const float* __restrict__ eu,
+                                                                        const float* __restrict__ et, const float* __restrict__ noise,
+                                                                        float* out, const float* __restrict__ coef, float gs, float gr,
+                                                                        long n) {
+  __shared__ float part[2][CRA_THREADS / 64];
+  const long base = (long)blockIdx.x * n;
+  x += base, eu += base, et += base, out += base;
+  const AnCoef k = {coef[0], coef[1], coef[2]};
+  const bool noisy = k.c != 0.0f;
+  if (noisy) noise += base;   // (never formed from a null pointer)
+  const int tid = threadIdx.x;
+  constexpr int R = RESIDENT ? CRA_RES : 1;
+  float cv[R];
+  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
+  if (RESIDENT) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int i = tid + j * CRA_THREADS;
+      if (i < n) out[i] = ancestral_elem(k, noisy, x[i], cv[j] * scale, noisy ? noise[i] : 0.f);
+    }
+  } else {
+    for (long i = tid; i < n; i += CRA_THREADS)
+      out[i] = ancestral_elem(k, noisy, x[i], cfg_mix(eu[i], et[i], gs) * scale, noisy ? noise[i] : 0.f);
+  }
+}
+
+int launch_ancestral_update(const float* x, const float* eu, const float* et, const float* noise, float* out, const float* coef,
+                            float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  if (batch <= 0 || per_sample < 1) return SD_ERR_INVALID;
+  if (et && gr > 0.0f) {
+    if (per_sample < 2) return SD_ERR_INVALID;
+    if (per_sample <= (long)CRA_THREADS * CRA_RES)
+      hipLaunchKernelGGL(ancestral_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, noise, out, coef,
+                         gs, gr, per_sample);
+    else
+      hipLaunchKernelGGL(ancestral_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, noise, out, coef,
+                         gs, gr, per_sample);
+    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  }
+  const long n = (long)batch * per_sample;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)noise | (uintptr_t)out;
+  const long nv = (bits & 15) ? 0 : n / 4;
+  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
+  long nb = (work + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  if (et)
+    hipLaunchKernelGGL(ancestral_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, noise, out, coef, gs, nv, n);
+  else
+    hipLaunchKernelGGL(ancestral_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, noise, out, coef, gs, nv, n);
+  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+}
+
 // additive attention bias of a keep-mask: (1 - mask) * -10000 (unet_2d_condition.py:921-927, 1-D masks of 1 = attend, 0 = mask out)
 __global__ void mask_to_bias_kernel(const float* __restrict__ mask, float* __restrict__ bias, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) bias[i] = (1.0f - mask[i]) * -10000.0f;

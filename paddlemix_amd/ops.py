@@ -387,6 +387,35 @@ def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     return out, m_out
 
 
+def ancestral_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise: Tensor, coef: Tensor, guidance_scale: float,
+                     guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One ancestral step ("Euler a") in one launch -> out. x, eps_uncond, eps_text (None: no guidance), noise: contiguous fp32
+    [B, ...] of one shape; coef: fp32 GPU (a, b, c) of ``EulerAncestralDiscreteScheduler.ancestral_coefficients``. With e the guided
+    (and, with guidance_rescale > 0, rescaled) model output: out = a x + b e + c noise; c == 0 does not read noise (the C entry takes a
+    null plane for such a row; this wrapper always wants a real one). out may be x."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
+        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
+    rescale = eps_text is not None and guidance_rescale > 0.0
+    if rescale and x.numel() // x.shape[0] < 2:
+        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
+    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (noise, "noise"), (out, "out")):
+        if t is None and name in ("eps_text", "out"):
+            continue
+        _flat_f32(t, name, x.numel())
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 3 or \
+            not coef.is_contiguous():
+        raise ValueError("coef: expected a contiguous fp32 GPU tensor (a, b, c)")
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_ancestral_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), noise.data_ptr(), out.data_ptr(),
+                                         coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
+                                         x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
                  guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
     """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),

@@ -109,6 +109,26 @@ class _UniPCTail(_FusedTail):
                                                lat.numel() // lat.shape[0], stream)
 
 
+class _AncestralTail(_FusedTail):
+    """``ancestral_coefficients`` (Euler a): prev = a * x + b * model_output + c * z, (a, b, c) = row i of a table [steps, 3] over the
+    scheduler's WHOLE schedule, ``scales`` as in _LinearTail. z is drawn here, once per step, by the ``torch.randn`` call of the
+    scheduler's ``step`` from the call's generator -- one seed gives the same noise on both paths -- and the launch reads it; the last
+    row has c = 0 and its plane is drawn (the generator advances as in ``step``) but not read"""
+
+    def __init__(self, lib, emulated, coef, scales, generator):
+        super().__init__(lib, emulated, coef, scales)
+        self.generator, self.noise = generator, None
+
+    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
+        self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32)
+        return super().update(latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale)
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        return self.lib.mi355x_sd_ancestral_update(lat.data_ptr(), eps, eps_text, self.noise.data_ptr(), out.data_ptr(),
+                                                   self.coef.data_ptr() + 12 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0],
+                                                   stream)
+
+
 class _VaeSwitches:
     """``enable_vae_tiling`` / ``enable_vae_slicing`` of the reference's pipelines (pipeline_stable_diffusion.py enable_vae_slicing /
     enable_vae_tiling and their disable_ twins): forwarded to the ``vae`` the pipeline owns."""
@@ -181,26 +201,28 @@ class StableDiffusionDenoiser(_VaeSwitches):
                              f"{cfg.projection_class_embeddings_input_dim}, but a vector of {passed} was created.")
         return torch.tensor([ids], dtype=torch.float32, device=device)
 
-    def _fused_plan(self, rescale: bool, device, timesteps=None):
+    def _fused_plan(self, rescale: bool, device, timesteps=None, generator=None):
         """The fused step tail, when the scheduler's step is an update the library runs in one launch; None -> the generic path.
         The library always has every entry (its ABI version is checked at load); a test backend from before one keeps that path."""
         sch = self.scheduler
         unipc, multistep = hasattr(sch, "unipc_coefficients"), hasattr(sch, "multistep_coefficients")
+        ancestral = hasattr(sch, "ancestral_coefficients")   # (a stateless row, like Euler's: the walk covers the WHOLE schedule)
         stateful = unipc or multistep   # the row depends on the steps before it: the walk covers the timesteps the loop RUNS
         lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
         entry = "mi355x_sd_unipc_update" if unipc else "mi355x_sd_multistep_update" if multistep else \
-            "mi355x_sd_cfg_rescale_axpby" if rescale else None
-        if lib is None or not (stateful or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
+            "mi355x_sd_ancestral_update" if ancestral else "mi355x_sd_cfg_rescale_axpby" if rescale else None
+        if lib is None or not (stateful or ancestral or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
             return None
         unipc_state = ("_step_index", "lower_order_nums", "model_outputs", "timestep_list", "last_sample", "this_order")
         saved = {k: (list(v) if isinstance(v, list) else v) for k, v in ((k, getattr(sch, k)) for k in unipc_state)} if unipc else {}
         try:
             scales, coefs = [], []
-            walk = sch.unipc_coefficients if unipc else sch.multistep_coefficients if multistep else sch.step_coefficients
+            walk = sch.unipc_coefficients if unipc else sch.multistep_coefficients if multistep else \
+                sch.ancestral_coefficients if ancestral else sch.step_coefficients
             for t in (timesteps if stateful else sch.timesteps):
                 if not stateful:
                     scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
-                coefs.append(tuple(float(v) for v in walk(t)))   # Euler, DPM-Solver, UniPC: advances the step index
+                coefs.append(tuple(float(v) for v in walk(t)))   # Euler (a), DPM-Solver, UniPC: advances the step index
         except NotImplementedError:
             return None
         finally:   # the walk advanced the scheduler's step state: as set_timesteps left it
@@ -213,6 +235,8 @@ class StableDiffusionDenoiser(_VaeSwitches):
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
         if unipc:
             return _UniPCTail(lib, emulated, coef, sch.config.solver_order)
+        if ancestral:
+            return _AncestralTail(lib, emulated, coef, scales, generator)
         return _MultistepTail(lib, emulated, coef) if multistep else _LinearTail(lib, emulated, coef, scales)
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
@@ -434,7 +458,7 @@ class StableDiffusionDenoiser(_VaeSwitches):
             w = torch.full((B,), float(guidance_scale) - 1.0, device=latents.device)
             unet_kw["timestep_cond"] = self.get_guidance_scale_embedding(w, embedding_dim=tc_dim)
         rescale = do_cfg and guidance_rescale > 0.0   # without CFG the reference applies no rescale (:886-888)
-        tail = (self._fused_plan(rescale, latents.device, timesteps) if fused_update and not eta else None) \
+        tail = (self._fused_plan(rescale, latents.device, timesteps, generator) if fused_update and not eta else None) \
             or _GenericTail(self.scheduler, extra)
         guidance = (do_cfg, guidance_scale, guidance_rescale if rescale else 0.0)
         nine = inp is not None and cfg.in_channels != latents.shape[1]

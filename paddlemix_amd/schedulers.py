@@ -9,6 +9,7 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
   DPMSolverMultistepScheduler        scheduling_dpmsolver_multistep.py:66 (deterministic variants, orders 1-2; step :802-878)
   LCMScheduler                       scheduling_lcm.py:140 (set_timesteps :330-466, step :476-566) -- 2-8 step latent-consistency sampling
   UniPCMultistepScheduler            scheduling_unipc_multistep.py:31 (predictor :438-565, corrector :567-701, step :720-804), orders 1-3
+  EulerAncestralDiscreteScheduler    scheduling_euler_ancestral_discrete.py:130 (set_timesteps :210-250, step :268-363) -- "Euler a"
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
@@ -19,6 +20,9 @@ The DPM-Solver multistep update is linear in two tensors, the sample and the pre
 prev = A*sample + B*m0 + D*(m0 - m1)  for the library's ``mi355x_sd_multistep_update``.
 The UniPC step -- corrector, then predictor -- is linear in the sample, the model output, ``last_sample`` and up to three history
 entries: ``UniPCMultistepScheduler.unipc_coefficients`` returns its 12 scalars for the library's ``mi355x_sd_unipc_update``.
+The ancestral Euler step is linear in the sample, the model output and the step's noise:
+``EulerAncestralDiscreteScheduler.ancestral_coefficients`` returns (a, b, c) with  prev = a*sample + b*model_output + c*noise  for the
+library's ``mi355x_sd_ancestral_update``; the noise stays a host draw (``torch.randn`` from the call's generator).
 """
 from __future__ import annotations
 
@@ -406,6 +410,128 @@ class EulerDiscreteScheduler:
         while sigma.dim() < original_samples.dim():
             sigma = sigma.unsqueeze(-1)
         return original_samples + noise * sigma
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class EulerAncestralDiscreteScheduler:
+    """"Euler a" (scheduling_euler_ancestral_discrete.py:130-389): an Euler step down to sigma_down and fresh noise of sigma_up back
+    up, every step. epsilon and v prediction, the three spacings; ``trained_betas`` is not implemented. The step is linear in the
+    sample, the model output and the noise: ``ancestral_coefficients`` returns (a, b, c) with  prev = a*sample + b*model_output +
+    c*noise  for the library's ``mi355x_sd_ancestral_update``."""
+    order = 1
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", trained_betas=None, prediction_type: str = "epsilon",
+                 timestep_spacing: str = "linspace", steps_offset: int = 0):
+        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        if trained_betas is not None:
+            raise NotImplementedError("EulerAncestralDiscreteScheduler(mi355x): trained_betas is not implemented")
+        # The training table in float32 TENSOR arithmetic, as the reference builds it (:141-161: linspace, cumprod and the sigmas are
+        # float32 tensor operations). _make_betas' float64 linspace rounded to float32 ends 9 float32 steps away at sigma_max, and an
+        # ancestral loop, whose every step divides by sigma^2, carries that into the latents (tests/golden/euler_ancestral/README.md)
+        if beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{beta_schedule} is not implemented")
+        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
+        self.alphas_cumprod = alphas_cumprod.numpy()
+        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
+        self.sigmas = np.concatenate([self._train_sigmas[::-1], [0.0]]).astype(np.float32)
+        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=float)[::-1].astype(np.float32)
+        self.num_inference_steps = None
+        self._step_index: Optional[int] = None
+
+    @property
+    def init_noise_sigma(self):
+        m = float(self.sigmas.max())
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return m
+        return (m ** 2 + 1) ** 0.5
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: int):
+        c, T = self.config, self.config.num_train_timesteps
+        self.num_inference_steps = n = num_inference_steps
+        if c.timestep_spacing == "linspace":   # (not rounded)
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        sig_all = np.array(self._train_sigmas)
+        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
+        self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
+        self.timesteps = ts.astype(np.float32)
+        self._step_index = None
+
+    _init_step_index = EulerDiscreteScheduler._init_step_index
+    scale_model_input = EulerDiscreteScheduler.scale_model_input
+    model_input_scale = EulerDiscreteScheduler.model_input_scale
+    add_noise = EulerDiscreteScheduler.add_noise
+
+    def _check(self, timestep):
+        pt = self.config.prediction_type
+        if pt == "sample":
+            raise NotImplementedError("prediction_type not implemented yet: sample")
+        if pt not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+
+    def _ancestral_sigmas(self):
+        """(sigma, sigma_up, dt) of this step in float32, the reference's own expressions (:339-347) on its float32 sigmas"""
+        s, s_to = self.sigmas[self._step_index], self.sigmas[self._step_index + 1]
+        s_up = np.sqrt(s_to * s_to * (s * s - s_to * s_to) / (s * s))
+        s_down = np.sqrt(s_to * s_to - s_up * s_up)
+        assert s_up.dtype == s_down.dtype == np.float32
+        return s, s_up, s_down - s
+
+    def ancestral_coefficients(self, timestep) -> Tuple[float, float, float]:
+        """(a, b, c) with prev = a*sample + b*model_output + c*noise, composed in float64 from the float32 sigma, sigma_up and dt of
+        ``step``; advances the index. c == 0.0 exactly on the last row (sigma_to = 0). A non-finite row: NotImplementedError."""
+        self._check(timestep)
+        s, c, dt = (float(v) for v in self._ancestral_sigmas())
+        self._step_index += 1
+        if self.config.prediction_type == "v_prediction":
+            # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+            a, b = 1.0 + dt * s / (s ** 2 + 1), dt / (s ** 2 + 1) ** 0.5
+        else:
+            a, b = 1.0, dt
+        if not all(np.isfinite(v) for v in (a, b, c)):
+            raise NotImplementedError("a non-finite row has no linear-update form")
+        return a, b, c
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, *, noise=None):
+        """-> prev_sample and pred_original_sample. ``noise`` (extension): this step's draw, otherwise ``torch.randn`` from
+        ``generator`` -- on every step, the last included (sigma_up = 0 there), as the reference draws."""
+        if isinstance(timestep, int) or (torch.is_tensor(timestep) and not timestep.is_floating_point()):
+            raise ValueError("Passing integer indices (e.g. from `enumerate(timesteps)`) as timesteps to `EulerDiscreteScheduler.step()` "
+                             "is not supported. Make sure to pass one of the `scheduler.timesteps` as a timestep.")
+        self._check(timestep)
+        s, s_up, dt = (float(v) for v in self._ancestral_sigmas())
+        if self.config.prediction_type == "epsilon":
+            x0 = sample - s * model_output
+        else:
+            x0 = model_output * (-s / (s ** 2 + 1) ** 0.5) + (sample / (s ** 2 + 1))
+        derivative = (sample - x0) / s
+        prev = sample + derivative * dt
+        if noise is None:
+            noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        prev = prev + noise * s_up
+        self._step_index += 1
+        return _out(prev, return_dict, pred_original_sample=x0)
 
     def __len__(self):
         return self.config.num_train_timesteps
