@@ -134,16 +134,16 @@ SIGNATURES = {
     "mi355x_sd_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355x_sd_mask_to_bias": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355x_sd_cfg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
-    # guidance rescale folded into the update (csrc/misc.hip, ABI 14)
+    # guidance rescale folded into the update (csrc/step_tail.hip, ABI 14)
     "mi355x_sd_cfg_rescale_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int64,
                                             c_void_p]),
-    # one DPM-Solver multistep step: guidance, rescale, convert_model_output, update and history (csrc/misc.hip, ABI 15)
+    # one DPM-Solver multistep step: guidance, rescale, convert_model_output, update and history (csrc/step_tail.hip, ABI 15)
     "mi355x_sd_multistep_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                            c_int, c_int64, c_void_p]),
-    # one UniPC step: guidance, rescale, convert_model_output, corrector, predictor, last_sample and history (csrc/misc.hip, ABI 16)
+    # one UniPC step: guidance, rescale, convert_model_output, corrector, predictor, last_sample and history (csrc/step_tail.hip, ABI 16)
     "mi355x_sd_unipc_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float,
                                        c_int, c_int64, c_void_p]),
-    # one ancestral step: guidance, rescale and prev = a x + b e + c noise (csrc/misc.hip, ABI 17)
+    # one ancestral step: guidance, rescale and prev = a x + b e + c noise (csrc/step_tail.hip, ABI 17)
     "mi355x_sd_ancestral_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int64,
                                            c_void_p]),
     # seam B1: the whole UNet behind a handle (csrc/unet_exec.hip)

@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -582,17 +584,48 @@ int mi355x_sd_cfg_axpby(const float* x, const float* eps_uncond, const float* ep
   return finish(launch_cfg_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, (long)n, S(stream)), "mi355x_sd_cfg_axpby");
 }
 
+// The argument rule of the step-tail entries (step_tail.hip). Blocks write their part of the `written` spans while other blocks still
+// read the inputs, so a written span must not overlap another one, nor anything read -- except a pair named in `same`, when the two
+// are one pointer: the same lane reads and then writes each element of such a pair. A null span (no guidance, no noise) overlaps
+// nothing. The range: batch > 0, per_sample >= min_per_sample, and batch * per_sample * planes * 4 bytes fit an int64_t (planes:
+// UniPC's history). `bytes` of the callers is meaningful only once the range has passed, and only then is it used.
+struct Span {
+  const void* p;
+  uintptr_t len;
+};
+struct SamePair {   // written[w] may be read[r] itself
+  int w, r;
+};
+static int check_step_args(const char* who, int batch, int64_t per_sample, int min_per_sample, int planes, const char* range_rule,
+                           std::initializer_list<Span> written, std::initializer_list<Span> read,
+                           std::initializer_list<SamePair> same, const char* overlap_rule) {
+  if (batch <= 0 || per_sample < min_per_sample || per_sample > INT64_MAX / 4 / planes / batch) return fail(SD_ERR_INVALID, range_rule, who);
+  auto overlaps = [](const Span& a, const Span& b) {
+    return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.len && (uintptr_t)b.p < (uintptr_t)a.p + a.len;
+  };
+  bool bad = false;
+  for (const Span* w = written.begin(); w != written.end(); ++w) {
+    for (const Span* v = w + 1; v != written.end(); ++v) bad = bad || overlaps(*w, *v);
+    for (const Span* r = read.begin(); r != read.end(); ++r) {
+      bool allowed = false;
+      for (const SamePair& s : same) allowed = allowed || (s.w == w - written.begin() && s.r == r - read.begin() && w->p == r->p);
+      bad = bad || (!allowed && overlaps(*w, *r));
+    }
+  }
+  return bad ? fail(SD_ERR_INVALID, overlap_rule, who) : SD_OK;
+}
+static const char* const STEP_RANGE_RULE =
+    "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by per_sample - 1)";
+
 int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
                                 float guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream) {
   const char* who = "mi355x_sd_cfg_rescale_axpby";
   if (!x || !eps_uncond || !eps_text || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  if (batch <= 0 || per_sample < 2 || per_sample > INT64_MAX / 4 / batch)
-    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 2 (the estimator divides by per_sample - 1)", who);
-  // the block of a sample reads eps_* in three passes and x in the last one while other blocks already write out
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4, o = (uintptr_t)out;
-  auto overlaps = [&](const float* p) { return o < (uintptr_t)p + bytes && (uintptr_t)p < o + bytes; };
-  if (overlaps(eps_uncond) || overlaps(eps_text) || (out != x && overlaps(x)))
-    return fail(SD_ERR_INVALID, "%s: out may be x itself, but must not overlap x in any other way, nor eps_uncond / eps_text", who);
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  if (int rc = check_step_args(who, batch, per_sample, 2, 1, "%s: needs batch > 0 and per_sample >= 2 (the estimator divides by per_sample - 1)",
+                               {{out, bytes}}, {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}}, {{0, 0}},
+                               "%s: out may be x itself, but must not overlap x in any other way, nor eps_uncond / eps_text"))
+    return rc;
   return finish(launch_cfg_rescale_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, guidance_rescale, batch, (long)per_sample,
                                          S(stream)), who);
 }
@@ -603,22 +636,13 @@ int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const fl
   const char* who = "mi355x_sd_multistep_update";
   if (!x || !eps_uncond || !m_prev || !out || !m_out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
   const bool rescale = eps_text && guidance_rescale > 0.0f;
-  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / batch)
-    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
-                "per_sample - 1)", who);
-  // blocks write out and m_out while others still read the inputs: only the same-lane pairs out = x and m_out = m_prev may alias
   const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  auto overlaps = [&](const void* w, const void* p, uintptr_t len) {
-    return p && (uintptr_t)w < (uintptr_t)p + len && (uintptr_t)p < (uintptr_t)w + bytes;
-  };
-  bool bad = overlaps(out, m_out, bytes);
-  for (const float* w : {(const float*)out, (const float*)m_out}) {
-    bad = bad || overlaps(w, eps_uncond, bytes) || overlaps(w, eps_text, bytes) || overlaps(w, coef, 5 * sizeof(float));
-    bad = bad || (!(w == out && out == x) && overlaps(w, x, bytes)) || (!(w == m_out && m_out == m_prev) && overlaps(w, m_prev, bytes));
-  }
-  if (bad)
-    return fail(SD_ERR_INVALID, "%s: out may be x itself and m_out may be m_prev itself; out and m_out must not overlap each other, "
-                "the inputs or coef in any other way", who);
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {m_out, bytes}},
+                               {{x, bytes}, {m_prev, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 5 * sizeof(float)}},
+                               {{0, 0}, {1, 1}},
+                               "%s: out may be x itself and m_out may be m_prev itself; out and m_out must not overlap each other, "
+                               "the inputs or coef in any other way"))
+    return rc;
   return finish(launch_multistep_update(x, eps_uncond, eps_text, m_prev, out, m_out, coef, guidance_scale,
                                         rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
 }
@@ -629,28 +653,15 @@ int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float*
   const char* who = "mi355x_sd_unipc_update";
   if (!x || !eps_uncond || !last || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
   if (order < 1 || order > 3) return fail(SD_ERR_INVALID, "%s: order must be 1, 2 or 3 (the planes of hist)", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / order / batch)
-    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
-                "per_sample - 1)", who);
   if ((uintptr_t)coef & 15) return fail(SD_ERR_INVALID, "%s: coef must be 16-byte aligned", who);
-  // blocks write out, last and hist while others still read the inputs: only the same-lane pair out = x may alias
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
   const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  struct Span {
-    const void* p;
-    uintptr_t len;
-  };
-  const Span written[3] = {{out, bytes}, {last, bytes}, {hist, bytes * (uintptr_t)order}};
-  const Span read[4] = {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 12 * sizeof(float)}};
-  auto overlaps = [](const Span& a, const Span& b) {
-    return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.len && (uintptr_t)b.p < (uintptr_t)a.p + a.len;
-  };
-  bool bad = overlaps(written[0], written[1]) || overlaps(written[0], written[2]) || overlaps(written[1], written[2]);
-  for (const Span& w : written)
-    for (const Span& r : read) bad = bad || (!(w.p == out && r.p == x && out == x) && overlaps(w, r));
-  if (bad)
-    return fail(SD_ERR_INVALID, "%s: out may be x itself; out, last and hist must not overlap each other, the inputs or coef in any "
-                "other way", who);
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, order, STEP_RANGE_RULE,
+                               {{out, bytes}, {last, bytes}, {hist, bytes * (uintptr_t)order}},
+                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 12 * sizeof(float)}}, {{0, 0}},
+                               "%s: out may be x itself; out, last and hist must not overlap each other, the inputs or coef in any "
+                               "other way"))
+    return rc;
   return finish(launch_unipc_update(x, eps_uncond, eps_text, last, hist, order, out, coef, guidance_scale,
                                     rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
 }
@@ -661,18 +672,12 @@ int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const fl
   const char* who = "mi355x_sd_ancestral_update";
   if (!x || !eps_uncond || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);   // (noise: see the header)
   const bool rescale = eps_text && guidance_rescale > 0.0f;
-  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / batch)
-    return fail(SD_ERR_INVALID, "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
-                "per_sample - 1)", who);
-  // blocks write out while others still read the inputs: only the same-lane pair out = x may alias
   const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  auto overlaps = [&](const void* p, uintptr_t len) {
-    return p && (uintptr_t)out < (uintptr_t)p + len && (uintptr_t)p < (uintptr_t)out + bytes;
-  };
-  if (overlaps(eps_uncond, bytes) || overlaps(eps_text, bytes) || overlaps(noise, bytes) || overlaps(coef, 3 * sizeof(float)) ||
-      (out != x && overlaps(x, bytes)))
-    return fail(SD_ERR_INVALID, "%s: out may be x itself; it must not overlap x in any other way, nor eps_uncond, eps_text, noise or "
-                "coef", who);
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}},
+                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {noise, bytes}, {coef, 3 * sizeof(float)}}, {{0, 0}},
+                               "%s: out may be x itself; it must not overlap x in any other way, nor eps_uncond, eps_text, noise or "
+                               "coef"))
+    return rc;
   return finish(launch_ancestral_update(x, eps_uncond, eps_text, noise, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
                                         batch, (long)per_sample, S(stream)), who);
 }

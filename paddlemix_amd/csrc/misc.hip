@@ -600,514 +600,6 @@ int launch_cfg_axpby(const float* x, const float* eu, const float* et, float* ou
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
-// The same pass with the guidance rescale folded in (rescale_noise_cfg, pipeline_stable_diffusion.py:69-80): per sample
-//   c = eu + gs * (et - eu),  r = std(et) / std(c) over the sample's n elements,  out = coef[0] * x + coef[1] * c * (gr * r + 1 - gr).
-// One block of 1024 threads per sample, no scratch. Each variance takes two passes (the mean, then the squared deviations from it; a
-// latent with an offset would cancel in sum(v^2) - n mean^2). Every sum is a fixed tree: a lane adds its elements tid, tid + 1024, ...
-// in that order, the 64 lanes of a wave fold by butterfly (wave_sum), the 16 wave partials go through LDS and fold by a second,
-// four-level butterfly -- no atomics, and every lane ends with the same bits. Nothing is added to a zero variance.
-// A block of 1024 threads has 128 registers per lane (16 waves on 4 SIMDs of 512), so a lane keeps CRA_RES = 32 values of et and 32 of
-// c in registers: samples of up to CRA_THREADS * CRA_RES = 32768 elements are read from memory once (RESIDENT); larger ones (the
-// 4 x 128 x 128 SDXL latent is 65536) read eu / et three times, the second and third time from L2 (<= 2 MB per step: latency, not
-// bandwidth). x is read and out written by the same lane in the last pass only, so out may be x.
-constexpr int CRA_THREADS = 1024, CRA_RES = 32;
-
-__device__ __forceinline__ float cfg_mix(float u, float t, float gs) { return fmaf(gs, t - u, u); }
-
-// a, b <- their sums over the block, in every lane; part: LDS [2][16]
-__device__ __forceinline__ void block_sum2(float& a, float& b, float (*part)[CRA_THREADS / 64]) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63;
-  __syncthreads();   // (the readers of the previous call are done with part)
-  if (lane == 0) {
-    part[0][threadIdx.x >> 6] = a;
-    part[1][threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  a = part[0][lane & 15];
-  b = part[1][lane & 15];
-  for (int o = 8; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-}
-
-// The statistics passes of a sample: k = gr * std(et) / std(c) + (1 - gr), the same bits in every lane. RESIDENT: cv[j] <- c of the
-// lane's element tid + j * CRA_THREADS (0 past n), kept for the caller's last pass.
-template <bool RESIDENT>
-__device__ __forceinline__ float cfg_rescale_factor(const float* __restrict__ eu, const float* __restrict__ et, float gs, float gr,
-                                                    long n, float (&cv)[RESIDENT ? CRA_RES : 1], float (*part)[CRA_THREADS / 64]) {
-  const int tid = threadIdx.x;
-  constexpr int R = RESIDENT ? CRA_RES : 1;
-  float tv[R];
-  float s_t = 0.f, s_c = 0.f;
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int i = tid + j * CRA_THREADS;
-      tv[j] = cv[j] = 0.f;
-      if (i < n) {
-        tv[j] = et[i];
-        cv[j] = cfg_mix(eu[i], tv[j], gs);
-        s_t += tv[j];
-        s_c += cv[j];
-      }
-    }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS) {
-      const float t = et[i];
-      s_t += t;
-      s_c += cfg_mix(eu[i], t, gs);
-    }
-  }
-  block_sum2(s_t, s_c, part);
-  const float inv_n = 1.0f / (float)n;
-  const float m_t = s_t * inv_n, m_c = s_c * inv_n;
-  float q_t = 0.f, q_c = 0.f;
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j)
-      if (tid + j * CRA_THREADS < n) {
-        const float dt = tv[j] - m_t, dc = cv[j] - m_c;
-        q_t += dt * dt;
-        q_c += dc * dc;
-      }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS) {
-      const float t = et[i];
-      const float dt = t - m_t, dc = cfg_mix(eu[i], t, gs) - m_c;
-      q_t += dt * dt;
-      q_c += dc * dc;
-    }
-  }
-  block_sum2(q_t, q_c, part);
-  const float inv_nm1 = 1.0f / (float)(n - 1);
-  const float r = sqrtf(q_t * inv_nm1) / sqrtf(q_c * inv_nm1);
-  return gr * r + (1.0f - gr);
-}
-
-template <bool RESIDENT>
-__global__ __launch_bounds__(CRA_THREADS) void cfg_rescale_axpby_kernel(const float* x, const float* __restrict__ eu,
-                                                                        const float* __restrict__ et, float* out,
-                                                                        const float* __restrict__ coef, float gs, float gr, long n) {
-  __shared__ float part[2][CRA_THREADS / 64];
-  const long base = (long)blockIdx.x * n;
-  x += base, eu += base, et += base, out += base;
-  const float a = coef[0], b = coef[1];
-  const int tid = threadIdx.x;
-  constexpr int R = RESIDENT ? CRA_RES : 1;
-  float cv[R];
-  const float k = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int i = tid + j * CRA_THREADS;
-      if (i < n) out[i] = a * x[i] + b * (cv[j] * k);
-    }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS) out[i] = a * x[i] + b * (cfg_mix(eu[i], et[i], gs) * k);
-  }
-}
-
-int launch_cfg_rescale_axpby(const float* x, const float* eu, const float* et, float* out, const float* coef, float gs, float gr,
-                             int batch, long per_sample, hipStream_t stream) {
-  if (batch <= 0 || per_sample < 2) return SD_ERR_INVALID;
-  if (per_sample <= (long)CRA_THREADS * CRA_RES)
-    hipLaunchKernelGGL(cfg_rescale_axpby_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, out, coef, gs,
-                       gr, per_sample);
-  else
-    hipLaunchKernelGGL(cfg_rescale_axpby_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, out, coef, gs,
-                       gr, per_sample);
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-}
-
-// One step of DPM-Solver multistep sampling (DPMSolverMultistepScheduler: dpmsolver++ / dpmsolver, orders 1 and 2) in one launch:
-// the guidance combine, the guidance rescale, convert_model_output, the multistep update and the history. With coef = (p, q, A, B, D)
-// in device memory, u = eu, t = et, m1 = m_prev, per element and IN THIS ORDER (tests/multistep_bounds.py derives its bound from it;
-// which product fuses with which sum is the compiler's choice):
-//   c   = fma(gs, t - u, u)                      (et == nullptr: c = u)
-//   e   = c * k                                  (rescale form only; k of cfg_rescale_factor)
-//   m0  = p * x + q * e                          -> m_out
-//   out = A * x + B * m0 + D * (m0 - m1)         the difference is formed first, as the reference forms it: D carries 1 / r, and
-//                                                (B + D) * m0 - D * m1 would cancel
-// D == 0 (a first-order step: the first one, solver_order 1, lower_order_final / euler_at_final) is a uniform branch on the device
-// value: m_prev is NOT read then -- a fresh loop's history is uninitialised, and 0 * NaN would poison the latents -- and
-// out = A * x + B * m0. x / out and m_prev / m_out are read and written by the same lane at the same element, in the last pass
-// only: out may be x and m_out may be m_prev (one history buffer).
-struct MsCoef {
-  float p, q, A, B, D;
-};
-
-__device__ __forceinline__ void multistep_elem(const MsCoef& k, bool second, float x, float e, float m1, float& o, float& m0) {
-  m0 = k.p * x + k.q * e;
-  o = k.A * x + k.B * m0;
-  if (second) o += k.D * (m0 - m1);
-}
-
-// gr == 0 (or no guidance): elementwise. nv 16-byte vectors first (0 when a pointer is not 16-byte aligned), then the elements
-// 4 * nv .. n - 1 one by one: nothing past n is read or written.
-template <bool CFG>
-__global__ void multistep_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et, const float* m_prev,
-                                 float* out, float* m_out, const float* __restrict__ coef, float gs, long nv, long n) {
-  const MsCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4]};
-  const bool second = k.D != 0.0f;
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et),
-              *p4 = reinterpret_cast<const f32x4*>(m_prev);
-  f32x4 *o4 = reinterpret_cast<f32x4*>(out), *m4 = reinterpret_cast<f32x4*>(m_out);
-  for (long i = gid; i < nv; i += stride) {
-    const f32x4 xv = x4[i], uv = u4[i];
-    f32x4 tv = uv, pv = {0.f, 0.f, 0.f, 0.f}, ov, mv;
-    if (CFG) tv = t4[i];
-    if (second) pv = p4[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float o, m0;
-      multistep_elem(k, second, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], pv[j], o, m0);
-      ov[j] = o, mv[j] = m0;
-    }
-    o4[i] = ov;
-    m4[i] = mv;
-  }
-  for (long i = 4 * nv + gid; i < n; i += stride) {
-    const float u = eu[i];
-    float o, m0;
-    multistep_elem(k, second, x[i], CFG ? cfg_mix(u, et[i], gs) : u, second ? m_prev[i] : 0.f, o, m0);
-    out[i] = o;
-    m_out[i] = m0;
-  }
-}
-
-// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the update in the last pass
-template <bool RESIDENT>
-__global__ __launch_bounds__(CRA_THREADS) void multistep_rescale_kernel(const float* x, const float* __restrict__ eu,
-                                                                        const float* __restrict__ et, const float* m_prev, float* out,
-                                                                        float* m_out, const float* __restrict__ coef, float gs, float gr,
-                                                                        long n) {
-  __shared__ float part[2][CRA_THREADS / 64];
-  const long base = (long)blockIdx.x * n;
-  x += base, eu += base, et += base, m_prev += base, out += base, m_out += base;
-  const MsCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4]};
-  const bool second = k.D != 0.0f;
-  const int tid = threadIdx.x;
-  constexpr int R = RESIDENT ? CRA_RES : 1;
-  float cv[R];
-  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int i = tid + j * CRA_THREADS;
-      if (i < n) {
-        float o, m0;
-        multistep_elem(k, second, x[i], cv[j] * scale, second ? m_prev[i] : 0.f, o, m0);
-        out[i] = o;
-        m_out[i] = m0;
-      }
-    }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS) {
-      float o, m0;
-      multistep_elem(k, second, x[i], cfg_mix(eu[i], et[i], gs) * scale, second ? m_prev[i] : 0.f, o, m0);
-      out[i] = o;
-      m_out[i] = m0;
-    }
-  }
-}
-
-int launch_multistep_update(const float* x, const float* eu, const float* et, const float* m_prev, float* out, float* m_out,
-                            const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
-  if (batch <= 0 || per_sample < 1) return SD_ERR_INVALID;
-  if (et && gr > 0.0f) {
-    if (per_sample < 2) return SD_ERR_INVALID;
-    if (per_sample <= (long)CRA_THREADS * CRA_RES)
-      hipLaunchKernelGGL(multistep_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, m_prev, out, m_out,
-                         coef, gs, gr, per_sample);
-    else
-      hipLaunchKernelGGL(multistep_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, m_prev, out,
-                         m_out, coef, gs, gr, per_sample);
-    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-  }
-  const long n = (long)batch * per_sample;
-  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)m_prev | (uintptr_t)out | (uintptr_t)m_out;
-  const long nv = (bits & 15) ? 0 : n / 4;
-  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
-  long nb = (work + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  if (et)
-    hipLaunchKernelGGL(multistep_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, m_prev, out, m_out, coef, gs, nv, n);
-  else
-    hipLaunchKernelGGL(multistep_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, m_prev, out, m_out, coef, gs, nv, n);
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-}
-
-// One step of UniPC sampling (UniPCMultistepScheduler: B(h) corrector then B(h) predictor, orders 1-3) in one launch: the guidance
-// combine, the guidance rescale, convert_model_output, the corrector, the predictor, last_sample and the history shift. With
-// coef = (p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr) in device memory (12 fp32, 16-byte aligned), L = last, h1 / h2 / h3 = the
-// history planes 0 / 1 / 2 BEFORE this step's shift (plane 0 newest), per element and IN THIS ORDER (tests/unipc_bounds.py derives
-// its bound from it; which product fuses with which sum is the compiler's choice, as in multistep_elem):
-//   e   = the guided (and rescaled) model output, as in the multistep kernels
-//   m_t = p * x + q * e                                                           convert_model_output on the UNCORRECTED x
-//   x_c = Ac * L + Bc * h1 + C2 * (h2 - h1) + C3 * (h3 - h1) + Ct * (m_t - h1)    corr != 0; corr == 0: x_c = x         -> last
-//   out = Ap * x_c + Bp * m_t + D1 * (h1 - m_t) + D2 * (h2 - m_t)
-//   plane[k] <- plane[k - 1] for k = order - 1 .. 1, plane[0] <- m_t
-// Every difference is formed first and then multiplied (C_k and D_k carry 1 / r_k: the regrouped form would cancel); the terms are
-// summed left to right as written. A term whose coefficient is 0.0 is not formed and its operand does not enter the arithmetic: L, each
-// plane inside a difference, the whole corrector at corr == 0 -- uniform branches on the device values (UpPlan), so the
-// uninitialised last / hist of a fresh loop or of an img2img start never reach out (0 * NaN). A plane a term needs is also never read
-// past `order`. The shift copies planes bit for bit whatever they hold. Every element of x / out, last and the planes is read and
-// then written by the same lane in the last pass only: out may be x, and all pointers stay fixed from step to step.
-struct UpCoef {
-  float p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr;
-};
-struct UpPlan {   // which terms are formed, which planes are read (for a term or as the shift's source)
-  bool corr, cL, cB, c2, c3, ct, d1, d2, rd1, rd2, rd3;
-};
-
-__device__ __forceinline__ UpCoef unipc_coef(const float* __restrict__ c) {
-  return {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11]};
-}
-
-__device__ __forceinline__ UpPlan unipc_plan(const UpCoef& k, int order) {
-  UpPlan f;
-  f.corr = k.corr != 0.0f;
-  f.cL = f.corr && k.Ac != 0.0f;
-  f.cB = f.corr && k.Bc != 0.0f;
-  f.c2 = f.corr && order >= 2 && k.C2 != 0.0f;
-  f.c3 = f.corr && order >= 3 && k.C3 != 0.0f;
-  f.ct = f.corr && k.Ct != 0.0f;
-  f.d1 = k.D1 != 0.0f;
-  f.d2 = order >= 2 && k.D2 != 0.0f;
-  f.rd1 = order >= 2 || f.cB || f.c2 || f.c3 || f.ct || f.d1;
-  f.rd2 = order >= 3 || f.c2 || f.d2;
-  f.rd3 = f.c3;
-  return f;
-}
-
-__device__ __forceinline__ void unipc_elem(const UpCoef& k, const UpPlan& f, float x, float e, float L, float h1, float h2, float h3,
-                                           float& o, float& xc, float& mt) {
-  mt = k.p * x + k.q * e;
-  xc = x;
-  if (f.corr) {
-    float a = 0.f;
-    if (f.cL) a = k.Ac * L;
-    if (f.cB) a += k.Bc * h1;
-    if (f.c2) a += k.C2 * (h2 - h1);
-    if (f.c3) a += k.C3 * (h3 - h1);
-    if (f.ct) a += k.Ct * (mt - h1);
-    xc = a;
-  }
-  o = k.Ap * xc + k.Bp * mt;
-  if (f.d1) o += k.D1 * (h1 - mt);
-  if (f.d2) o += k.D2 * (h2 - mt);
-}
-
-// element i of one step: x, last, hist (planes `plane` elements apart), out already offset to the sample or the batch
-__device__ __forceinline__ void unipc_at(const UpCoef& k, const UpPlan& f, int order, const float* x, float* last, float* hist,
-                                         long plane, float* out, long i, float e) {
-  const float h1 = f.rd1 ? hist[i] : 0.f, h2 = f.rd2 ? hist[plane + i] : 0.f, h3 = f.rd3 ? hist[2 * plane + i] : 0.f;
-  const float L = f.cL ? last[i] : 0.f;
-  float o, xc, mt;
-  unipc_elem(k, f, x[i], e, L, h1, h2, h3, o, xc, mt);
-  out[i] = o;
-  last[i] = xc;
-  if (order >= 3) hist[2 * plane + i] = h2;
-  if (order >= 2) hist[plane + i] = h1;
-  hist[i] = mt;
-}
-
-// gr == 0 (or no guidance): elementwise over the n = batch * per_sample elements (the planes are n apart). nv 16-byte vectors first
-// (0 when a pointer or a plane is not 16-byte aligned), then the elements 4 * nv .. n - 1 one by one: nothing past n is touched.
-template <bool CFG>
-__global__ void unipc_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et, float* last, float* hist,
-                             int order, float* out, const float* __restrict__ coef, float gs, long nv, long n) {
-  const UpCoef k = unipc_coef(coef);
-  const UpPlan f = unipc_plan(k, order);
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et);
-  f32x4 *o4 = reinterpret_cast<f32x4*>(out), *l4 = reinterpret_cast<f32x4*>(last), *p0 = reinterpret_cast<f32x4*>(hist),
-        *p1 = reinterpret_cast<f32x4*>(hist + n), *p2 = reinterpret_cast<f32x4*>(hist + 2 * n);   // (p1, p2: used below `order` only)
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  for (long i = gid; i < nv; i += stride) {
-    const f32x4 xv = x4[i], uv = u4[i];
-    f32x4 tv = uv, Lv = zero, h1 = zero, h2 = zero, h3 = zero, ov, cv, mv;
-    if (CFG) tv = t4[i];
-    if (f.cL) Lv = l4[i];
-    if (f.rd1) h1 = p0[i];
-    if (f.rd2) h2 = p1[i];
-    if (f.rd3) h3 = p2[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float o, xc, mt;
-      unipc_elem(k, f, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], Lv[j], h1[j], h2[j], h3[j], o, xc, mt);
-      ov[j] = o, cv[j] = xc, mv[j] = mt;
-    }
-    o4[i] = ov;
-    l4[i] = cv;
-    if (order >= 3) p2[i] = h2;
-    if (order >= 2) p1[i] = h1;
-    p0[i] = mv;
-  }
-  for (long i = 4 * nv + gid; i < n; i += stride) {
-    const float u = eu[i];
-    unipc_at(k, f, order, x, last, hist, n, out, i, CFG ? cfg_mix(u, et[i], gs) : u);
-  }
-}
-
-// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the step in the last pass
-template <bool RESIDENT>
-__global__ __launch_bounds__(CRA_THREADS) void unipc_rescale_kernel(const float* x, const float* __restrict__ eu,
-                                                                    const float* __restrict__ et, float* last, float* hist, int order,
-                                                                    float* out, const float* __restrict__ coef, float gs, float gr, long n,
-                                                                    long plane) {
-  __shared__ float part[2][CRA_THREADS / 64];
-  const long base = (long)blockIdx.x * n;
-  x += base, eu += base, et += base, last += base, hist += base, out += base;
-  const UpCoef k = unipc_coef(coef);
-  const UpPlan f = unipc_plan(k, order);
-  const int tid = threadIdx.x;
-  constexpr int R = RESIDENT ? CRA_RES : 1;
-  float cv[R];
-  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int i = tid + j * CRA_THREADS;
-      if (i < n) unipc_at(k, f, order, x, last, hist, plane, out, i, cv[j] * scale);
-    }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS) unipc_at(k, f, order, x, last, hist, plane, out, i, cfg_mix(eu[i], et[i], gs) * scale);
-  }
-}
-
-int launch_unipc_update(const float* x, const float* eu, const float* et, float* last, float* hist, int order, float* out,
-                        const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
-  if (batch <= 0 || per_sample < 1 || order < 1 || order > 3) return SD_ERR_INVALID;
-  const long n = (long)batch * per_sample;
-  if (et && gr > 0.0f) {
-    if (per_sample < 2) return SD_ERR_INVALID;
-    if (per_sample <= (long)CRA_THREADS * CRA_RES)
-      hipLaunchKernelGGL(unipc_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, last, hist, order, out,
-                         coef, gs, gr, per_sample, n);
-    else
-      hipLaunchKernelGGL(unipc_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, last, hist, order, out,
-                         coef, gs, gr, per_sample, n);
-    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-  }
-  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)last | (uintptr_t)hist | (uintptr_t)out;
-  const long nv = ((bits & 15) || (order > 1 && (n & 3))) ? 0 : n / 4;   // (the planes are n elements apart)
-  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
-  long nb = (work + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  if (et)
-    hipLaunchKernelGGL(unipc_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, last, hist, order, out, coef, gs, nv, n);
-  else
-    hipLaunchKernelGGL(unipc_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, last, hist, order, out, coef, gs, nv, n);
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-}
-
-// One step of ancestral sampling (EulerAncestralDiscreteScheduler: a deterministic move plus fresh noise) in one launch: the guidance
-// combine, the guidance rescale and prev = a x + b e + c z. With coef = (a, b, c) in device memory and z the noise plane the host
-// drew, per element and IN THIS ORDER (tests/ancestral_bounds.py derives its bound from it; which product fuses with which sum is the
-// compiler's choice, as in multistep_elem):
-//   e   = u                                      (et == nullptr)
-//       = fma(gs, t - u, u)                      (cfg_mix)
-//   e   = e * k                                  (rescale form only; k of cfg_rescale_factor)
-//   out = a * x + b * e
-//   out = out + c * z                            only if c != 0
-// c == 0 (the last row of every schedule: sigma_up = 0) is a uniform branch on the device value: noise is NOT read then, so a stale or
-// NaN plane cannot reach the final latents (0 * NaN), and a caller that knows the row may pass a null noise. x is read and out written
-// by the same lane at the same element, in the last pass only: out may be x.
-struct AnCoef {
-  float a, b, c;
-};
-
-__device__ __forceinline__ float ancestral_elem(const AnCoef& k, bool noisy, float x, float e, float z) {
-  float o = k.a * x + k.b * e;
-  if (noisy) o += k.c * z;
-  return o;
-}
-
-// gr == 0 (or no guidance): elementwise. nv 16-byte vectors first (0 when a pointer is not 16-byte aligned), then the elements
-// 4 * nv .. n - 1 one by one: nothing past n is read or written.
-template <bool CFG>
-__global__ void ancestral_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ et,
-                                 const float* __restrict__ noise, float* out, const float* __restrict__ coef, float gs, long nv, long n) {
-  const AnCoef k = {coef[0], coef[1], coef[2]};
-  const bool noisy = k.c != 0.0f;
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-  const f32x4 *x4 = reinterpret_cast<const f32x4*>(x), *u4 = reinterpret_cast<const f32x4*>(eu), *t4 = reinterpret_cast<const f32x4*>(et),
-              *z4 = reinterpret_cast<const f32x4*>(noise);
-  f32x4* o4 = reinterpret_cast<f32x4*>(out);
-  for (long i = gid; i < nv; i += stride) {
-    const f32x4 xv = x4[i], uv = u4[i];
-    f32x4 tv = uv, zv = {0.f, 0.f, 0.f, 0.f}, ov;
-    if (CFG) tv = t4[i];
-    if (noisy) zv = z4[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ov[j] = ancestral_elem(k, noisy, xv[j], CFG ? cfg_mix(uv[j], tv[j], gs) : uv[j], zv[j]);
-    o4[i] = ov;
-  }
-  for (long i = 4 * nv + gid; i < n; i += stride) {
-    const float u = eu[i];
-    out[i] = ancestral_elem(k, noisy, x[i], CFG ? cfg_mix(u, et[i], gs) : u, noisy ? noise[i] : 0.f);
-  }
-}
-
-// gr > 0: one block per sample, the statistics of cfg_rescale_axpby_kernel (cfg_rescale_factor), then the update in the last pass
-template <bool RESIDENT>
-__global__ __launch_bounds__(CRA_THREADS) void ancestral_rescale_kernel(const float* x, const float* __restrict__ eu,
-                                                                        const float* __restrict__ et, const float* __restrict__ noise,
-                                                                        float* out, const float* __restrict__ coef, float gs, float gr,
-                                                                        long n) {
-  __shared__ float part[2][CRA_THREADS / 64];
-  const long base = (long)blockIdx.x * n;
-  x += base, eu += base, et += base, out += base;
-  const AnCoef k = {coef[0], coef[1], coef[2]};
-  const bool noisy = k.c != 0.0f;
-  if (noisy) noise += base;   // (never formed from a null pointer)
-  const int tid = threadIdx.x;
-  constexpr int R = RESIDENT ? CRA_RES : 1;
-  float cv[R];
-  const float scale = cfg_rescale_factor<RESIDENT>(eu, et, gs, gr, n, cv, part);
-  if (RESIDENT) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int i = tid + j * CRA_THREADS;
-      if (i < n) out[i] = ancestral_elem(k, noisy, x[i], cv[j] * scale, noisy ? noise[i] : 0.f);
-    }
-  } else {
-    for (long i = tid; i < n; i += CRA_THREADS)
-      out[i] = ancestral_elem(k, noisy, x[i], cfg_mix(eu[i], et[i], gs) * scale, noisy ? noise[i] : 0.f);
-  }
-}
-
-int launch_ancestral_update(const float* x, const float* eu, const float* et, const float* noise, float* out, const float* coef,
-                            float gs, float gr, int batch, long per_sample, hipStream_t stream) {
-  if (batch <= 0 || per_sample < 1) return SD_ERR_INVALID;
-  if (et && gr > 0.0f) {
-    if (per_sample < 2) return SD_ERR_INVALID;
-    if (per_sample <= (long)CRA_THREADS * CRA_RES)
-      hipLaunchKernelGGL(ancestral_rescale_kernel<true>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, noise, out, coef,
-                         gs, gr, per_sample);
-    else
-      hipLaunchKernelGGL(ancestral_rescale_kernel<false>, dim3((unsigned)batch), dim3(CRA_THREADS), 0, stream, x, eu, et, noise, out, coef,
-                         gs, gr, per_sample);
-    return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-  }
-  const long n = (long)batch * per_sample;
-  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eu | (uintptr_t)et | (uintptr_t)noise | (uintptr_t)out;
-  const long nv = (bits & 15) ? 0 : n / 4;
-  const long work = nv > n - 4 * nv ? nv : n - 4 * nv;
-  long nb = (work + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  if (et)
-    hipLaunchKernelGGL(ancestral_kernel<true>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, noise, out, coef, gs, nv, n);
-  else
-    hipLaunchKernelGGL(ancestral_kernel<false>, dim3((unsigned)nb), dim3(256), 0, stream, x, eu, et, noise, out, coef, gs, nv, n);
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-}
-
 // additive attention bias of a keep-mask: (1 - mask) * -10000 (unet_2d_condition.py:921-927, 1-D masks of 1 = attend, 0 = mask out)
 __global__ void mask_to_bias_kernel(const float* __restrict__ mask, float* __restrict__ bias, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) bias[i] = (1.0f - mask[i]) * -10000.0f;

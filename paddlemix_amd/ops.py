@@ -330,6 +330,30 @@ def axpby(x: Tensor, y: Tensor, coef: Tensor, out: Optional[Tensor] = None) -> T
     return out
 
 
+def _step_args(x: Tensor, same_shape, coef: Tensor, width: int, coef_error: str, rescale: bool, always_rescale: bool = False,
+               coef_align: int = 1) -> None:
+    """The checks the step-tail wrappers share. x: contiguous fp32 GPU [B, ...], non-empty, with at least 2 elements per sample under
+    the guidance rescale; same_shape: (tensor, name, may_be_none) triples, each like x; coef: contiguous fp32 GPU with at least
+    `width` values at a multiple of coef_align bytes (coef_error: the form's own text)"""
+    _flat_f32(x, "x")
+    if always_rescale:
+        if x.dim() < 2 or x.shape[0] < 1 or x.numel() // x.shape[0] < 2:
+            raise ValueError(f"x: expected [B, ...] with at least 2 elements per sample, got {tuple(x.shape)}")
+    elif x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
+        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
+    elif rescale and x.numel() // x.shape[0] < 2:
+        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
+    for t, name, may_be_none in same_shape:
+        if t is None and may_be_none:
+            continue
+        _flat_f32(t, name, x.numel())
+        if t.shape != x.shape:
+            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < width or \
+            not coef.is_contiguous() or coef.data_ptr() % coef_align:
+        raise ValueError(coef_error)
+
+
 def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Tensor, guidance_scale: float,
                       guidance_rescale: float, out: Optional[Tensor] = None) -> Tensor:
     """Guidance combine, guidance rescale (``rescale_noise_cfg``) and the linear scheduler update in one launch. x, eps_uncond,
@@ -337,16 +361,8 @@ def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Ten
     (eps_text - eps_uncond) and r[s] = std(eps_text[s]) / std(c[s]) over everything but the batch axis,
     out = coef[0] * x + coef[1] * c * (guidance_rescale * r[s] + 1 - guidance_rescale). out may be x."""
     lib = _lib.load()
-    _flat_f32(x, "x")
-    if x.dim() < 2 or x.shape[0] < 1 or x.numel() // x.shape[0] < 2:
-        raise ValueError(f"x: expected [B, ...] with at least 2 elements per sample, got {tuple(x.shape)}")
-    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text")):
-        _flat_f32(t, name, x.numel())
-        if t.shape != x.shape:
-            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
-    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 2 or \
-            not coef.is_contiguous():
-        raise ValueError("coef: expected a contiguous fp32 GPU tensor (a, b)")
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", False)), coef, 2,
+               "coef: expected a contiguous fp32 GPU tensor (a, b)", True, always_rescale=True)
     if out is None:
         out = torch.empty_like(x)
     else:
@@ -364,21 +380,9 @@ def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     the guided (and, with guidance_rescale > 0, rescaled) model output: m_out = p x + q e, out = A x + B m_out + D (m_out - m_prev);
     D == 0 does not read m_prev. out may be x and m_out may be m_prev."""
     lib = _lib.load()
-    _flat_f32(x, "x")
-    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
-        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
-    rescale = eps_text is not None and guidance_rescale > 0.0
-    if rescale and x.numel() // x.shape[0] < 2:
-        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
-    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (m_prev, "m_prev"), (out, "out"), (m_out, "m_out")):
-        if t is None and name in ("eps_text", "out", "m_out"):
-            continue
-        _flat_f32(t, name, x.numel())
-        if t.shape != x.shape:
-            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
-    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 5 or \
-            not coef.is_contiguous():
-        raise ValueError("coef: expected a contiguous fp32 GPU tensor (p, q, A, B, D)")
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (m_prev, "m_prev", False), (out, "out", True),
+                   (m_out, "m_out", True)), coef, 5, "coef: expected a contiguous fp32 GPU tensor (p, q, A, B, D)",
+               eps_text is not None and guidance_rescale > 0.0)
     out = torch.empty_like(x) if out is None else out
     m_out = torch.empty_like(x) if m_out is None else m_out
     check(lib.mi355x_sd_multistep_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), m_prev.data_ptr(), out.data_ptr(),
@@ -394,21 +398,8 @@ def ancestral_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     (and, with guidance_rescale > 0, rescaled) model output: out = a x + b e + c noise; c == 0 does not read noise (the C entry takes a
     null plane for such a row; this wrapper always wants a real one). out may be x."""
     lib = _lib.load()
-    _flat_f32(x, "x")
-    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
-        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
-    rescale = eps_text is not None and guidance_rescale > 0.0
-    if rescale and x.numel() // x.shape[0] < 2:
-        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
-    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (noise, "noise"), (out, "out")):
-        if t is None and name in ("eps_text", "out"):
-            continue
-        _flat_f32(t, name, x.numel())
-        if t.shape != x.shape:
-            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
-    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 3 or \
-            not coef.is_contiguous():
-        raise ValueError("coef: expected a contiguous fp32 GPU tensor (a, b, c)")
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (noise, "noise", False), (out, "out", True)),
+               coef, 3, "coef: expected a contiguous fp32 GPU tensor (a, b, c)", eps_text is not None and guidance_rescale > 0.0)
     out = torch.empty_like(x) if out is None else out
     check(lib.mi355x_sd_ancestral_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), noise.data_ptr(), out.data_ptr(),
                                          coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
@@ -426,24 +417,12 @@ def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last
     out = Ap x_c + Bp m_t + D1 (h1 - m_t) + D2 (h2 - m_t); then last = x_c and hist = [m_t, h1, h2][:order]. A term with a zero
     coefficient does not read its operand. out may be x."""
     lib = _lib.load()
-    _flat_f32(x, "x")
-    if x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
-        raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
-    rescale = eps_text is not None and guidance_rescale > 0.0
-    if rescale and x.numel() // x.shape[0] < 2:
-        raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
-    for t, name in ((eps_uncond, "eps_uncond"), (eps_text, "eps_text"), (last, "last"), (out, "out")):
-        if t is None and name in ("eps_text", "out"):
-            continue
-        _flat_f32(t, name, x.numel())
-        if t.shape != x.shape:
-            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (last, "last", False), (out, "out", True)),
+               coef, 12, "coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients",
+               eps_text is not None and guidance_rescale > 0.0, coef_align=16)
     if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] not in (1, 2, 3) or hist.shape[1:] != x.shape:
         raise ValueError(f"hist: expected [order, {', '.join(map(str, x.shape))}] with order 1-3")
     _flat_f32(hist, "hist")
-    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < 12 or \
-            not coef.is_contiguous() or coef.data_ptr() % 16:
-        raise ValueError("coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients")
     out = torch.empty_like(x) if out is None else out
     check(lib.mi355x_sd_unipc_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), last.data_ptr(), hist.data_ptr(),
                                      hist.shape[0], out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale),

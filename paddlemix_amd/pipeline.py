@@ -11,6 +11,7 @@ stays outside: the loop starts from ``prompt_embeds``.
 """
 from __future__ import annotations
 
+from contextlib import nullcontext
 from typing import Callable, Dict, Optional
 
 import numpy as np
@@ -48,10 +49,21 @@ class _GenericTail:
 
 class _FusedTail:
     """Guidance combine (+ rescale) and scheduler update as ONE device pass over the latents on the caller's stream, coefficients in a
-    device table. Not through paddlemix_amd.ops: its wrappers refuse the emulator's host tensors and validate every call."""
+    device table. Not through paddlemix_amd.ops: its wrappers refuse the emulator's host tensors and validate every call.
+    A subclass is one row of _TAILS: it names the scheduler method whose rows it runs and the library entry it needs."""
+
+    walk = None              # the scheduler method that gives a step's coefficient row
+    whole_schedule = False   # a row depends on the steps before it: the walk covers the timesteps the loop RUNS. True: a stateless
+    #                          row, walked over the scheduler's WHOLE schedule together with its model_input_scale
+    entry = None             # the library entry every step needs (a test backend from before it keeps the generic path)
+    rescale_entry = None     # ... and the one it needs instead under the guidance rescale
 
     def __init__(self, lib, emulated, coef, scales=None):
         self.lib, self.emulated, self.coef, self.scales, self.history = lib, emulated, coef, scales, None
+
+    @classmethod
+    def build(cls, lib, emulated, coef, scales, scheduler, generator):
+        return cls(lib, emulated, coef, scales)
 
     def scale(self, x, i, t):
         return x if self.scales is None else x * self.scales[i]
@@ -69,6 +81,8 @@ class _LinearTail(_FusedTail):
     """``step_coefficients`` (DDIM at eta = 0, Euler; epsilon and v prediction): prev = a * x + b * model_output, (a, b) = row i of a
     table [steps, 2] over the scheduler's WHOLE schedule; ``scales``: that schedule's model-input scales"""
 
+    walk, whole_schedule, rescale_entry = "step_coefficients", True, "mi355x_sd_cfg_rescale_axpby"
+
     def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
         n, cp = lat.numel(), self.coef.data_ptr() + 8 * i
         if gr > 0.0:
@@ -82,6 +96,8 @@ class _LinearTail(_FusedTail):
 class _MultistepTail(_FusedTail):
     """``multistep_coefficients`` (DPM-Solver multistep): convert_model_output and the history shuffle ride in the same launch;
     (p, q, A, B, D) = row i - first of a table [steps, 5] over the steps the loop RUNS (img2img starts inside the schedule)"""
+
+    walk, entry = "multistep_coefficients", "mi355x_sd_multistep_update"
 
     def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
         if self.history is None:   # the previous step's converted model output, fp32; row 0 has D = 0: a fresh one is not read
@@ -97,9 +113,15 @@ class _UniPCTail(_FusedTail):
     the same launch; the 12 coefficients = row i - first of a table [steps, 12] over the steps the loop RUNS. The tail owns ``last``
     and the ``order`` planes of ``hist``; the first row forms no term that reads them, so fresh ones are not initialised"""
 
+    walk, entry = "unipc_coefficients", "mi355x_sd_unipc_update"
+
     def __init__(self, lib, emulated, coef, order):
         super().__init__(lib, emulated, coef)
         self.order, self.last = order, None
+
+    @classmethod
+    def build(cls, lib, emulated, coef, scales, scheduler, generator):
+        return cls(lib, emulated, coef, scheduler.config.solver_order)
 
     def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
         if self.history is None:
@@ -115,9 +137,15 @@ class _AncestralTail(_FusedTail):
     scheduler's ``step`` from the call's generator -- one seed gives the same noise on both paths -- and the launch reads it; the last
     row has c = 0 and its plane is drawn (the generator advances as in ``step``) but not read"""
 
+    walk, whole_schedule, entry = "ancestral_coefficients", True, "mi355x_sd_ancestral_update"
+
     def __init__(self, lib, emulated, coef, scales, generator):
         super().__init__(lib, emulated, coef, scales)
         self.generator, self.noise = generator, None
+
+    @classmethod
+    def build(cls, lib, emulated, coef, scales, scheduler, generator):
+        return cls(lib, emulated, coef, scales, generator)
 
     def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
         self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32)
@@ -127,6 +155,9 @@ class _AncestralTail(_FusedTail):
         return self.lib.mi355x_sd_ancestral_update(lat.data_ptr(), eps, eps_text, self.noise.data_ptr(), out.data_ptr(),
                                                    self.coef.data_ptr() + 12 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0],
                                                    stream)
+
+
+_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _LinearTail)   # in priority order: the first whose walk the scheduler has
 
 
 class _VaeSwitches:
@@ -205,39 +236,22 @@ class StableDiffusionDenoiser(_VaeSwitches):
         """The fused step tail, when the scheduler's step is an update the library runs in one launch; None -> the generic path.
         The library always has every entry (its ABI version is checked at load); a test backend from before one keeps that path."""
         sch = self.scheduler
-        unipc, multistep = hasattr(sch, "unipc_coefficients"), hasattr(sch, "multistep_coefficients")
-        ancestral = hasattr(sch, "ancestral_coefficients")   # (a stateless row, like Euler's: the walk covers the WHOLE schedule)
-        stateful = unipc or multistep   # the row depends on the steps before it: the walk covers the timesteps the loop RUNS
         lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
-        entry = "mi355x_sd_unipc_update" if unipc else "mi355x_sd_multistep_update" if multistep else \
-            "mi355x_sd_ancestral_update" if ancestral else "mi355x_sd_cfg_rescale_axpby" if rescale else None
-        if lib is None or not (stateful or ancestral or hasattr(sch, "step_coefficients")) or (emulated and entry and not hasattr(lib, entry)):
+        tail = next((c for c in _TAILS if hasattr(sch, c.walk)), None)
+        entry = tail and ((rescale and tail.rescale_entry) or tail.entry)
+        if lib is None or tail is None or (emulated and entry and not hasattr(lib, entry)):
             return None
-        unipc_state = ("_step_index", "lower_order_nums", "model_outputs", "timestep_list", "last_sample", "this_order")
-        saved = {k: (list(v) if isinstance(v, list) else v) for k, v in ((k, getattr(sch, k)) for k in unipc_state)} if unipc else {}
+        scales, coefs, walk = [] if tail.whole_schedule else None, [], getattr(sch, tail.walk)
         try:
-            scales, coefs = [], []
-            walk = sch.unipc_coefficients if unipc else sch.multistep_coefficients if multistep else \
-                sch.ancestral_coefficients if ancestral else sch.step_coefficients
-            for t in (timesteps if stateful else sch.timesteps):
-                if not stateful:
-                    scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
-                coefs.append(tuple(float(v) for v in walk(t)))   # Euler (a), DPM-Solver, UniPC: advances the step index
+            with getattr(sch, "coefficient_walk", nullcontext)():   # the walk advances the scheduler's step state: put back on exit
+                for t in (sch.timesteps if tail.whole_schedule else timesteps):
+                    if tail.whole_schedule:
+                        scales.append(float(sch.model_input_scale(t)) if hasattr(sch, "model_input_scale") else 1.0)
+                    coefs.append(tuple(float(v) for v in walk(t)))
         except NotImplementedError:
             return None
-        finally:   # the walk advanced the scheduler's step state: as set_timesteps left it
-            if hasattr(sch, "_step_index"):
-                sch._step_index = None
-            if multistep:
-                sch.lower_order_nums, sch.model_outputs = 0, [None] * sch.config.solver_order
-            for k, v in saved.items():
-                setattr(sch, k, v)
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
-        if unipc:
-            return _UniPCTail(lib, emulated, coef, sch.config.solver_order)
-        if ancestral:
-            return _AncestralTail(lib, emulated, coef, scales, generator)
-        return _MultistepTail(lib, emulated, coef) if multistep else _LinearTail(lib, emulated, coef, scales)
+        return tail.build(lib, emulated, coef, scales, sch, generator)
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
         """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1)."""

@@ -26,6 +26,7 @@ library's ``mi355x_sd_ancestral_update``; the noise stays a host draw (``torch.r
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from types import SimpleNamespace
 from typing import Optional, Tuple
 
@@ -45,6 +46,23 @@ def _out(prev, return_dict, **extra):
     if not return_dict:
         return (prev,)
     return SimpleNamespace(prev_sample=prev, **extra)
+
+
+def _coefficient_walk(*fields):
+    """-> the ``coefficient_walk`` method of a scheduler whose ``*_coefficients`` advance the step state in `fields` as ``step`` does:
+    ``with scheduler.coefficient_walk():`` puts that state back on exit, so a loop can tabulate its rows ahead of its steps. Lists are
+    copied one level deep (the walk replaces their entries, never mutates one); nothing else of the scheduler is copied."""
+
+    @contextmanager
+    def coefficient_walk(self):
+        saved = {k: (list(v) if isinstance(v, list) else v) for k, v in ((k, getattr(self, k)) for k in fields)}
+        try:
+            yield
+        finally:
+            for k, v in saved.items():
+                setattr(self, k, v)
+
+    return coefficient_walk
 
 
 class DDIMScheduler:
@@ -307,6 +325,8 @@ class EulerDiscreteScheduler:
     def step_index(self):
         return self._step_index
 
+    coefficient_walk = _coefficient_walk("_step_index")   # (step_coefficients, model_input_scale)
+
     def set_timesteps(self, num_inference_steps: int):
         c = self.config
         self.num_inference_steps = n = num_inference_steps
@@ -456,6 +476,8 @@ class EulerAncestralDiscreteScheduler:
     def step_index(self):
         return self._step_index
 
+    coefficient_walk = _coefficient_walk("_step_index")   # (ancestral_coefficients, model_input_scale)
+
     def set_timesteps(self, num_inference_steps: int):
         c, T = self.config, self.config.num_train_timesteps
         self.num_inference_steps = n = num_inference_steps
@@ -571,6 +593,8 @@ class DPMSolverMultistepScheduler:
     @property
     def step_index(self):
         return self._step_index
+
+    coefficient_walk = _coefficient_walk("_step_index", "lower_order_nums", "model_outputs")   # (multistep_coefficients)
 
     def set_timesteps(self, num_inference_steps: int):
         c, n = self.config, num_inference_steps
@@ -759,6 +783,9 @@ class UniPCMultistepScheduler:
     @property
     def step_index(self):
         return self._step_index
+
+    coefficient_walk = _coefficient_walk("_step_index", "lower_order_nums", "model_outputs", "timestep_list", "last_sample",
+                                         "this_order")   # (unipc_coefficients)
 
     def set_timesteps(self, num_inference_steps: int):
         c, n, T = self.config, num_inference_steps, self.config.num_train_timesteps
