@@ -38,9 +38,42 @@ gate, m // rows_per_batch, and added with the bias: its magnitude joins the bias
 gemm_epilogue.h epi4 rounds four times -- bias add, rowbias add (the batched form adds rowbias + fp32 residual first, then that sum:
 still one rounding per operand), residual add, scale; a bias that starts the accumulators (bias_acc) saves one -- so EPI_OPS = 4 holds
 and is not raised. An fp32 output (OUT_F32) is the epilogue value itself: u_out = 0 and the bound is e + 2^-24 |ref| (the reference
-is compared in float64; 2^-24 |ref| is the fp32 representation of the value). Split-K needs no constant: a slice chains K / (32 s)
-steps, the reduce kernel adds the s slices in order, K / (32 s) + s roundings in all, which stays below K / 32 for 2 <= s <= K / 256 --
-what plan_splitk guarantees (at least 4 K-tiles of 64 per slice, nt >= 8) -- so gamma_K covers it.
+is compared in float64; 2^-24 |ref| is the fp32 representation of the value). Split-K needs no constant: a slice of kc K-tiles chains 2 kc MFMA steps, the reduce
+kernel (splitk_reduce_kernel) adds the s slices in index order, 2 kc + s roundings on a product's way in all. plan_splitk slices a
+launch of at most 160 tiles of 128 x 128 with nt = ceil(K / 64) >= 8 K-tiles into 2 <= s <= nt / 4 slices of kc = ceil(nt / s) <=
+nt / s + 1 K-tiles (the last slice may be shorter): 2 kc + s <= 2 nt / s + 2 + s, which is convex in s and at both ends -- nt + 4 at
+s = 2, 10 + nt / 4 at s = nt / 4 -- at most 2 nt for nt >= 8. The unsliced chain has 2 nt steps (a ragged last K-tile adds exact
+zeros), so gamma_K covers every plan.
+
+A bias that starts the accumulators (GemmArgs::bias_acc: the pipelined loops of gemm_pipe.hip and the small tile of gemm_small.hip
+on 16-bit weights, no split-K, no LayerNorm fold) is no epilogue operand any more: it rides the whole chain, every partial sum is
+bounded by |bias| + S, and the accumulator term becomes gamma_K (S + |bias|). Callers whose launch may take that form pass
+bias_acc=True; the four-wave tile and the generic loop add the bias in the epilogue and leave it False.
+
+In-kernel e4m3 weights (the W8 instantiations of the generic loop, routes +f8): the fragments are widened exactly, acc = A . Q^T, and
+gemm_epilogue.h epi4 multiplies by the channel's scale FIRST (`v *= wsc`), then adds the bias: z = ((acc * scale + bias + rowbias) *
+gate + R) * out_scale. Callers pass W = Q * scale (computed in float64 so that it is the exact product; the scale is positive), which
+makes gamma_K S the scaled accumulator term. The scale multiply is one more fp32 rounding, on |acc * scale|. What Python reaches
+(ops.linear_ex with w_scale) has scale, bias, gate and residual -- four roundings, out_scale is 1.0 and multiplies exactly, there is
+no rowbias -- so EPI_OPS holds; `acc * scale + bias` contracted into one FMA under -ffp-contract=fast only saves one. Through the C
+ABI all six operands can meet (scale, bias, rowbias, gate, residual, out_scale): such a caller passes epi_ops=6. The module
+constant stays 4.
+
+LayerNorm fold (gemm_epilogue_ln, routes +ln and the LN instantiations of the pipelined loops, the small tile, the phased kernel and
+the split-K reduce kernel): rowstat [M, 2] = (rstd, nmr = -mean * rstd) and wsum [N], both fp32 and both taken exactly as the
+kernel reads them (tests/norm_bounds.py bounds row_stats itself), give
+
+    z = rstd[m] * acc + nmr[m] * wsum[n] + bias[n]
+
+so the accumulator term arrives as |rstd| gamma_K S. The code is `v = rs[0] * acc + rs[1] * wsum; if (bias) v += bias`: a multiply,
+then either a multiply and an add or -- contracted -- one FMA, then the bias add: at most four roundings (EPI_OPS), each on a partial
+result bounded by |rstd * acc| + |nmr * wsum| + |bias|. The two products nearly cancel when the row mean is large against the row
+deviation; the roundings do not know that, so the magnitudes are summed, not the terms:
+
+    e_z = |rstd| gamma_K S + EPI_OPS 2^-24 (|rstd * acc| + |nmr * wsum| + |bias|)
+
+dispatch_gemm refuses gate / rowbias / residual / fp8 scale next to the fold, and mi355x_sd_linear_ln has no out_scale; GEGLU and the
+activations follow as above.
 
 check() returns the worst |out - ref| / bound over the WHOLE output (the margin the logs show; a correct kernel stays below ~0.5, a
 wrong sub-tile or a doubled bias lands far above 1) and the rel-L2 of the same comparison.
@@ -71,11 +104,14 @@ def _act(name, z):
 
 
 def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=False, gate=None, rows_per_batch=0,
-              residual=None, rowbias=None):
+              residual=None, rowbias=None, rowstat=None, wsum=None, bias_acc=False, epi_ops=EPI_OPS):
     """float64 reference and elementwise accumulator-side error e (before the output rounding) of
     out = act(((a @ w^T) * w_scale + bias + rowbias[m // rows_per_batch]) * gate[m // rows_per_batch] + residual) * out_scale ...,
     or the GEGLU form. a [M, K], w [N, K] (for WS: the dequantized weights, w_scale None), bias [N], gate and rowbias
-    [batches, N], residual [M, N] (16-bit, or fp32 for r_f32 launches): the logical operands exactly as the kernel reads them."""
+    [batches, N], residual [M, N] (16-bit, or fp32 for r_f32 launches): the logical operands exactly as the kernel reads them.
+    rowstat [M, 2] fp32 (rstd, -mean * rstd) with wsum [N] fp32: the LayerNorm-folded form z = rstd * acc + nmr * wsum + bias.
+    bias_acc: the bias starts the accumulators; epi_ops: the epilogue's fp32 roundings where a form has more than EPI_OPS (the
+    module docstring derives both)."""
     M, K = a.shape
     A, W = a.double(), w.double()
     acc = A @ W.t()
@@ -85,8 +121,18 @@ def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=F
         acc = acc * w_scale.double()
         e = e * w_scale.double().abs()
     b = bias.double() if bias is not None else torch.zeros(acc.shape[1], dtype=torch.float64, device=acc.device)
-    mag = acc.abs() + b.abs()
-    z = acc + b
+    if bias_acc:
+        e = e + gamma(K) * b.abs()
+    if rowstat is not None:
+        rstd, nmr = rowstat.double()[:, :1], rowstat.double()[:, 1:]
+        corr = nmr * wsum.double()
+        acc, e = rstd * acc, rstd.abs() * e
+        mag = acc.abs() + corr.abs() + b.abs()
+        z = acc + corr + b
+        del corr
+    else:
+        mag = acc.abs() + b.abs()
+        z = acc + b
     del acc
     if rowbias is not None:
         rb = rowbias.double()[torch.arange(M, device=z.device) // rows_per_batch]
@@ -100,7 +146,7 @@ def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=F
         r = residual.double()
         z, mag = z + r, mag + r.abs()
         del r
-    e = abs(out_scale) * (e + EPI_OPS * U32 * mag)
+    e = abs(out_scale) * (e + epi_ops * U32 * mag)
     z = z * out_scale
     del mag
     if geglu:

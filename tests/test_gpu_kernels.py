@@ -222,8 +222,10 @@ def _close(a, b, rel):
                                           (4100, 700, 640, 320), (260, 260, 2048, 257), (9000, 1280, 128, 160)])
 def test_pipelined_tiles_ragged_edges(ops, M, N, K, tile):
     """K % 64 == 0 takes the software-pipelined loops (gemm_pipe.hip): rows >= M / N are out-of-range buffer offsets
-    that the hardware zero-fills. Ragged M and N against every tile family, forced through MI355X_SD_GEMM_TILE in a
-    subprocess-free way (the env var is read once per process, so the picker's own choice is used when it is unset)."""
+    that the hardware zero-fills. Ragged M and N on the PICKER's choice for each shape. The parameter `tile` has no effect: it names
+    the family the shape was chosen for, but MI355X_SD_GEMM_TILE is a switch of the debug build read once per process, and this
+    process runs the production library with nothing set. The forced tile families, with their routes asserted and the whole
+    output held to the float64 bound, are in tests/test_gpu_gemm_linear.py."""
     g = torch.Generator().manual_seed(M + N + K)
     a = bfr(torch.randn(M, K, generator=g))
     w = bfr(torch.randn(N, K, generator=g) / math.sqrt(K))
