@@ -6,89 +6,88 @@
 //       triton_ops.py:1692-1752 (kernel :1652-1689)
 // Inside this library's own SD3 program the same arithmetic lives in GEMM epilogues / row maps (sd3.py); these entry points exist
 // so that a PaddleMIX maintainer can swap the Triton ops one for one.
-// One wave per row, 16-byte accesses, fp32 statistics (shifted one-pass, like layernorm_kernel), two outputs written in the pass
-// that read the inputs: 2 reads + 2 writes of the row = the op's minimum traffic.
+// One wave per row, 16-byte accesses, fp32 statistics (the shifted one-pass row_moments of norm_rows.h), two outputs written in the
+// pass that read the inputs: 2 reads + 2 writes of the row = the op's minimum traffic.
 #include "common.h"
 #include "kernels.h"
+#include "norm_rows.h"
 
 namespace sd {
 
+// Not a form of row_norm_kernel (written as one, every instantiation compiled to more registers: profiles/r16_row_norm_skeleton.txt):
+// the body below stands on the skeleton's pieces -- RowWave, row_moments at one row per trip, pack8 / store8, the launcher.
 // M16: gate / scale / shift / weight / bias are the build's 16-bit element type (what the reference passes) instead of fp32
-template <int NCH, bool M16>
-__global__ __launch_bounds__(256) void fused_adaln_scale_residual_kernel(
-    const bf16* __restrict__ x, int ldx, const bf16* __restrict__ mha, int ldm, const void* __restrict__ gate,
-    const void* __restrict__ scale, const void* __restrict__ shift, int ld_mod, int rows_per_batch,
-    const void* __restrict__ weight, const void* __restrict__ bias, float eps, int rows, int C, bf16* __restrict__ resi,
-    int ldr, bf16* __restrict__ out, int ldo) {
-  const int lane = threadIdx.x & 63;
+template <bool M16>
+struct FusedAdaLN {
+  const bf16* x;
+  int ldx;
+  const bf16* mha;
+  int ldm;
+  const void *gate, *scale, *shift;
+  int ld_mod, rows_per_batch;
+  const void *weight, *bias;   // either may be null
+  bf16* resi;
+  int ldr;
+  bf16* out;
+  int ldo;
+};
+
+template <bool M16, int NCH>
+__global__ __launch_bounds__(256) void fused_adaln_scale_residual_kernel(FusedAdaLN<M16> f, int rows, int C, float eps) {
+  const RowWave w(C);
   const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  const float invC = 1.0f / (float)C;
   for (int row = wave_g; row < rows; row += nwaves) {
-    const size_t mrow = (size_t)(row / rows_per_batch) * ld_mod;
-    float v[NCH][8];
+    const size_t mrow = (size_t)(row / f.rows_per_batch) * f.ld_mod;
+    float v[1][NCH][8];
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      const int cc = lane + 64 * i;
-      if (cc < cv) {
-        const u32x4 rx = *reinterpret_cast<const u32x4*>(x + (size_t)row * ldx + cc * 8);
-        const u32x4 rm = *reinterpret_cast<const u32x4*>(mha + (size_t)row * ldm + cc * 8);
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
+        const u32x4 rx = *reinterpret_cast<const u32x4*>(f.x + (size_t)row * f.ldx + cc * 8);
+        const u32x4 rm = *reinterpret_cast<const u32x4*>(f.mha + (size_t)row * f.ldm + cc * 8);
         const bf16x8 tx = *reinterpret_cast<const bf16x8*>(&rx), tm = *reinterpret_cast<const bf16x8*>(&rm);
         float g8[8], r8[8];
-        load_mod8<M16>(gate, mrow + cc * 8, g8);
+        load_mod8<M16>(f.gate, mrow + cc * 8, g8);
 #pragma unroll
         for (int j = 0; j < 8; ++j) r8[j] = __builtin_fmaf((float)tm[j], g8[j], (float)tx[j]);
         // the residual leaves as a 16-bit tensor; the LayerNorm of the unfused definition sees THAT tensor
-        const u32x4 pk = {pack_bf16(r8[0], r8[1]), pack_bf16(r8[2], r8[3]), pack_bf16(r8[4], r8[5]), pack_bf16(r8[6], r8[7])};
-        *reinterpret_cast<u32x4*>(resi + (size_t)row * ldr + cc * 8) = pk;
-        const bf16x8 rr = *reinterpret_cast<const bf16x8*>(&pk);
+        const u32x4 pk = pack8(r8);
+        *reinterpret_cast<u32x4*>(f.resi + (size_t)row * f.ldr + cc * 8) = pk;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[i][j] = (float)rr[j];
+        for (int j = 0; j < 8; ++j) v[0][i][j] = chunk_val(pk, j);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+        for (int j = 0; j < 8; ++j) v[0][i][j] = 0.f;
       }
     }
-    const float K = __shfl(v[0][0], 0, 64);
-    float a = 0.f, q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (lane + 64 * i < cv) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = v[i][j] - K;
-          a += d;
-          q = __builtin_fmaf(d, d, q);
-        }
-      }
-    a = wave_sum(a);
-    q = wave_sum(q);
-    const float m = a * invC;
-    const float rstd = rsqrtf(fmaxf(q * invC - m * m, 0.f) + eps);
-    const float mean = K + m;
+    float mean[1], rstd[1];
+    row_moments(v, w, eps, mean, rstd);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      const int cc = lane + 64 * i;
-      if (cc < cv) {
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
         float sc[8], sh[8], wv[8], bv[8], o[8];
-        load_mod8<M16>(scale, mrow + cc * 8, sc);
-        load_mod8<M16>(shift, mrow + cc * 8, sh);
-        if (weight) load_mod8<M16>(weight, (size_t)cc * 8, wv);
-        if (bias) load_mod8<M16>(bias, (size_t)cc * 8, bv);
+        load_mod8<M16>(f.scale, mrow + cc * 8, sc);
+        load_mod8<M16>(f.shift, mrow + cc * 8, sh);
+        if (f.weight) load_mod8<M16>(f.weight, (size_t)cc * 8, wv);
+        if (f.bias) load_mod8<M16>(f.bias, (size_t)cc * 8, bv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          float y = (v[i][j] - mean) * rstd;
-          if (weight) y *= wv[j];
-          if (bias) y += bv[j];
+          float y = (v[0][i][j] - mean[0]) * rstd[0];
+          if (f.weight) y *= wv[j];
+          if (f.bias) y += bv[j];
           o[j] = __builtin_fmaf(y, 1.0f + sc[j], sh[j]);
         }
-        const u32x4 pk = {pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
-        *reinterpret_cast<u32x4*>(out + (size_t)row * ldo + cc * 8) = pk;
+        store8(f.out + (size_t)row * f.ldo + cc * 8, o);
       }
     }
   }
 }
+template <bool M16, int NCH>
+struct RowKernel<FusedAdaLN<M16>, NCH, 1> {
+  static constexpr auto fn = fused_adaln_scale_residual_kernel<M16, NCH>;
+};
 
 int launch_fused_adaln_scale_residual(const bf16* x, int ldx, const bf16* mha, int ldm, const void* gate, const void* scale,
                                       const void* shift, int ld_mod, int mod16, int rows_per_batch, const void* weight,
@@ -97,25 +96,16 @@ int launch_fused_adaln_scale_residual(const bf16* x, int ldx, const bf16* mha, i
   if (rows <= 0 || C <= 0 || rows_per_batch <= 0) return SD_ERR_INVALID;
   if ((C & 7) || (ldx & 7) || (ldm & 7) || (ldr & 7) || (ldo & 7) || (ld_mod & (mod16 ? 7 : 3)) || C > 4096) return SD_ERR_UNSUPPORTED;
   if (mod16 && ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias)) & 15)) return SD_ERR_UNSUPPORTED;
-  const int cv = C >> 3;
-  int blocks = (rows + 3) / 4;
-  if (blocks > 2048) blocks = 2048;
-#define SD_FA_LAUNCH(NCH, M16) do {                                                                                                    \
-  hipLaunchKernelGGL((fused_adaln_scale_residual_kernel<NCH, M16>), dim3(blocks), dim3(256), 0, stream, x, ldx, mha, ldm, gate, scale, \
-                     shift, ld_mod, rows_per_batch, weight, bias, eps, rows, C, resi, ldr, out, ldo);                                  \
-  norm_route("fused_adaln", C, NCH, 1, M16 ? "m16" : "m32"); } while (0)
-  if (mod16) {
-    if (cv <= 128) SD_FA_LAUNCH(2, true);
-    else if (cv <= 256) SD_FA_LAUNCH(4, true);
-    else SD_FA_LAUNCH(8, true);
-  } else {
-    if (cv <= 128) SD_FA_LAUNCH(2, false);
-    else if (cv <= 256) SD_FA_LAUNCH(4, false);
-    else SD_FA_LAUNCH(8, false);
-  }
-#undef SD_FA_LAUNCH
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  const int blocks = one_row_grid(rows);
+  if (mod16)
+    return launch_row_norm<Inst<2, 1>, Inst<4, 1>, Inst<8, 1>>(
+        FusedAdaLN<true>{x, ldx, mha, ldm, gate, scale, shift, ld_mod, rows_per_batch, weight, bias, resi, ldr, out, ldo}, rows, C, eps,
+        blocks, "fused_adaln", "m16", stream);
+  return launch_row_norm<Inst<2, 1>, Inst<4, 1>, Inst<8, 1>>(
+      FusedAdaLN<false>{x, ldx, mha, ldm, gate, scale, shift, ld_mod, rows_per_batch, weight, bias, resi, ldr, out, ldo}, rows, C, eps,
+      blocks, "fused_adaln", "m32", stream);
 }
+
 
 // out_i[b][s][:] = (s < S1 ? x[b][s] : y[b][s - S1])[i*C : (i+1)*C], i = 0 (q), 1 (k), 2 (v)
 __global__ void split_concat_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y, bf16* __restrict__ o0,

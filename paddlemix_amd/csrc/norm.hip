@@ -19,10 +19,9 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "norm_rows.h"
 
 namespace sd {
-
-static int ln_grid(int rows, int rows_per_block);
 
 // MI355X_SD_NORM_LOG=<path> (debug-switch build only, like MI355X_SD_GEMM_LOG / MI355X_SD_ATTN_LOG) appends "entry C NCH ROWS flags"
 // per kernel launch of the normalisation launchers here and in fused_ops.hip: entry is the kernel, NCH / ROWS / flags its template
@@ -36,30 +35,6 @@ void norm_route(const char* entry, int C, int nch, int rows, const char* flags) 
   if (!log) return;
   fprintf(log, "%s %d %d %d %s\n", entry, C, nch, rows, flags);
   fflush(log);
-}
-
-// 8 consecutive channels of a row as fp32: from the build's 16-bit elements (one 16-byte load) or, in the fp32
-// residual-stream mode (XF32), from fp32 rows (two 16-byte loads). `x` is the row base in ELEMENTS of its own type.
-// `ok == false` yields zeros. Only the raw load sits under the predicate (the conversion does not), so that the compiler
-// issues the loads of an unrolled caller back to back instead of one branch + s_waitcnt per chunk.
-template <bool XF32>
-__device__ __forceinline__ void load8f(const void* x, size_t elem_off, float (&f)[8], bool ok = true) {
-  if constexpr (XF32) {
-    const float* p = reinterpret_cast<const float*>(x) + elem_off;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-    if (ok) {
-      a = *reinterpret_cast<const f32x4*>(p);
-      b = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[j] = a[j]; f[4 + j] = b[j]; }
-  } else {
-    u32x4 raw = {0u, 0u, 0u, 0u};
-    if (ok) raw = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16*>(x) + elem_off);
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(&raw);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
-  }
 }
 
 // one element of x as fp32 (the GroupNorm pilot K of a (batch, group): x[b][pixel 0][first channel of the group])
@@ -429,384 +404,219 @@ int launch_groupnorm_act(const bf16* x, int B, int HW, int C, int ldx, int group
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 
-// LayerNorm: persistent waves. A wave keeps gamma / beta of its channel chunks in registers and walks rows
-// (ROWS at a time: all loads issued up front, the ROWS reduction chains interleave), so the per-row traffic is
-// exactly one read and one write of the row. Statistics in one pass over data shifted by the row's first element
-// (sum(x-K), sum((x-K)^2): no cancellation for the O(1..10) activations here), fp32.
-template <int NCH, int ROWS, bool XF32 = false>
-__global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ x, int rows, int C, int ldx,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float eps, bf16* __restrict__ y, int ldy) {
-  const int lane = threadIdx.x & 63;
-  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  float g[NCH][8], bt[NCH][8];
+// ---- the row kernels: forms of row_norm_kernel (norm_rows.h) -------------------------------------------------------------------------
+// LayerNorm: a wave keeps gamma / beta of its channel chunks in registers, so the per-row traffic is exactly one read and one
+// write of the row. XF32: x rows are fp32 (residual-stream mode).
+template <bool XF32>
+struct LayerNormRows {
+  const void* x;
+  int ldx;
+  const float *gamma, *beta;   // either may be null: 1 / 0
+  bf16* y;
+  int ldy;
+  typedef float Chunk[8];
+  template <int NCH>
+  struct Affine {
+    float g[NCH][8], bt[NCH][8];
+  };
+  template <int NCH>
+  __device__ __forceinline__ Affine<NCH> keep(const RowWave& w) const {
+    Affine<NCH> k;
 #pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int cc = lane + 64 * i;
-    // two 16-byte loads per vector under ONE predicate each (element-wise selects compile to a branch + dword load per element)
-    f32x4 ga = {1.f, 1.f, 1.f, 1.f}, gb = ga, ba = {0.f, 0.f, 0.f, 0.f}, bb = ba;
-    if (gamma && cc < cv) {
-      ga = *reinterpret_cast<const f32x4*>(gamma + cc * 8);
-      gb = *reinterpret_cast<const f32x4*>(gamma + cc * 8 + 4);
-    }
-    if (beta && cc < cv) {
-      ba = *reinterpret_cast<const f32x4*>(beta + cc * 8);
-      bb = *reinterpret_cast<const f32x4*>(beta + cc * 8 + 4);
-    }
+    for (int i = 0; i < NCH; ++i) {
+      const int cc = w.lane + 64 * i;
+      // two 16-byte loads per vector under ONE predicate each (element-wise selects compile to a branch + dword load per element)
+      f32x4 ga = {1.f, 1.f, 1.f, 1.f}, gb = ga, ba = {0.f, 0.f, 0.f, 0.f}, bb = ba;
+      if (gamma && cc < w.cv) {
+        ga = *reinterpret_cast<const f32x4*>(gamma + cc * 8);
+        gb = *reinterpret_cast<const f32x4*>(gamma + cc * 8 + 4);
+      }
+      if (beta && cc < w.cv) {
+        ba = *reinterpret_cast<const f32x4*>(beta + cc * 8);
+        bb = *reinterpret_cast<const f32x4*>(beta + cc * 8 + 4);
+      }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      g[i][j] = ga[j];
-      g[i][4 + j] = gb[j];
-      bt[i][j] = ba[j];
-      bt[i][4 + j] = bb[j];
+      for (int j = 0; j < 4; ++j) {
+        k.g[i][j] = ga[j];
+        k.g[i][4 + j] = gb[j];
+        k.bt[i][j] = ba[j];
+        k.bt[i][4 + j] = bb[j];
+      }
     }
+    return k;
   }
-  const float invC = 1.0f / (float)C;
-  for (int row0 = wave_g * ROWS; row0 < rows; row0 += nwaves * ROWS) {
-    float v[ROWS][NCH][8];
+  template <int NCH>
+  __device__ __forceinline__ void load(int row, float (&v)[NCH][8], const RowWave& w) const {
+    load_row<XF32>(x, (size_t)row * ldx, v, w);
+  }
+  template <int NCH>
+  __device__ __forceinline__ void finish(int row, const float (&v)[NCH][8], float mean, float rstd, const RowWave& w,
+                                         const Affine<NCH>& k) const {
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int row = min(row0 + r, rows - 1);
+    for (int i = 0; i < NCH; ++i) {
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
+        float o[8];
 #pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        const int cc = lane + 64 * i;
-        load8f<XF32>(x, (size_t)row * ldx + cc * 8, v[r][i], cc < cv);
-      }
-    }
-    float mean[ROWS], rstd[ROWS], s1[ROWS], s2[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const float K = __shfl(v[r][0][0], 0, 64);
-      float a = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (lane + 64 * i < cv) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float d = v[r][i][j] - K;
-            a += d;
-            q = __builtin_fmaf(d, d, q);
-          }
-        }
-      }
-      s1[r] = a;
-      s2[r] = q;
-      mean[r] = K;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        s1[r] += __shfl_xor(s1[r], o, 64);
-        s2[r] += __shfl_xor(s2[r], o, 64);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const float m = s1[r] * invC;
-      const float var = fmaxf(s2[r] * invC - m * m, 0.f);
-      mean[r] += m;
-      rstd[r] = rsqrtf(var + eps);
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      if (row0 + r < rows) {
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const int cc = lane + 64 * i;
-          if (cc < cv) {
-            float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf((v[r][i][j] - mean[r]) * rstd[r], g[i][j], bt[i][j]);
-            u32x4 pk = {pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
-            *reinterpret_cast<u32x4*>(y + (size_t)(row0 + r) * ldy + cc * 8) = pk;
-          }
-        }
+        for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf((v[i][j] - mean) * rstd, k.g[i][j], k.bt[i][j]);
+        store8(y + (size_t)row * ldy + cc * 8, o);
       }
     }
   }
-}
-
-// Grid of the row-normalisation kernels: blocks = clamp(needed / div, min, max). Round 1 measured, back to back in isolation,
-// that waves walking 2-4 row groups beat one group per wave (scripts/ln_probe.py: 8192 x 1280 15.7 -> 13.6 us at 256 blocks) and
-// used div = 2; inside the SDXL step, and with the per-wave prologue now 12 vector loads instead of 48 branches, one trip per
-// wave wins (LayerNorm class 3.07 -> 2.79 ms per step, profiles/r02_k_ln_grid.txt): div = 1, at most 1024 blocks.
-static int ln_grid(int rows, int rows_per_block) {
-  constexpr int lo = 256, hi = 1024;   // (div = 1)
-  const int needed = (rows + rows_per_block - 1) / rows_per_block;
-  int blocks = needed;
-  if (blocks < lo) blocks = lo;
-  if (blocks > hi) blocks = hi;
-  return blocks < needed ? blocks : needed;
-}
+};
 
 int launch_layernorm(const void* x, int x_f32, int rows, int C, int ldx, const float* gamma, const float* beta, float eps, bf16* y,
                      int ldy, hipStream_t stream) {
   if (rows <= 0 || C <= 0) return SD_ERR_INVALID;
   if ((C & 7) || (ldx & 7) || (ldy & 7) || C > 2560) return SD_ERR_UNSUPPORTED;
-  const int wpb = 4;
-  const int cv = C >> 3;
   // rows per wave: round 1 measured 4 better than 2 (4.6 vs 5.2 ms per SDXL step) when every wave paid a 48-branch prologue; with
   // the vector prologue and one trip per wave, 2 rows (twice the waves, ~110 instead of 200 registers) is ahead again: class
   // 2.80 -> 2.65 ms per step (profiles/r02_l_norm_knobs.txt).
-  const int blocks = ln_grid(rows, wpb * 2);
-#define SD_LN_LAUNCH(NCH, R_, F_) do {                                                                                               \
-  hipLaunchKernelGGL((layernorm_kernel<NCH, R_, F_>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, gamma, beta, eps, y, \
-                     ldy);                                                                                                           \
-  norm_route("layernorm", C, NCH, R_, F_ ? "xf32" : "x16"); } while (0)
-  if (x_f32) {
-    if (cv <= 128) SD_LN_LAUNCH(2, 2, true);
-    else if (cv <= 192) SD_LN_LAUNCH(3, 2, true);
-    else SD_LN_LAUNCH(5, 2, true);
-  } else {
-    if (cv <= 128) SD_LN_LAUNCH(2, 2, false);
-    else if (cv <= 192) SD_LN_LAUNCH(3, 2, false);
-    else SD_LN_LAUNCH(5, 2, false);
-  }
-#undef SD_LN_LAUNCH
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  const int blocks = ln_grid(rows, 4 * 2);
+  if (x_f32)
+    return launch_row_norm<Inst<2, 2>, Inst<3, 2>, Inst<5, 2>>(LayerNormRows<true>{x, ldx, gamma, beta, y, ldy}, rows, C, eps, blocks,
+                                                        "layernorm", "xf32", stream);
+  else
+    return launch_row_norm<Inst<2, 2>, Inst<3, 2>, Inst<5, 2>>(LayerNormRows<false>{x, ldx, gamma, beta, y, ldy}, rows, C, eps, blocks,
+                                                        "layernorm", "x16", stream);
 }
 
-// Row statistics for the LayerNorm-folded GEMM (mi355x_sd_linear_ln): stats[row] = (rstd, -mean * rstd), the same
-// shifted one-pass fp32 statistics as layernorm_kernel. The normalised row is never written: the consumer GEMM
-// multiplies the raw rows by W.diag(gamma) and applies  rstd * acc - mean * rstd * rowsum(W')  in its epilogue.
-template <int NCH, int ROWS>
-__global__ __launch_bounds__(256) void row_stats_kernel(const bf16* __restrict__ x, int rows, int C, int ldx, float eps,
-                                                        float* __restrict__ stats) {
-  const int lane = threadIdx.x & 63;
-  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  const float invC = 1.0f / (float)C;
-  for (int row0 = wave_g * ROWS; row0 < rows; row0 += nwaves * ROWS) {
-    float s1[ROWS], s2[ROWS], K[ROWS];
-    u32x4 raw[ROWS][NCH];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const bf16* xr = x + (size_t)min(row0 + r, rows - 1) * ldx;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        const int cc = lane + 64 * i;
-        raw[r][i] = u32x4{0u, 0u, 0u, 0u};
-        if (cc < cv) raw[r][i] = *reinterpret_cast<const u32x4*>(xr + cc * 8);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const bf16x8 t0 = *reinterpret_cast<const bf16x8*>(&raw[r][0]);
-      K[r] = __shfl((float)t0[0], 0, 64);
-      float a = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (lane + 64 * i < cv) {
-          const bf16x8 t = *reinterpret_cast<const bf16x8*>(&raw[r][i]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float d = (float)t[j] - K[r];
-            a += d;
-            q = __builtin_fmaf(d, d, q);
-          }
-        }
-      }
-      s1[r] = a;
-      s2[r] = q;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        s1[r] += __shfl_xor(s1[r], o, 64);
-        s2[r] += __shfl_xor(s2[r], o, 64);
-      }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        if (row0 + r < rows) {
-          const float m = s1[r] * invC;
-          const float rstd = rsqrtf(fmaxf(s2[r] * invC - m * m, 0.f) + eps);
-          *reinterpret_cast<float2*>(stats + 2 * (size_t)(row0 + r)) = make_float2(rstd, -(K[r] + m) * rstd);
-        }
-      }
-    }
+// Row statistics for the LayerNorm-folded GEMM (mi355x_sd_linear_ln): stats[row] = (rstd, -mean * rstd). The normalised row is
+// never written: the consumer GEMM multiplies the raw rows by W.diag(gamma) and applies  rstd * acc - mean * rstd * rowsum(W')  in
+// its epilogue. Four rows per trip, so a lane keeps the raw 16-bit vectors (4 registers per chunk, not 8 floats).
+struct RowStats {
+  const bf16* x;
+  int ldx;
+  float* stats;
+  typedef u32x4 Chunk;
+  template <int NCH>
+  __device__ __forceinline__ Nothing keep(const RowWave&) const { return {}; }
+  template <int NCH>
+  __device__ __forceinline__ void load(int row, u32x4 (&v)[NCH], const RowWave& w) const {
+    load_row(x, (size_t)row * ldx, v, w);
   }
-}
+  template <int NCH>
+  __device__ __forceinline__ void finish(int row, const u32x4 (&)[NCH], float mean, float rstd, const RowWave& w, Nothing) const {
+    if (w.lane == 0) *reinterpret_cast<float2*>(stats + 2 * (size_t)row) = make_float2(rstd, -mean * rstd);
+  }
+};
 
 int launch_row_stats(const bf16* x, int rows, int C, int ldx, float eps, float* stats, hipStream_t stream) {
   if (rows <= 0 || C <= 0) return SD_ERR_INVALID;
   if ((C & 7) || (ldx & 7) || C > 2560) return SD_ERR_UNSUPPORTED;
-  const int wpb = 4, cv = C >> 3;
-  constexpr int R = 4;
-  const int blocks = ln_grid(rows, wpb * R);
-#define SD_RS_LAUNCH(NCH) do {                                                                                          \
-  hipLaunchKernelGGL((row_stats_kernel<NCH, R>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, eps, stats); \
-  norm_route("row_stats", C, NCH, R, "-"); } while (0)
-  if (cv <= 64) SD_RS_LAUNCH(1);
-  else if (cv <= 128) SD_RS_LAUNCH(2);
-  else if (cv <= 192) SD_RS_LAUNCH(3);
-  else SD_RS_LAUNCH(5);
-#undef SD_RS_LAUNCH
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  return launch_row_norm<Inst<1, 4>, Inst<2, 4>, Inst<3, 4>, Inst<5, 4>>(RowStats{x, ldx, stats}, rows, C, eps, ln_grid(rows, 4 * 4),
+                                                                  "row_stats", "-", stream);
 }
 
 // T5LayerNorm (RMSNorm; PPD/transformers/t5/modeling.py:86-108): y = weight * x * rsqrt(mean(x^2) + eps), no mean
-// subtraction, no bias; statistics in fp32. Same wave layout as layernorm_kernel (a wave owns ROWS rows).
+// subtraction, no bias; statistics in fp32. Not a form of the skeleton: the body sums the squares WHILE it loads (with fp16 elements
+// the compiler then keeps the raw halves and converts them again at the store: 124 registers at NCH 8 where loading first and
+// summing afterwards holds 184) and has no mean. It stands on the skeleton's pieces: RowWave, load8f, row_rms, store8, the launcher.
+struct RmsNormRows {
+  const bf16* x;
+  int ldx;
+  const float* weight;
+  bf16* y;
+  int ldy;
+};
 template <int NCH, int ROWS>
-__global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16* __restrict__ x, int rows, int C, int ldx,
-                                                      const float* __restrict__ weight, float eps, bf16* __restrict__ y,
-                                                      int ldy) {
-  const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void rmsnorm_kernel(RmsNormRows f, int rows, int C, float eps) {
+  const RowWave w(C);
   const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  const float invC = 1.0f / (float)C;
   for (int row0 = wave_g * ROWS; row0 < rows; row0 += nwaves * ROWS) {
-    float v[ROWS][NCH][8], ss[ROWS];
+    float v[ROWS][NCH][8], ss[ROWS], rstd[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
-      const bf16* xr = x + (size_t)min(row0 + r, rows - 1) * ldx;
+      const size_t xr = (size_t)min(row0 + r, rows - 1) * f.ldx;
       float q = 0.f;
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        const int cc = lane + 64 * i;
-        u32x4 raw = {0u, 0u, 0u, 0u};
-        if (cc < cv) raw = *reinterpret_cast<const u32x4*>(xr + cc * 8);
-        const bf16x8 t = *reinterpret_cast<const bf16x8*>(&raw);
+        const int cc = w.lane + 64 * i;
+        load8f<false>(f.x, xr + cc * 8, v[r][i], cc < w.cv);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          v[r][i][j] = (float)t[j];
-          q = __builtin_fmaf(v[r][i][j], v[r][i][j], q);
-        }
+        for (int j = 0; j < 8; ++j) q = __builtin_fmaf(v[r][i][j], v[r][i][j], q);
       }
       ss[r] = q;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) ss[r] += __shfl_xor(ss[r], o, 64);
+    row_rms(ss, w, eps, rstd);
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
       if (row0 + r >= rows) continue;
-      const float rstd = rsqrtf(ss[r] * invC + eps);
-      bf16* yr = y + (size_t)(row0 + r) * ldy;
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
-        const int cc = lane + 64 * i;
-        if (cc < cv) {
-          float o8[8];
+        const int cc = w.lane + 64 * i;
+        if (cc < w.cv) {
+          float o[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j) o8[j] = v[r][i][j] * rstd * weight[cc * 8 + j];
-          u32x4 pk = {pack_bf16(o8[0], o8[1]), pack_bf16(o8[2], o8[3]), pack_bf16(o8[4], o8[5]), pack_bf16(o8[6], o8[7])};
-          *reinterpret_cast<u32x4*>(yr + cc * 8) = pk;
+          for (int j = 0; j < 8; ++j) o[j] = v[r][i][j] * rstd[r] * f.weight[cc * 8 + j];
+          store8(f.y + (size_t)(row0 + r) * f.ldy + cc * 8, o);
         }
       }
     }
   }
 }
+template <int NCH, int ROWS>
+struct RowKernel<RmsNormRows, NCH, ROWS> {
+  static constexpr auto fn = rmsnorm_kernel<NCH, ROWS>;
+};
 
 int launch_rmsnorm(const bf16* x, int rows, int C, int ldx, const float* weight, float eps, bf16* y, int ldy,
                    hipStream_t stream) {
   if (rows <= 0 || C <= 0) return SD_ERR_INVALID;
   if ((C & 7) || (ldx & 7) || (ldy & 7) || C > 4096) return SD_ERR_UNSUPPORTED;
-  const int cv = C >> 3;
-  const int blocks = ln_grid(rows, 8);
-#define SD_RMS_LAUNCH(NCH) do {                                                                                           \
-  hipLaunchKernelGGL((rmsnorm_kernel<NCH, 2>), dim3(blocks), dim3(256), 0, stream, x, rows, C, ldx, weight, eps, y, ldy); \
-  norm_route("rmsnorm", C, NCH, 2, "-"); } while (0)
-  if (cv <= 128) SD_RMS_LAUNCH(2);
-  else if (cv <= 256) SD_RMS_LAUNCH(4);
-  else SD_RMS_LAUNCH(8);
-#undef SD_RMS_LAUNCH
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  return launch_row_norm<Inst<2, 2>, Inst<4, 2>, Inst<8, 2>>(RmsNormRows{x, ldx, weight, y, ldy}, rows, C, eps, ln_grid(rows, 8),
+                                                             "rmsnorm", "-", stream);
 }
 
 // Adaptive LayerNorm of the MMDiT blocks: y = LN(x) * (1 + scale[b]) + shift[b], LN without affine, b = row / rows_per_batch.
 // Reference: AdaLayerNormZero.forward (ppdiffusers/ppdiffusers/models/normalization.py:72-86), AdaLayerNormContinuous
 // (:190-202), the modulated norm2 of JointTransformerBlock (attention.py:184-185) and the fused Triton op
-// adaptive_layer_norm (paddlemix/triton_ops/triton_ops.py:981-1027).  Same wave layout as layernorm_kernel.
-template <int NCH, int ROWS, bool M16 = false>
-__global__ __launch_bounds__(256) void adaln_kernel(const bf16* __restrict__ x, int rows, int C, int ldx,
-                                                    const void* __restrict__ scale, const void* __restrict__ shift,
-                                                    int ld_mod, int rows_per_batch, float eps, bf16* __restrict__ y,
-                                                    int ldy) {
-  const int lane = threadIdx.x & 63;
-  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  const float invC = 1.0f / (float)C;
-  for (int row0 = wave_g * ROWS; row0 < rows; row0 += nwaves * ROWS) {
-    float v[ROWS][NCH][8];
+// adaptive_layer_norm (paddlemix/triton_ops/triton_ops.py:981-1027).
+template <bool M16>
+struct AdaLNRows {
+  const bf16* x;
+  int ldx;
+  const void *scale, *shift;
+  int ld_mod, rows_per_batch;
+  bf16* y;
+  int ldy;
+  typedef float Chunk[8];
+  template <int NCH>
+  __device__ __forceinline__ Nothing keep(const RowWave&) const { return {}; }
+  template <int NCH>
+  __device__ __forceinline__ void load(int row, float (&v)[NCH][8], const RowWave& w) const {
+    load_row<false>(x, (size_t)row * ldx, v, w);
+  }
+  template <int NCH>
+  __device__ __forceinline__ void finish(int row, const float (&v)[NCH][8], float mean, float rstd, const RowWave& w, Nothing) const {
+    const size_t mrow = (size_t)(row / rows_per_batch) * ld_mod;
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int row = min(row0 + r, rows - 1);
-      const bf16* xr = x + (size_t)row * ldx;
+    for (int i = 0; i < NCH; ++i) {
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
+        float sc[8], sh[8], o[8];
+        load_mod8<M16>(scale, mrow + cc * 8, sc);
+        load_mod8<M16>(shift, mrow + cc * 8, sh);
 #pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        const int cc = lane + 64 * i;
-        u32x4 raw = {0u, 0u, 0u, 0u};
-        if (cc < cv) raw = *reinterpret_cast<const u32x4*>(xr + cc * 8);
-        const bf16x8 t = *reinterpret_cast<const bf16x8*>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[r][i][j] = (float)t[j];
-      }
-    }
-    float mean[ROWS], rstd[ROWS], s1[ROWS], s2[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const float K = __shfl(v[r][0][0], 0, 64);
-      float a = 0.f, q = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (lane + 64 * i < cv) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float d = v[r][i][j] - K;
-            a += d;
-            q = __builtin_fmaf(d, d, q);
-          }
-        }
-      }
-      s1[r] = a;
-      s2[r] = q;
-      mean[r] = K;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        s1[r] += __shfl_xor(s1[r], o, 64);
-        s2[r] += __shfl_xor(s2[r], o, 64);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const float m = s1[r] * invC;
-      const float var = fmaxf(s2[r] * invC - m * m, 0.f);
-      mean[r] += m;
-      rstd[r] = rsqrtf(var + eps);
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      if (row0 + r < rows) {
-        const size_t mrow = (size_t)((row0 + r) / rows_per_batch) * ld_mod;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const int cc = lane + 64 * i;
-          if (cc < cv) {
-            float sc[8], sh[8], o[8];
-            load_mod8<M16>(scale, mrow + cc * 8, sc);
-            load_mod8<M16>(shift, mrow + cc * 8, sh);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf((v[r][i][j] - mean[r]) * rstd[r], 1.0f + sc[j], sh[j]);
-            u32x4 pk = {pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
-            *reinterpret_cast<u32x4*>(y + (size_t)(row0 + r) * ldy + cc * 8) = pk;
-          }
-        }
+        for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf((v[i][j] - mean) * rstd, 1.0f + sc[j], sh[j]);
+        store8(y + (size_t)row * ldy + cc * 8, o);
       }
     }
   }
+};
+
+int launch_adaln(const bf16* x, int rows, int C, int ldx, const void* scale, const void* shift, int ld_mod, int mod16,
+                 int rows_per_batch, float eps, bf16* y, int ldy, hipStream_t stream) {
+  if (rows <= 0 || C <= 0 || rows_per_batch <= 0) return SD_ERR_INVALID;
+  if ((C & 7) || (ldx & 7) || (ldy & 7) || (ld_mod & (mod16 ? 7 : 3)) || C > 2560) return SD_ERR_UNSUPPORTED;
+  const int blocks = adaln_grid(rows);
+  if (mod16)   // 16-bit modulation vectors (the reference's own operand type)
+    return launch_row_norm<Inst<2, 4>, Inst<3, 4>, Inst<5, 2>>(AdaLNRows<true>{x, ldx, scale, shift, ld_mod, rows_per_batch, y, ldy}, rows, C,
+                                                        eps, blocks, "adaln", "m16", stream);
+  else
+    return launch_row_norm<Inst<2, 4>, Inst<3, 4>, Inst<5, 2>>(AdaLNRows<false>{x, ldx, scale, shift, ld_mod, rows_per_batch, y, ldy}, rows, C,
+                                                        eps, blocks, "adaln", "m32", stream);
 }
 
 // ---- W8A8 producers: rows quantised to OCP e4m3 with one fp32 scale per row (absmax / 448) ----
@@ -817,55 +627,33 @@ __device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float 
   return (unsigned)w;
 }
 
-// AdaLayerNorm (same arithmetic as adaln_kernel) with the fp8 quantisation fused: the modulated row never exists in
-// bf16. y8[row][C] bytes (row stride ldy bytes), yscale[row] = absmax / 448 (dequantised value = scale * q).
-template <int NCH>
-__global__ __launch_bounds__(256) void adaln_f8_kernel(const bf16* __restrict__ x, int rows, int C, int ldx,
-                                                       const float* __restrict__ scale, const float* __restrict__ shift,
-                                                       int ld_mod, int rows_per_batch, float eps,
-                                                       unsigned char* __restrict__ y8, int ldy, float* __restrict__ yscale,
-                                                       float* __restrict__ yl2) {
-  const int lane = threadIdx.x & 63;
-  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int cv = C >> 3;
-  const float invC = 1.0f / (float)C;
-  for (int row = wave_g; row < rows; row += nwaves) {
-    float v[NCH][8];
-    const bf16* xr = x + (size_t)row * ldx;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int cc = lane + 64 * i;
-      u32x4 raw = {0u, 0u, 0u, 0u};
-      if (cc < cv) raw = *reinterpret_cast<const u32x4*>(xr + cc * 8);
-      const bf16x8 t = *reinterpret_cast<const bf16x8*>(&raw);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[i][j] = (float)t[j];
-    }
-    const float K = __shfl(v[0][0], 0, 64);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (lane + 64 * i < cv) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = v[i][j] - K;
-          s1 += d;
-          s2 = __builtin_fmaf(d, d, s2);
-        }
-      }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const float m = s1 * invC;
-    const float mean = K + m, rstd = rsqrtf(fmaxf(s2 * invC - m * m, 0.f) + eps);
+// AdaLayerNorm (the arithmetic of AdaLNRows, fp32 modulation) with the fp8 quantisation fused: the modulated row never exists in
+// bf16. y8[row][C] bytes (row stride ldy bytes), yscale[row] = absmax / 448 (dequantised value = scale * q). One row per trip.
+struct AdaLNF8Rows {
+  const bf16* x;
+  int ldx;
+  const float *scale, *shift;
+  int ld_mod, rows_per_batch;
+  unsigned char* y8;
+  int ldy;
+  float *yscale, *yl2;   // yl2 may be null
+  typedef float Chunk[8];
+  template <int NCH>
+  __device__ __forceinline__ Nothing keep(const RowWave&) const { return {}; }
+  template <int NCH>
+  __device__ __forceinline__ void load(int row, float (&v)[NCH][8], const RowWave& w) const {
+    load_row<false>(x, (size_t)row * ldx, v, w);
+  }
+  template <int NCH>
+  __device__ __forceinline__ void finish(int row, float (&v)[NCH][8], float mean, float rstd, const RowWave& w, Nothing) const {
     const int bidx = row / rows_per_batch;
     const float* sc = scale + (size_t)bidx * ld_mod;
     const float* sh = shift + (size_t)bidx * ld_mod;
     float amax = 0.f, sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      const int cc = lane + 64 * i;
-      if (cc < cv) {
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           v[i][j] = __builtin_fmaf((v[i][j] - mean) * rstd, 1.0f + sc[cc * 8 + j], sh[cc * 8 + j]);
@@ -877,39 +665,29 @@ __global__ __launch_bounds__(256) void adaln_f8_kernel(const bf16* __restrict__ 
     amax = wave_max(amax);
     sq = wave_sum(sq);
     const float qs = fmaxf(amax, 1e-12f) * (1.0f / 448.0f), inv = 1.0f / qs;
-    if (lane == 0) {
+    if (w.lane == 0) {
       yscale[row] = qs;
       if (yl2) yl2[row] = sqrtf(sq);   // row L2 norm: bounds every output of the consuming GEMM (Cauchy-Schwarz)
     }
     unsigned char* yr = y8 + (size_t)row * ldy;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      const int cc = lane + 64 * i;
-      if (cc < cv) {
+      const int cc = w.lane + 64 * i;
+      if (cc < w.cv) {
         u32x2 pk = {pack_fp8x4(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv),
                     pack_fp8x4(v[i][4] * inv, v[i][5] * inv, v[i][6] * inv, v[i][7] * inv)};
         *reinterpret_cast<u32x2*>(yr + cc * 8) = pk;
       }
     }
   }
-}
+};
 
 int launch_adaln_f8(const bf16* x, int rows, int C, int ldx, const float* scale, const float* shift, int ld_mod,
                     int rows_per_batch, float eps, unsigned char* y8, int ldy, float* yscale, float* yl2, hipStream_t stream) {
   if (rows <= 0 || C <= 0 || rows_per_batch <= 0) return SD_ERR_INVALID;
   if ((C & 7) || (ldx & 7) || (ldy & 7) || (ld_mod & 3) || C > 2560) return SD_ERR_UNSUPPORTED;
-  const int cv = C >> 3;
-  int blocks = (rows + 3) / 4;
-  if (blocks > 2048) blocks = 2048;
-#define SD_AF8(NCH) do {                                                                                                \
-  hipLaunchKernelGGL((adaln_f8_kernel<NCH>), dim3(blocks), dim3(256), 0, stream, x, rows, C, ldx, scale, shift, ld_mod, \
-                     rows_per_batch, eps, y8, ldy, yscale, yl2);                                                        \
-  norm_route("adaln_f8", C, NCH, 1, "-"); } while (0)
-  if (cv <= 128) SD_AF8(2);
-  else if (cv <= 192) SD_AF8(3);
-  else SD_AF8(5);
-#undef SD_AF8
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
+  return launch_row_norm<Inst<2, 1>, Inst<3, 1>, Inst<5, 1>>(AdaLNF8Rows{x, ldx, scale, shift, ld_mod, rows_per_batch, y8, ldy, yscale, yl2},
+                                                      rows, C, eps, one_row_grid(rows), "adaln_f8", "-", stream);
 }
 
 // bf16 rows -> e4m3 rows + per-row scale (the attention output in front of the MMDiT output projections). One wave per
@@ -954,34 +732,6 @@ int launch_quantize_rows(const bf16* x, long rows, int C, int ldx, int x_rpb, lo
   hipLaunchKernelGGL(quantize_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, rows, C, ldx, x_rpb, x_bstride, y8,
                      ldy, yscale);
   norm_route("quantize_rows", C, 0, 1, "-");
-  return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
-}
-
-int launch_adaln(const bf16* x, int rows, int C, int ldx, const void* scale, const void* shift, int ld_mod, int mod16,
-                 int rows_per_batch, float eps, bf16* y, int ldy, hipStream_t stream) {
-  if (rows <= 0 || C <= 0 || rows_per_batch <= 0) return SD_ERR_INVALID;
-  if ((C & 7) || (ldx & 7) || (ldy & 7) || (ld_mod & (mod16 ? 7 : 3)) || C > 2560) return SD_ERR_UNSUPPORTED;
-  const int wpb = 4;
-  const int cv = C >> 3;
-  constexpr int R = 4;
-  // all row groups resident (measured better here than the capped grid of ln_grid: 2.54 vs 2.77 ms per SD3 step --
-  // the per-batch scale / shift vectors add a dependent load to every iteration)
-  int blocks = (rows + wpb * R - 1) / (wpb * R);
-  if (blocks > 256 * 8) blocks = 256 * 8;
-#define SD_ADALN_LAUNCH(NCH, RR, M16) do {                                                                                         \
-  hipLaunchKernelGGL((adaln_kernel<NCH, RR, M16>), dim3(blocks), dim3(64 * wpb), 0, stream, x, rows, C, ldx, scale, shift, ld_mod, \
-                     rows_per_batch, eps, y, ldy);                                                                                 \
-  norm_route("adaln", C, NCH, RR, M16 ? "m16" : "m32"); } while (0)
-  if (mod16) {   // 16-bit modulation vectors (the reference's own operand type)
-    if (cv <= 128) SD_ADALN_LAUNCH(2, R, true);
-    else if (cv <= 192) SD_ADALN_LAUNCH(3, R, true);
-    else SD_ADALN_LAUNCH(5, 2, true);
-  } else {
-    if (cv <= 128) SD_ADALN_LAUNCH(2, R, false);
-    else if (cv <= 192) SD_ADALN_LAUNCH(3, R, false);
-    else SD_ADALN_LAUNCH(5, 2, false);
-  }
-#undef SD_ADALN_LAUNCH
   return hipGetLastError() == hipSuccess ? SD_OK : SD_ERR_HIP;
 }
 

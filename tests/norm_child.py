@@ -3,7 +3,8 @@ to the elementwise float64 bound of tests/norm_bounds.py over its WHOLE output (
 inside buffers of the 0x7FA5 canary (row padding ldy > C, rows past the end); the input row gaps (ldx > C) and the modulation
 vectors' gaps (ld_mod > C) hold NaN, so a read outside a row poisons the statistics. With MI355X_SD_NORM_LOG set (debug build) each
 case also reports the kernel instantiations its launcher logged. Prints one JSON line: per case worst err / bound (and of the
-side outputs), unwritten / overwritten element counts, bit checks, route.
+side outputs), unwritten / overwritten element counts, bit checks, route, and "sha": a digest (tests/gpu_child.sha) of every output
+tensor the case checks -- what a comparison of two builds' bits reads.
 
   python tests/norm_child.py [case ...]     (no names: every case)
 """
@@ -16,7 +17,7 @@ import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import norm_bounds as NB  # noqa: E402
-from tests.gpu_child import Routes, emit  # noqa: E402
+from tests.gpu_child import Routes, emit, sha  # noqa: E402
 
 CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 CANARY32 = 0x7FA5A5A5
@@ -304,7 +305,9 @@ def run_case(name):
         ref, e = NB.groupnorm(vals, gamma, beta, groups, EPS, s["silu"], L=L)
         res["ratio"], res["rel"] = NB.check(y, ref, e)
         res["unwritten"], res["overwritten"] = _counts(ybits, yin, CANARY)
+        res["sha"] = {"y": sha(y)}
         if entry == "gn" and s["raw16"]:
+            res["sha"]["raw16"] = sha(raw)
             uw, ow = _counts(rbits, rin, CANARY)
             res["unwritten"] += uw
             res["overwritten"] += ow
@@ -321,6 +324,7 @@ def run_case(name):
         res["rc"] = lib.mi355x_sd_layernorm_ex(x.data_ptr(), rows, C, C + 16, ops._p(gamma), ops._p(beta), EPS, y.data_ptr(), C + 8,
                                                1 if s["xf32"] else 0, st)
         torch.cuda.synchronize()
+        res["sha"] = {"y": sha(y)}
         ref, e = NB.layernorm(vals, gamma, beta, EPS, NB.chain_rows("layernorm", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
         res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
@@ -333,6 +337,7 @@ def run_case(name):
         y, bits, inside = _canary((rows, 2), 2, 32)
         res["rc"] = lib.mi355x_sd_row_stats(x.data_ptr(), rows, C, C + 8, EPS, y.data_ptr(), st)
         torch.cuda.synchronize()
+        res["sha"] = {"stats": sha(y)}
         ref, e = NB.row_stats(vals, EPS, NB.chain_rows("row_stats", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e, u_out=0.0)
         res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY32)
@@ -343,6 +348,7 @@ def run_case(name):
         y, bits, inside = _canary((rows, C), C + 8, 16)
         res["rc"] = lib.mi355x_sd_rmsnorm(x.data_ptr(), rows, C, C + 24, w.data_ptr(), 1e-6, y.data_ptr(), C + 8, st)
         torch.cuda.synchronize()
+        res["sha"] = {"y": sha(y)}
         ref, e = NB.rmsnorm(vals, w, 1e-6, NB.chain_rows("rmsnorm", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
         res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
@@ -358,6 +364,7 @@ def run_case(name):
         res["rc"] = lib.mi355x_sd_adaln_ex(x.data_ptr(), rows, C, C + 8, sc.data_ptr(), sh.data_ptr(), sc.stride(0),
                                            _lib.MOD_ELEM if s["m16"] else _lib.MOD_F32, rpb, 1e-6, y.data_ptr(), C + 8, st)
         torch.cuda.synchronize()
+        res["sha"] = {"y": sha(y)}
         ref, e = NB.adaln(vals, sc, sh, rpb, 1e-6, NB.chain_rows("adaln", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
         res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
@@ -378,6 +385,9 @@ def run_case(name):
         res["rc"] = lib.mi355x_sd_adaln_f8(x.data_ptr(), rows, C, C + 8, sc.data_ptr(), sh.data_ptr(), sc.stride(0), rpb, 1e-6,
                                            y8.data_ptr(), C + 16, qs.data_ptr(), l2.data_ptr() if l2 is not None else None, st)
         torch.cuda.synchronize()
+        res["sha"] = {"y8": sha(y8), "yscale": sha(qs)}
+        if l2 is not None:
+            res["sha"]["yl2"] = sha(l2)
         ref, e = NB.adaln_pre(vals, sc, sh, rpb, 1e-6, NB.chain_rows("adaln_f8", C))
         r_val, r_qs, r_l2, nan = NB.check_f8(y8, qs[:, 0], l2[:, 0] if l2 is not None else None, ref, e)
         res["ratio"], res["ratio_qs"], res["ratio_l2"], res["nan_bytes"] = r_val, r_qs, r_l2, nan
@@ -401,6 +411,7 @@ def run_case(name):
         qs, qbits, qin = _canary((rows, 1), 1, 32)
         res["rc"] = lib.mi355x_sd_quantize_rows(xp, rows, C, ldx, rpb, bst, y8.data_ptr(), C + 8, qs.data_ptr(), st)
         torch.cuda.synchronize()
+        res["sha"] = {"y8": sha(y8), "yscale": sha(qs)}
         q_ref, qs_ref = NB.quantize_rows_exact(vals)
         got = y8.contiguous().cpu()
         res["exact_bytes_off"] = int((got != q_ref).sum().item())
@@ -427,6 +438,7 @@ def run_case(name):
             _lib.MOD_ELEM if s["m16"] else _lib.MOD_F32, rpb, ops._p(w), ops._p(b), EPS, rows, C, resi.data_ptr(), C + 8,
             y.data_ptr(), C + 24, st)
         torch.cuda.synchronize()
+        res["sha"] = {"resi": sha(resi), "out": sha(y)}
         rref, re_ = NB.fused_resi(xv, mv, gate, rpb)
         res["ratio_resi"], _ = NB.check(resi, rref, re_)
         ref, e = NB.fused_adaln_out(resi.float(), sc, sh, rpb, w, b, EPS, NB.chain_rows("fused_adaln", C))

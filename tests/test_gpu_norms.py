@@ -17,11 +17,11 @@ INSTANTIATIONS = (
     ["gn_partial 0 0 x16", "gn_partial 0 0 xf32", "gn_finalize 0 0 -"]                              # gn_partial_kernel<XF32>, gn_finalize_kernel
     + [f"scale_shift_act 0 0 {a},{x}" for a in ("silu", "id") for x in ("x16", "xf32")]              # scale_shift_act_kernel<SILU, XF32>
     + ["gn_fused 0 0 silu", "gn_fused 0 0 id"]                                                        # gn_fused_kernel<SILU>
-    + [f"layernorm {n} 2 {x}" for n in (2, 3, 5) for x in ("x16", "xf32")]                            # layernorm_kernel<NCH, 2, XF32>
-    + [f"row_stats {n} 4 -" for n in (1, 2, 3, 5)]                                                    # row_stats_kernel<NCH, 4>
+    + [f"layernorm {n} 2 {x}" for n in (2, 3, 5) for x in ("x16", "xf32")]                            # row_norm_kernel<LayerNormRows<XF32>, NCH, 2>
+    + [f"row_stats {n} 4 -" for n in (1, 2, 3, 5)]                                                    # row_norm_kernel<RowStats, NCH, 4>
     + [f"rmsnorm {n} 2 -" for n in (2, 4, 8)]                                                         # rmsnorm_kernel<NCH, 2>
-    + [f"adaln {n} {r} {m}" for n, r in ((2, 4), (3, 4), (5, 2)) for m in ("m16", "m32")]             # adaln_kernel<NCH, ROWS, M16>
-    + [f"adaln_f8 {n} 1 -" for n in (2, 3, 5)]                                                        # adaln_f8_kernel<NCH>
+    + [f"adaln {n} {r} {m}" for n, r in ((2, 4), (3, 4), (5, 2)) for m in ("m16", "m32")]             # row_norm_kernel<AdaLNRows<M16>, NCH, ROWS>
+    + [f"adaln_f8 {n} 1 -" for n in (2, 3, 5)]                                                        # row_norm_kernel<AdaLNF8Rows, NCH, 1>
     + ["quantize_rows 0 1 -"]                                                                         # quantize_rows_kernel
     + [f"fused_adaln {n} 1 {m}" for n in (2, 4, 8) for m in ("m16", "m32")])                          # fused_adaln_scale_residual_kernel<NCH, M16>
 

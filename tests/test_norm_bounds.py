@@ -22,7 +22,7 @@ def fma32(a, b, c):
     return (a.double() * b.double() + c.double()).to(F32)
 
 
-# ---- row kernels (layernorm_kernel, row_stats_kernel, adaln_kernel, fused_adaln_scale_residual_kernel) -------------------------
+# ---- row kernels (row_norm_kernel's forms: LayerNormRows, RowStats, AdaLNRows; fused_adaln_scale_residual_kernel) ----------------
 def row_moments(x, n_ch, fault=None):
     """x fp32 [rows, C]: (mean, rstd-input var) of the shifted one-pass statistics: lane l owns chunks l + 64 i (i < NCH), chains
     of 8 per chunk in order, then the butterfly over 64 lanes; fault: unshifted | drop_last"""
