@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 17
+#define MI355X_SD_ABI_VERSION 18
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -550,6 +550,34 @@ int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float*
 int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* out,
                                const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                                void* stream);
+
+/* One model evaluation of a two-stage, second-order step (HeunDiscreteScheduler, "Heun": an Euler step, then Heun's correction from
+ * the same start; 2n - 1 evaluations for n steps) in one launch: guidance combine, guidance rescale, the derivative and the update.
+ * `sample` (S) and `deriv` (D) are two caller-owned planes of batch * per_sample fp32 values that hold the step's state between
+ * its two launches. Per element, with e the guided (and rescaled) model output as in mi355x_sd_multistep_update:
+ *   d = p*x + q*e                                  p == 0: d = q*e, the product with x is not formed
+ *   second == 0:  out = x + h*d                    S <- x (bit copy), D <- d; S and D are NOT read
+ *   second != 0:  out = S + h*(g*D + d)            g == 0: D is NOT read; S and D are NOT written
+ * Rules:
+ *  - coef is 5 fp32 values (p, q, h, g, second) in device memory, read by the kernel (HeunDiscreteScheduler.heun_coefficients): a
+ *    captured graph of one node replays a whole loop, both stages, with only the row changing and S / D at fixed addresses.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - second, p == 0 and g == 0 are wave-uniform branches on the device values. State a stage does not need is not dereferenced:
+ *    neither plane needs initialising before the first stage-1 launch, and stale or NaN contents cannot reach out. g weights the
+ *    parked derivative: Heun's average uses 1 (h carries the 1/2); a midpoint method uses 0 and never reads D.
+ *  - operation order: as written above; which product contracts into which sum is the compiler's choice, as in
+ *    mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when x, sample, deriv, out and the eps planes are 16-byte aligned, and a scalar tail.
+ *    No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap of out, sample or deriv with each other, x, eps_uncond, eps_text or coef is
+ *    MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, sample, deriv, out or coef, batch <= 0, per_sample < 1,
+ *    and per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* eps_text, float* sample, float* deriv, float* out,
+                          const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                          void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

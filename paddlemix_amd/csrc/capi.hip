@@ -682,6 +682,22 @@ int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const fl
                                         batch, (long)per_sample, S(stream)), who);
 }
 
+int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* eps_text, float* sample, float* deriv, float* out,
+                          const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                          void* stream) {
+  const char* who = "mi355x_sd_heun_update";
+  if (!x || !eps_uncond || !sample || !deriv || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {sample, bytes}, {deriv, bytes}},
+                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 5 * sizeof(float)}}, {{0, 0}},
+                               "%s: out may be x itself; out, sample and deriv must not overlap each other, the inputs or coef in any "
+                               "other way"))
+    return rc;
+  return finish(launch_heun_update(x, eps_uncond, eps_text, sample, deriv, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
+                                   batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

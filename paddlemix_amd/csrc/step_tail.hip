@@ -1,7 +1,8 @@
 // The fused step tails (gfx950): the guidance combine, the guidance rescale and one scheduler step in one launch over the fp32 latents.
 //
-// One skeleton, four step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
-// multistep), UniPCStep, AncestralStep (Euler a) -- that holds the operand pointers of its step and states its arithmetic once:
+// One skeleton, five step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
+// multistep), UniPCStep, AncestralStep (Euler a), HeunStep (Heun: two stages) -- that holds the operand pointers of its step and
+// states its arithmetic once:
 //   operands            the leading members, filled by the public launcher (aggregate initialisation; the rest is set on the device)
 //   FLAT                whether the form has an elementwise kernel here (LinearStep: no, see there)
 //   vector_ok()         host: the operands allow the 16-byte vector loop (alignment, and whatever else the form needs)
@@ -19,7 +20,8 @@
 // Reference semantics:
 //   guidance combine, rescale_noise_cfg  ppdiffusers/ppdiffusers/pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-80, 882-891
 //   the steps                            schedulers/scheduling_euler_discrete.py, scheduling_ddim.py, scheduling_dpmsolver_multistep.py,
-//                                        scheduling_unipc_multistep.py, scheduling_euler_ancestral_discrete.py
+//                                        scheduling_unipc_multistep.py, scheduling_euler_ancestral_discrete.py,
+//                                        scheduling_heun_discrete.py
 #include "common.h"
 #include "kernels.h"
 
@@ -442,6 +444,90 @@ struct AncestralStep {
 int launch_ancestral_update(const float* x, const float* eu, const float* et, const float* noise, float* out, const float* coef,
                             float gs, float gr, int batch, long per_sample, hipStream_t stream) {
   return launch_step(AncestralStep{x, noise, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
+}
+
+// One model evaluation of a two-stage, second-order step (HeunDiscreteScheduler: an Euler step, then Heun's correction from the same
+// start) in one launch: the guidance combine, the guidance rescale, the derivative and the update. The step's state lives in two
+// caller-owned planes: S (the sample the step started from) and D (the derivative there). With coef = (p, q, h, g, second) in device
+// memory, per element and IN THIS ORDER (tests/heun_bounds.py derives its bound from it; which product fuses with which sum is the
+// compiler's choice, as in multistep_elem):
+//   e   = the guided (and rescaled) model output, as in the ancestral step
+//   d   = p * x + q * e                          p == 0 (epsilon prediction): d = q * e, the product with x is not formed
+//   second == 0 (stage 1):  out = x + h * d      S <- x (bit copy), D <- d; S and D are NOT read
+//   second != 0 (stage 2):  m   = g * D + d      g == 0: m = d and D is NOT read; g == 1 (Heun): the product is exact
+//                           out = S + h * m      S and D are NOT written
+// second, p == 0 and g == 0 are uniform branches on the device values, set once in load(): one captured node replays both stages with
+// only the row changing. State a stage does not need never enters the arithmetic -- the S / D of a fresh loop are uninitialised, and
+// 0 * NaN would poison the latents; stage 2 at p == 0 does not read x either. g weights the parked derivative: Heun's average takes
+// 1 (h carries the 1 / 2); a midpoint method (KDPM2) would take 0 and never read D. x is read and out written by the same lane in the
+// last pass only: out may be x. S and D are touched by that same lane at the same element; they overlap nothing else.
+struct HeCoef {
+  float p, q, h, g, second;
+};
+
+__device__ __forceinline__ void heun_elem(const HeCoef& k, bool second, bool px, bool gd, float x, float e, float S, float D, float& o,
+                                          float& d) {
+  d = px ? k.p * x + k.q * e : k.q * e;
+  if (!second) {
+    o = x + k.h * d;
+  } else {
+    const float m = gd ? k.g * D + d : d;
+    o = S + k.h * m;
+  }
+}
+
+struct HeunStep {
+  static constexpr bool FLAT = true;
+  const float* x;
+  float *sample, *deriv, *out;
+  HeCoef k;
+  bool second, px, gd, rx;   // stage 2; p != 0; stage 2 reads D; x is read (stage 1, or p != 0)
+
+  bool vector_ok() const { return !((ptr_bits(x) | ptr_bits(sample) | ptr_bits(deriv) | ptr_bits(out)) & 15); }
+  __device__ __forceinline__ void load(const float* __restrict__ c) {
+    k = {c[0], c[1], c[2], c[3], c[4]};
+    second = k.second != 0.0f;
+    px = k.p != 0.0f;
+    gd = second && k.g != 0.0f;
+    rx = !second || px;
+  }
+  __device__ __forceinline__ void to_sample(long base) { x += base, sample += base, deriv += base, out += base; }
+  __device__ __forceinline__ void elem(long i, float e) const {
+    const float xv = rx ? x[i] : 0.f;
+    float o, d;
+    heun_elem(k, second, px, gd, xv, e, second ? sample[i] : 0.f, gd ? deriv[i] : 0.f, o, d);
+    out[i] = o;
+    if (!second) {
+      sample[i] = xv;
+      deriv[i] = d;
+    }
+  }
+  template <class E>
+  __device__ __forceinline__ void vec(long i, E&& guided) const {
+    f32x4 *s4 = reinterpret_cast<f32x4*>(sample), *d4 = reinterpret_cast<f32x4*>(deriv);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 xv = zero, Sv = zero, Dv = zero, ov, dv;
+    if (rx) xv = reinterpret_cast<const f32x4*>(x)[i];
+    const f32x4 ev = guided();
+    if (second) Sv = s4[i];
+    if (gd) Dv = d4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float o, d;
+      heun_elem(k, second, px, gd, xv[j], ev[j], Sv[j], Dv[j], o, d);
+      ov[j] = o, dv[j] = d;
+    }
+    reinterpret_cast<f32x4*>(out)[i] = ov;
+    if (!second) {
+      s4[i] = xv;
+      d4[i] = dv;
+    }
+  }
+};
+
+int launch_heun_update(const float* x, const float* eu, const float* et, float* sample, float* deriv, float* out, const float* coef,
+                       float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  return launch_step(HeunStep{x, sample, deriv, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
 }
 
 }  // namespace sd

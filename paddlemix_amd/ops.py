@@ -407,6 +407,24 @@ def ancestral_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     return out
 
 
+def heun_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], sample: Tensor, deriv: Tensor, coef: Tensor,
+                guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One model evaluation of a Heun step in one launch -> out; ``sample`` and ``deriv`` (the step's parked state S and D) are
+    updated IN PLACE by stage 1 and only read by stage 2. x, eps_uncond, eps_text (None: no guidance), sample, deriv: contiguous fp32
+    [B, ...] of one shape; coef: fp32 GPU (p, q, h, g, second) of ``HeunDiscreteScheduler.heun_coefficients``. With e the guided
+    (and, with guidance_rescale > 0, rescaled) model output and d = p x + q e: second == 0: out = x + h d, S = x, D = d (neither is
+    read); second != 0: out = S + h (g D + d) (g == 0 does not read D; neither is written). out may be x."""
+    lib = _lib.load()
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (sample, "sample", False),
+                   (deriv, "deriv", False), (out, "out", True)), coef, 5,
+               "coef: expected a contiguous fp32 GPU tensor (p, q, h, g, second)", eps_text is not None and guidance_rescale > 0.0)
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_heun_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), sample.data_ptr(), deriv.data_ptr(),
+                                    out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
+                                    x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
                  guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
     """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),

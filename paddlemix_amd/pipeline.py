@@ -157,7 +157,23 @@ class _AncestralTail(_FusedTail):
                                                    stream)
 
 
-_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _LinearTail)   # in priority order: the first whose walk the scheduler has
+class _HeunTail(_FusedTail):
+    """``heun_coefficients`` (Heun): one launch per model evaluation, 2n - 1 for n steps; (p, q, h, g, second) = row i of a table
+    [2n - 1, 5] over the scheduler's WHOLE schedule (even rows: stage 1, odd rows: stage 2), ``scales`` as in _LinearTail. The tail
+    owns the step's parked sample and derivative; stage 1 writes them without reading, so fresh ones are not initialised, and their
+    pointers stay fixed for the whole loop"""
+
+    walk, whole_schedule, entry = "heun_coefficients", True, "mi355x_sd_heun_update"
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:
+            self.history = (torch.empty_like(lat), torch.empty_like(lat))
+        sample, deriv = self.history
+        return self.lib.mi355x_sd_heun_update(lat.data_ptr(), eps, eps_text, sample.data_ptr(), deriv.data_ptr(), out.data_ptr(),
+                                              self.coef.data_ptr() + 20 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0], stream)
+
+
+_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _LinearTail)   # in priority order: the first whose walk the scheduler has
 
 
 class _VaeSwitches:

@@ -10,6 +10,7 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
   LCMScheduler                       scheduling_lcm.py:140 (set_timesteps :330-466, step :476-566) -- 2-8 step latent-consistency sampling
   UniPCMultistepScheduler            scheduling_unipc_multistep.py:31 (predictor :438-565, corrector :567-701, step :720-804), orders 1-3
   EulerAncestralDiscreteScheduler    scheduling_euler_ancestral_discrete.py:130 (set_timesteps :210-250, step :268-363) -- "Euler a"
+  HeunDiscreteScheduler              scheduling_heun_discrete.py:71 (set_timesteps :213-277, step :349-455) -- "Heun", order 2
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
@@ -23,6 +24,8 @@ entries: ``UniPCMultistepScheduler.unipc_coefficients`` returns its 12 scalars f
 The ancestral Euler step is linear in the sample, the model output and the step's noise:
 ``EulerAncestralDiscreteScheduler.ancestral_coefficients`` returns (a, b, c) with  prev = a*sample + b*model_output + c*noise  for the
 library's ``mi355x_sd_ancestral_update``; the noise stays a host draw (``torch.randn`` from the call's generator).
+The Heun step has two stages, each linear in the sample, the model output and the state the first stage parks (the sample and the
+derivative): ``HeunDiscreteScheduler.heun_coefficients`` returns (p, q, h, g, second) for the library's ``mi355x_sd_heun_update``.
 """
 from __future__ import annotations
 
@@ -554,6 +557,200 @@ class EulerAncestralDiscreteScheduler:
         prev = prev + noise * s_up
         self._step_index += 1
         return _out(prev, return_dict, pred_original_sample=x0)
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class HeunDiscreteScheduler:
+    """"Heun" (scheduling_heun_discrete.py:71-480): the second-order k-diffusion sampler, two model evaluations per step. Every
+    timestep but the first appears twice; the first evaluation of a pair takes an Euler step and parks the sample, the derivative and
+    dt, the second averages the two derivatives and steps again from the parked sample; the last step (to sigma = 0) is a plain Euler
+    step. epsilon, v_prediction and sample prediction, the three spacings, Karras sigmas, ``clip_sample``; ``trained_betas`` is not
+    implemented. Both stages are linear in the current sample, the model output and the parked state: ``heun_coefficients`` returns
+    (p, q, h, g, second) for the library's ``mi355x_sd_heun_update``."""
+    order = 2
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "linear", trained_betas=None, prediction_type: str = "epsilon",
+                 use_karras_sigmas: bool = False, clip_sample: bool = False, clip_sample_range: float = 1.0,
+                 timestep_spacing: str = "linspace", steps_offset: int = 0):
+        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        if trained_betas is not None:
+            raise NotImplementedError("HeunDiscreteScheduler(mi355x): trained_betas is not implemented")
+        # the training table in float32 TENSOR arithmetic, as the reference builds it (:128-146) and as
+        # EulerAncestralDiscreteScheduler does here (see there for what the float64 linspace of _make_betas costs)
+        if beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{beta_schedule} does is not implemented for {self.__class__}")
+        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
+        self.alphas_cumprod = alphas_cumprod.numpy()
+        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
+        self.use_karras_sigmas = use_karras_sigmas
+        self.set_timesteps(num_train_timesteps)   # "set all values" (:149)
+
+    @property
+    def init_noise_sigma(self):
+        m = np.float32(self.sigmas.max())
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return float(m)
+        return float(np.sqrt(m * m + np.float32(1.0)))   # float32, as the reference's tensor expression (max ** 2 + 1) ** 0.5
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def state_in_first_order(self):
+        return self.dt is None
+
+    coefficient_walk = _coefficient_walk("_step_index", "dt")   # (heun_coefficients, model_input_scale)
+
+    def set_timesteps(self, num_inference_steps: int):
+        c, T = self.config, self.config.num_train_timesteps
+        self.num_inference_steps = n = num_inference_steps
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        sig_all = np.array(self._train_sigmas)
+        log_sig = np.log(sig_all)
+        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
+        if c.use_karras_sigmas:   # (:304-327; the timesteps are not rounded)
+            rho = 7.0
+            lo, hi = sig[-1].item() ** (1 / rho), sig[0].item() ** (1 / rho)
+            sig = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
+            ts = np.array([EulerDiscreteScheduler._sigma_to_t(s, log_sig) for s in sig])
+        sig = np.concatenate([sig, [0.0]]).astype(np.float32)
+        ts = ts.astype(np.float32)
+        # [s0, s1, s1, ..., s_{n-1}, s_{n-1}, 0] and [t0, t1, t1, ..., t_{n-1}, t_{n-1}]: 2n sigmas, 2n - 1 timesteps
+        self.sigmas = np.concatenate([sig[:1], np.repeat(sig[1:-1], 2), sig[-1:]])
+        self.timesteps = np.concatenate([ts[:1], np.repeat(ts[1:], 2)])
+        self.prev_derivative = self.dt = self.sample = None
+        self._step_index: Optional[int] = None
+        self._index_counter = {}
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        """(:154-170) before any step: the second of two matching indices (the only one if single); afterwards the one the
+        counter of ``step`` calls at this timestep points to"""
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        t = float(timestep)
+        idx = np.nonzero(np.asarray(ts) == np.float32(t))[0]
+        if len(self._index_counter) == 0:
+            pos = 1 if len(idx) > 1 else 0
+        else:
+            pos = self._index_counter.setdefault(t, 0)
+        return int(idx[pos])
+
+    _init_step_index = EulerDiscreteScheduler._init_step_index
+
+    def _sigma(self, i, dtype):
+        """sigmas[i] as a 0-dim tensor of `dtype`: the reference casts its sigma tensor to the model output's dtype (:376-377), so the
+        scalar expressions of ``step`` are rounded in that dtype"""
+        return torch.tensor(float(self.sigmas[i]), dtype=dtype)
+
+    def scale_model_input(self, sample, timestep):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = self._sigma(self._step_index, sample.dtype)
+        return sample / ((sigma ** 2 + 1) ** 0.5)
+
+    def model_input_scale(self, timestep) -> float:
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return 1.0 / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
+
+    def _check(self, timestep):
+        pt = self.config.prediction_type
+        if pt not in ("epsilon", "v_prediction", "sample"):
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+
+    def heun_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
+        """(p, q, h, g, second): the row of the step ``step`` would take now, composed in float64 from the float32 sigmas; advances the
+        index and the stage (``dt``) as ``step`` does. With d = p*sample + q*model_output,
+          second == 0 (first order):  prev = sample + h*d, and the launch parks sample and d           h = dt = sigma_next - sigma
+          second == 1 (Heun):         prev = parked sample + h*(g*parked d + d)                        h = dt / 2 of the parked dt, g = 1
+        g weights the parked derivative: Heun's average takes 1; a midpoint method (KDPM2) would take 0 and never read it.
+        ``clip_sample`` is not linear, a non-finite row has no such form: NotImplementedError."""
+        self._check(timestep)
+        if self.config.clip_sample:
+            raise NotImplementedError("clip_sample has no linear-update form")
+        i, first = self._step_index, self.dt is None
+        if first:
+            s, s_next = float(self.sigmas[i]), float(self.sigmas[i + 1])
+            s_in, h, g, second = s, s_next - s, 0.0, 0.0
+            self.dt = h
+        else:
+            s_in, h, g, second = float(self.sigmas[i]), float(self.dt) / 2, 1.0, 1.0
+            self.dt = None
+        self._step_index += 1
+        pt = self.config.prediction_type
+        with np.errstate(all="ignore"):
+            s_in = np.float64(s_in)
+            if pt == "epsilon":
+                p, q = 0.0, 1.0
+            elif pt == "v_prediction":
+                # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+                p, q = float(s_in / (s_in ** 2 + 1)), float(1.0 / (s_in ** 2 + 1) ** 0.5)
+            else:
+                p, q = float(1.0 / s_in), float(-1.0 / s_in)
+        if not all(np.isfinite(v) for v in (p, q, h)):
+            raise NotImplementedError("a non-finite row has no linear-update form")
+        return p, q, h, g, second
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        """(:349-455) line by line; the sigmas enter as 0-dim tensors of the model output's dtype"""
+        self._check(timestep)
+        t = float(timestep)
+        self._index_counter[t] = self._index_counter.get(t, 0) + 1
+        i, dtype, c = self._step_index, model_output.dtype, self.config
+        first = self.state_in_first_order
+        if first:
+            sigma, sigma_next = self._sigma(i, dtype), self._sigma(i + 1, dtype)
+        else:   # 2nd order / Heun's method
+            sigma, sigma_next = self._sigma(i - 1, dtype), self._sigma(i, dtype)
+        sigma_hat = sigma   # gamma = 0
+        sigma_input = sigma_hat if first else sigma_next
+        if c.prediction_type == "epsilon":
+            x0 = sample - sigma_input * model_output
+        elif c.prediction_type == "v_prediction":
+            x0 = model_output * (-sigma_input / (sigma_input ** 2 + 1) ** 0.5) + (sample / (sigma_input ** 2 + 1))
+        else:
+            x0 = model_output
+        if c.clip_sample:
+            x0 = x0.clip(-c.clip_sample_range, c.clip_sample_range)
+        if first:
+            derivative = (sample - x0) / sigma_hat
+            dt = sigma_next - sigma_hat
+            self.prev_derivative, self.dt, self.sample = derivative, dt, sample
+        else:
+            derivative = (sample - x0) / sigma_next
+            derivative = (self.prev_derivative + derivative) / 2
+            dt, sample = self.dt, self.sample
+            self.prev_derivative = self.dt = self.sample = None   # back in first-order mode
+        prev = sample + derivative * dt
+        self._step_index += 1
+        return _out(prev, return_dict)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """(:457-477) x + noise * sigma[index_for_timestep of each timestep]"""
+        ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps, dtype=np.float32))
+        idx = [self.index_for_timestep(t) for t in ts]
+        sigma = torch.as_tensor(np.asarray(self.sigmas, dtype=np.float32)[idx]).to(original_samples.device,
+                                                                                  original_samples.dtype)
+        while sigma.dim() < original_samples.dim():
+            sigma = sigma.unsqueeze(-1)
+        return original_samples + noise * sigma
 
     def __len__(self):
         return self.config.num_train_timesteps
