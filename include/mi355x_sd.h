@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 18
+#define MI355X_SD_ABI_VERSION 19
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -576,6 +576,39 @@ int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const fl
  *    MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, sample, deriv, out or coef, batch <= 0, per_sample < 1,
  *    and per_sample < 2 with guidance_rescale > 0. */
 int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* eps_text, float* sample, float* deriv, float* out,
+                          const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                          void* stream);
+
+/* One model evaluation of a two-stage midpoint step (KDPM2DiscreteScheduler, "DPM2": an Euler step to the midpoint sigma, then the whole
+ * step from the same start with the derivative found there; KDPM2AncestralDiscreteScheduler, "DPM2 a": the same, ending at sigma_down
+ * and adding noise of sigma_up; 2n - 1 evaluations for n steps) in one launch: guidance combine, guidance rescale, the derivative and
+ * the update. `sample` (S) is one caller-owned plane of batch * per_sample fp32 values that holds the step's start between its two
+ * launches; `noise` (z) is the caller's N(0, I) plane for this evaluation (the library draws nothing). Per element, with e the guided
+ * (and rescaled) model output as in mi355x_sd_multistep_update:
+ *   d = p*x + q*e                                  p == 0: d = q*e, the product with x is not formed
+ *   second == 0:  out = x + h*d                    S <- x (bit copy); S and noise are NOT read
+ *   second != 0:  out = S + h*d [+ c*z]            c == 0: the term is not formed and noise is NOT read; S is NOT written
+ * Rules:
+ *  - coef is 5 fp32 values (p, q, h, c, second) in device memory, read by the kernel (dpm2_coefficients of either scheduler): a
+ *    captured graph of one node replays a whole loop, both stages, with only the row and the contents of noise changing and S at a
+ *    fixed address.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - second, p == 0 and c == 0 are wave-uniform branches on the device values. State a stage does not need is not dereferenced: S
+ *    needs no initialising before the first stage-1 launch, and stale or NaN contents of S or noise cannot reach out where the row
+ *    does not use them. noise is read by a stage-2 row with c != 0 only (every stage-2 row of DPM2 a; no row of DPM2). The DEVICE
+ *    value decides: noise == NULL is accepted for a row the caller knows reads none, as in mi355x_sd_ancestral_update, and a host
+ *    that replays one captured launch over both kinds of row keeps passing its plane.
+ *  - operation order: as written above, the noise term added last; which product contracts into which sum is the compiler's choice,
+ *    as in mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when x, noise (NULL counts as aligned), sample, out and the eps planes are 16-byte
+ *    aligned, and a scalar tail. No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap of out or sample with each other, x, eps_uncond, eps_text, noise or coef is
+ *    MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, sample, out or coef, batch <= 0, per_sample < 1, and
+ *    per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_dpm2_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* sample, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream);
 

@@ -698,6 +698,22 @@ int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* 
                                    batch, (long)per_sample, S(stream)), who);
 }
 
+int mi355x_sd_dpm2_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* sample, float* out,
+                          const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                          void* stream) {
+  const char* who = "mi355x_sd_dpm2_update";
+  if (!x || !eps_uncond || !sample || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);   // (noise: see the header)
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {sample, bytes}},
+                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {noise, bytes}, {coef, 5 * sizeof(float)}}, {{0, 0}},
+                               "%s: out may be x itself; out and sample must not overlap each other, the inputs, noise or coef in any "
+                               "other way"))
+    return rc;
+  return finish(launch_dpm2_update(x, eps_uncond, eps_text, noise, sample, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
+                                   batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

@@ -1,8 +1,8 @@
 // The fused step tails (gfx950): the guidance combine, the guidance rescale and one scheduler step in one launch over the fp32 latents.
 //
-// One skeleton, five step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
-// multistep), UniPCStep, AncestralStep (Euler a), HeunStep (Heun: two stages) -- that holds the operand pointers of its step and
-// states its arithmetic once:
+// One skeleton, six step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
+// multistep), UniPCStep, AncestralStep (Euler a), HeunStep (Heun: two stages), MidpointStep (DPM2 and DPM2 a: two stages, the second
+// with noise) -- that holds the operand pointers of its step and states its arithmetic once:
 //   operands            the leading members, filled by the public launcher (aggregate initialisation; the rest is set on the device)
 //   FLAT                whether the form has an elementwise kernel here (LinearStep: no, see there)
 //   vector_ok()         host: the operands allow the 16-byte vector loop (alignment, and whatever else the form needs)
@@ -21,7 +21,8 @@
 //   guidance combine, rescale_noise_cfg  ppdiffusers/ppdiffusers/pipelines/stable_diffusion/pipeline_stable_diffusion.py:69-80, 882-891
 //   the steps                            schedulers/scheduling_euler_discrete.py, scheduling_ddim.py, scheduling_dpmsolver_multistep.py,
 //                                        scheduling_unipc_multistep.py, scheduling_euler_ancestral_discrete.py,
-//                                        scheduling_heun_discrete.py
+//                                        scheduling_heun_discrete.py, scheduling_k_dpm_2_discrete.py,
+//                                        scheduling_k_dpm_2_ancestral_discrete.py
 #include "common.h"
 #include "kernels.h"
 
@@ -528,6 +529,79 @@ struct HeunStep {
 int launch_heun_update(const float* x, const float* eu, const float* et, float* sample, float* deriv, float* out, const float* coef,
                        float gs, float gr, int batch, long per_sample, hipStream_t stream) {
   return launch_step(HeunStep{x, sample, deriv, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
+}
+
+// One model evaluation of a two-stage midpoint step (KDPM2DiscreteScheduler, "DPM2": an Euler step to the midpoint sigma, then the
+// whole step from the same start with the derivative found there; KDPM2AncestralDiscreteScheduler, "DPM2 a": the same, ending lower
+// and adding fresh noise) in one launch: the guidance combine, the guidance rescale, the derivative and the update. The step's state
+// is ONE caller-owned plane, S (the sample the step started from): a midpoint method never reads the first derivative again, so
+// stage 1 writes a plane fewer than HeunStep. With coef = (p, q, h, c, second) in device memory and z the noise plane the host drew,
+// per element and IN THIS ORDER (tests/dpm2_bounds.py derives its bound from it; which product fuses with which sum is the compiler's
+// choice, as in multistep_elem):
+//   e   = the guided (and rescaled) model output, as in the ancestral step
+//   d   = p * x + q * e                          p == 0 (epsilon prediction): d = q * e, the product with x is not formed
+//   second == 0 (stage 1):  out = x + h * d      S <- x (bit copy); S and noise are NOT read
+//   second != 0 (stage 2):  out = S + h * d      S is NOT written
+//                           out = out + c * z    only if c != 0 (DPM2 a); c == 0: noise is NOT read
+// second, p == 0 and c == 0 are uniform branches on the device values, set once in load(): one captured node replays both stages with
+// only the row changing. State a stage does not need never enters the arithmetic -- the S of a fresh loop is uninitialised, a noise
+// plane may be stale or null where c == 0, and 0 * NaN would poison the latents; stage 2 at p == 0 does not read x either. The noise
+// counts in stage 2 only: a stage-1 row never reads it, whatever its c. x is read and out written by the same lane in the last pass
+// only: out may be x. S is touched by that same lane at the same element; it overlaps nothing else.
+struct MpCoef {
+  float p, q, h, c, second;
+};
+
+__device__ __forceinline__ float midpoint_elem(const MpCoef& k, bool second, bool px, bool noisy, float x, float e, float S, float z) {
+  const float d = px ? k.p * x + k.q * e : k.q * e;
+  float o = (second ? S : x) + k.h * d;
+  if (noisy) o += k.c * z;
+  return o;
+}
+
+struct MidpointStep {
+  static constexpr bool FLAT = true;
+  const float *x, *noise;
+  float *sample, *out;
+  MpCoef k;
+  bool second, px, noisy, rx;   // stage 2; p != 0; stage 2 adds c z; x is read (stage 1, or p != 0)
+
+  bool vector_ok() const { return !((ptr_bits(x) | ptr_bits(noise) | ptr_bits(sample) | ptr_bits(out)) & 15); }
+  __device__ __forceinline__ void load(const float* __restrict__ c) {
+    k = {c[0], c[1], c[2], c[3], c[4]};
+    second = k.second != 0.0f;
+    px = k.p != 0.0f;
+    noisy = second && k.c != 0.0f;
+    rx = !second || px;
+  }
+  __device__ __forceinline__ void to_sample(long base) {
+    x += base, sample += base, out += base;
+    if (noisy) noise += base;   // (never formed from a null pointer)
+  }
+  __device__ __forceinline__ void elem(long i, float e) const {
+    const float xv = rx ? x[i] : 0.f;
+    out[i] = midpoint_elem(k, second, px, noisy, xv, e, second ? sample[i] : 0.f, noisy ? noise[i] : 0.f);
+    if (!second) sample[i] = xv;
+  }
+  template <class E>
+  __device__ __forceinline__ void vec(long i, E&& guided) const {
+    f32x4* s4 = reinterpret_cast<f32x4*>(sample);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 xv = zero, Sv = zero, zv = zero, ov;
+    if (rx) xv = reinterpret_cast<const f32x4*>(x)[i];
+    const f32x4 ev = guided();
+    if (second) Sv = s4[i];
+    if (noisy) zv = reinterpret_cast<const f32x4*>(noise)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = midpoint_elem(k, second, px, noisy, xv[j], ev[j], Sv[j], zv[j]);
+    reinterpret_cast<f32x4*>(out)[i] = ov;
+    if (!second) s4[i] = xv;
+  }
+};
+
+int launch_dpm2_update(const float* x, const float* eu, const float* et, const float* noise, float* sample, float* out,
+                       const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  return launch_step(MidpointStep{x, noise, sample, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
 }
 
 }  // namespace sd

@@ -425,6 +425,24 @@ def heun_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], sampl
     return out
 
 
+def dpm2_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise: Optional[Tensor], sample: Tensor, coef: Tensor,
+                guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One model evaluation of a DPM2 / DPM2 a step in one launch -> out; ``sample`` (the step's parked start S) is updated IN PLACE
+    by stage 1 and only read by stage 2. x, eps_uncond, eps_text (None: no guidance), noise (None: DPM2, whose rows have c == 0),
+    sample: contiguous fp32 [B, ...] of one shape; coef: fp32 GPU (p, q, h, c, second) of ``dpm2_coefficients``. With e the guided
+    (and, with guidance_rescale > 0, rescaled) model output and d = p x + q e: second == 0: out = x + h d, S = x (neither S nor noise
+    is read); second != 0: out = S + h d + c noise (c == 0 does not read noise; S is not written). out may be x."""
+    lib = _lib.load()
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (noise, "noise", True), (sample, "sample", False),
+                   (out, "out", True)), coef, 5,
+               "coef: expected a contiguous fp32 GPU tensor (p, q, h, c, second)", eps_text is not None and guidance_rescale > 0.0)
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_dpm2_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), _p(noise), sample.data_ptr(), out.data_ptr(),
+                                    coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
+                                    x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
                  guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
     """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),

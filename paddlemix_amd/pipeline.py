@@ -11,6 +11,7 @@ stays outside: the loop starts from ``prompt_embeds``.
 """
 from __future__ import annotations
 
+import inspect
 from contextlib import nullcontext
 from typing import Callable, Dict, Optional
 
@@ -173,7 +174,43 @@ class _HeunTail(_FusedTail):
                                               self.coef.data_ptr() + 20 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0], stream)
 
 
-_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _LinearTail)   # in priority order: the first whose walk the scheduler has
+class _Dpm2Tail(_FusedTail):
+    """``dpm2_coefficients`` (DPM2, DPM2 a): one launch per model evaluation, 2n - 1 for n steps; (p, q, h, c, second) = row i of a
+    table [2n - 1, 5] over the scheduler's WHOLE schedule (even rows: stage 1, odd rows: stage 2), ``scales`` as in _LinearTail. The
+    tail owns the step's parked sample; stage 1 writes it without reading, so a fresh one is not initialised, and its pointer stays
+    fixed for the whole loop. For the ancestral class (its ``step`` takes a generator) z is drawn here, once per evaluation, by the
+    ``torch.randn`` call of that ``step`` from the call's generator -- one seed gives the same noise on both paths; after the first
+    evaluation the draw goes into the same buffer (``out=``: the same values, the same generator state), so the noise pointer stays
+    fixed too. Only the stage-2 rows read the plane. DPM2 draws nothing and passes a null noise (c = 0 on every row)"""
+
+    walk, whole_schedule, entry = "dpm2_coefficients", True, "mi355x_sd_dpm2_update"
+
+    def __init__(self, lib, emulated, coef, scales, noisy, generator):
+        super().__init__(lib, emulated, coef, scales)
+        self.noisy, self.generator, self.noise = noisy, generator, None
+
+    @classmethod
+    def build(cls, lib, emulated, coef, scales, scheduler, generator):
+        return cls(lib, emulated, coef, scales, "generator" in inspect.signature(scheduler.step).parameters, generator)
+
+    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
+        if self.noisy:
+            if self.noise is None:
+                self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32)
+            else:
+                torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32, out=self.noise)
+        return super().update(latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale)
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:
+            self.history = torch.empty_like(lat)
+        return self.lib.mi355x_sd_dpm2_update(lat.data_ptr(), eps, eps_text, self.noise.data_ptr() if self.noisy else None,
+                                              self.history.data_ptr(), out.data_ptr(), self.coef.data_ptr() + 20 * i, gs, gr,
+                                              lat.shape[0], lat.numel() // lat.shape[0], stream)
+
+
+# in priority order: the first whose walk the scheduler has
+_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _Dpm2Tail, _LinearTail)
 
 
 class _VaeSwitches:

@@ -11,6 +11,8 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
   UniPCMultistepScheduler            scheduling_unipc_multistep.py:31 (predictor :438-565, corrector :567-701, step :720-804), orders 1-3
   EulerAncestralDiscreteScheduler    scheduling_euler_ancestral_discrete.py:130 (set_timesteps :210-250, step :268-363) -- "Euler a"
   HeunDiscreteScheduler              scheduling_heun_discrete.py:71 (set_timesteps :213-277, step :349-455) -- "Heun", order 2
+  KDPM2DiscreteScheduler             scheduling_k_dpm_2_discrete.py:71 (set_timesteps :209-286, step :365-462) -- "DPM2", order 2
+  KDPM2AncestralDiscreteScheduler    scheduling_k_dpm_2_ancestral_discrete.py:72 (set_timesteps :210-296, step :373-478) -- "DPM2 a"
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
@@ -26,6 +28,8 @@ The ancestral Euler step is linear in the sample, the model output and the step'
 library's ``mi355x_sd_ancestral_update``; the noise stays a host draw (``torch.randn`` from the call's generator).
 The Heun step has two stages, each linear in the sample, the model output and the state the first stage parks (the sample and the
 derivative): ``HeunDiscreteScheduler.heun_coefficients`` returns (p, q, h, g, second) for the library's ``mi355x_sd_heun_update``.
+The DPM2 step is a midpoint method of the same two-stage shape that parks the sample alone, and its ancestral variant adds noise in
+the second stage: ``dpm2_coefficients`` of both classes returns (p, q, h, c, second) for the library's ``mi355x_sd_dpm2_update``.
 """
 from __future__ import annotations
 
@@ -754,6 +758,231 @@ class HeunDiscreteScheduler:
 
     def __len__(self):
         return self.config.num_train_timesteps
+
+
+class KDPM2DiscreteScheduler:
+    """"DPM2" (scheduling_k_dpm_2_discrete.py:71-487): the second-order k-diffusion midpoint sampler, two model evaluations per step.
+    The first evaluation of a step takes an Euler step to ``sigma_interpol``, the geometric mean of the step's two sigmas, and parks
+    the sample; the second is made there (its timestep comes from ``_sigma_to_t``) and takes the whole step from the parked sample
+    with the new derivative alone; the last step (to sigma = 0) is a plain Euler step. epsilon and v prediction, the three spacings,
+    ``steps_offset``, Karras sigmas; ``trained_betas`` and ``squaredcos_cap_v2`` are not implemented, ``prediction_type="sample"`` is
+    refused by ``step`` as the reference refuses it. Both stages are linear in the current sample, the model output and the parked
+    sample: ``dpm2_coefficients`` returns (p, q, h, c, second) for the library's ``mi355x_sd_dpm2_update``.
+
+    The tables are built in the reference's float32 tensor arithmetic; its ``Tensor.lerp`` is taken as ``torch.lerp``. ``step`` carries
+    ``sigmas`` as 0-dim tensors of the model output's dtype, as the reference's cast does; the reference leaves its other tables
+    (``sigmas_interpol``, and the ancestral class's ``sigmas_up`` / ``sigmas_down``) float32, and so does ``step`` -- but for a float64
+    model output, which takes them in float64 too (the float64 loops of the tests are this project's measuring stick)."""
+    order = 2
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 beta_schedule: str = "linear", trained_betas=None, use_karras_sigmas: bool = False,
+                 prediction_type: str = "epsilon", timestep_spacing: str = "linspace", steps_offset: int = 0):
+        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        if trained_betas is not None:
+            raise NotImplementedError(f"{self.__class__.__name__}(mi355x): trained_betas is not implemented")
+        # the training table in float32 TENSOR arithmetic, as HeunDiscreteScheduler builds it
+        if beta_schedule == "linear":
+            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        elif beta_schedule == "scaled_linear":
+            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        else:
+            raise NotImplementedError(f"{beta_schedule} does is not implemented for {self.__class__}")
+        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
+        self.alphas_cumprod = alphas_cumprod.numpy()
+        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
+        self.set_timesteps(num_train_timesteps, num_train_timesteps)   # "set all values" (:142)
+
+    init_noise_sigma = HeunDiscreteScheduler.init_noise_sigma
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def state_in_first_order(self):
+        return self.sample is None
+
+    coefficient_walk = _coefficient_walk("_step_index", "sample")   # (dpm2_coefficients, model_input_scale)
+
+    @staticmethod
+    def _tables(sig):
+        """the per-step tables beside the sigmas (:258-261), and which of their interpolated timesteps sit between the steps'"""
+        interpol = sig.log().lerp(sig.roll(1).log(), 0.5).exp()
+        interpol[-1] = 0.0
+        return dict(sigmas_interpol=interpol), slice(1, -1)
+
+    def _stage(self, i, first):
+        """float32 (sigma, sigma_interpol, the sigma stage 2 steps to, sigma_up) of the evaluation at index i (:400-409)"""
+        if first:
+            return self.sigmas[i], self.sigmas_interpol[i + 1], None, None
+        return self.sigmas[i - 1], self.sigmas_interpol[i], self.sigmas[i], None
+
+    def set_timesteps(self, num_inference_steps: int, num_train_timesteps: Optional[int] = None):
+        c, T = self.config, num_train_timesteps or self.config.num_train_timesteps
+        self.num_inference_steps = n = num_inference_steps
+        if c.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
+        elif c.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
+                             "'leading' or 'trailing'.")
+        sig_all = np.array(self._train_sigmas)
+        log_sig = np.log(sig_all)
+        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
+        if c.use_karras_sigmas:   # (here the timesteps ARE rounded, :252)
+            rho = 7.0
+            lo, hi = sig[-1].item() ** (1 / rho), sig[0].item() ** (1 / rho)
+            sig = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
+            ts = np.array([EulerDiscreteScheduler._sigma_to_t(s, log_sig) for s in sig]).round()
+        sig = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        # entries no evaluation reads go through log(0) and inf - inf on the way, as in the reference
+        tables, between = self._tables(sig)
+        for k, v in dict(tables, sigmas=sig).items():   # [v0, v1, v1, ..., vn, vn, vn]: 2n + 2 entries
+            setattr(self, k, torch.cat([v[:1], v[1:].repeat_interleave(2), v[-1:]]).numpy())
+        with np.errstate(all="ignore"):
+            # (one call over the array: the per-element arithmetic of the reference's loop over _sigma_to_t)
+            t_interpol = EulerDiscreteScheduler._sigma_to_t(tables["sigmas_interpol"].numpy(), log_sig).astype(np.float32)
+        ts = ts.astype(np.float32)
+        # [t0, t'0, t1, t'1, ..., t_{n-1}]: 2n - 1 timesteps, t'k the timestep of the sigma stage 2 of step k is evaluated at
+        self.timesteps = np.concatenate([ts[:1], np.stack((t_interpol[between], ts[1:]), axis=-1).reshape(-1)])
+        self.sample = None
+        self._step_index: Optional[int] = None
+        self._index_counter = {}
+
+    index_for_timestep = HeunDiscreteScheduler.index_for_timestep
+    _init_step_index = EulerDiscreteScheduler._init_step_index
+    add_noise = HeunDiscreteScheduler.add_noise
+
+    def _sigma_in(self):
+        """the float32 sigma the model is evaluated at now: ``sigmas`` in stage 1, ``sigmas_interpol`` in stage 2 (:200-204)"""
+        first = self.state_in_first_order
+        return self._stage(self._step_index, first)[0 if first else 1]
+
+    def scale_model_input(self, sample, timestep):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        sigma = torch.tensor(float(self._sigma_in()), dtype=torch.promote_types(torch.float32, sample.dtype))
+        return sample / ((sigma ** 2 + 1) ** 0.5)
+
+    def model_input_scale(self, timestep) -> float:
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return 1.0 / ((float(self._sigma_in()) ** 2 + 1) ** 0.5)
+
+    def _check_prediction_type(self):
+        pt = self.config.prediction_type
+        if pt == "sample":
+            raise NotImplementedError("prediction_type not implemented yet: sample")
+        if pt not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+
+    def dpm2_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
+        """(p, q, h, c, second): the row of the evaluation ``step`` would take now, composed in float64 from the float32 schedule
+        values ``step`` uses; advances the index and the stage as ``step`` does. With d = p*sample + q*model_output, the derivative
+        at the sigma the model was evaluated at,
+          second == 0:  prev = sample + h*d, and the launch parks sample             h = sigma_interpol - sigma
+          second == 1:  prev = parked sample + h*d [+ c*noise]                       h = sigma_next - sigma (DPM2), c = 0.0 exactly;
+                                                                                     h = sigma_down - sigma, c = sigma_up (DPM2 a)
+        A non-finite row has no such form: NotImplementedError."""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        self._check_prediction_type()
+        i, first = self._step_index, self.state_in_first_order
+        s, s_interpol, s_to, s_up = (None if v is None else float(v) for v in self._stage(i, first))
+        if first:
+            s_in, h, c, second = s, s_interpol - s, 0.0, 0.0
+            self.sample = _WALKED
+        else:
+            s_in, h, c, second = s_interpol, s_to - s, 0.0 if s_up is None else s_up, 1.0
+            self.sample = None
+        self._step_index += 1
+        with np.errstate(all="ignore"):
+            s_in = np.float64(s_in)
+            if self.config.prediction_type == "epsilon":
+                p, q = 0.0, 1.0
+            else:   # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+                p, q = float(s_in / (s_in ** 2 + 1)), float(1.0 / (s_in ** 2 + 1) ** 0.5)
+        if not all(np.isfinite(v) for v in (p, q, h, c)):
+            raise NotImplementedError("a non-finite row has no linear-update form")
+        return p, q, h, c, second
+
+    def _begin(self, timestep):
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        t = float(timestep)
+        self._index_counter[t] = self._index_counter.get(t, 0) + 1
+
+    def _advance(self, model_output, sample, noise, return_dict):
+        """(:411-462, ancestral :425-478) line by line from the prediction-type branch on"""
+        i, dtype, first = self._step_index, model_output.dtype, self.state_in_first_order
+        other = torch.promote_types(torch.float32, dtype)
+        s, s_interpol, s_to, s_up = self._stage(i, first)
+        sigma_hat = torch.tensor(float(s), dtype=dtype)   # gamma = 0
+        sigma_interpol = torch.tensor(float(s_interpol), dtype=other)
+        self._check_prediction_type()
+        sigma_input = sigma_hat if first else sigma_interpol
+        if self.config.prediction_type == "epsilon":
+            x0 = sample - sigma_input * model_output
+        else:
+            x0 = model_output * (-sigma_input / (sigma_input ** 2 + 1) ** 0.5) + (sample / (sigma_input ** 2 + 1))
+        if first:
+            derivative = (sample - x0) / sigma_hat
+            dt = sigma_interpol - sigma_hat
+            self.sample = sample   # store for 2nd order step
+            prev = sample + derivative * dt
+        else:   # DPM-Solver-2
+            derivative = (sample - x0) / sigma_interpol
+            dt = torch.tensor(float(s_to), dtype=other) - sigma_hat
+            sample, self.sample = self.sample, None
+            prev = sample + derivative * dt
+            if s_up is not None:
+                prev = prev + noise * torch.tensor(float(s_up), dtype=other)
+        self._step_index += 1
+        return _out(prev, return_dict)
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        self._begin(timestep)
+        return self._advance(model_output, sample, None, return_dict)
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class KDPM2AncestralDiscreteScheduler(KDPM2DiscreteScheduler):
+    """"DPM2 a" (scheduling_k_dpm_2_ancestral_discrete.py:72-504): KDPM2DiscreteScheduler whose steps end at ``sigma_down`` and add
+    fresh noise of ``sigma_up`` back, as Euler a's do. The midpoint lies between sigma and sigma_down; the noise enters in the second
+    evaluation of a step only, but ``step`` draws a plane at EVERY evaluation, as the reference does, so one seed leaves the generator
+    in the same state whichever path draws. ``dpm2_coefficients`` returns c = sigma_up on the second-stage rows."""
+
+    @staticmethod
+    def _tables(sig):
+        """(:259-268)"""
+        sig_next = sig.roll(-1)
+        sig_next[-1] = 0.0
+        up = (sig_next ** 2 * (sig ** 2 - sig_next ** 2) / sig ** 2) ** 0.5
+        down = (sig_next ** 2 - up ** 2) ** 0.5
+        down[-1] = 0.0
+        interpol = sig.log().lerp(down.log(), 0.5).exp()
+        interpol[-2:] = 0.0
+        return dict(sigmas_interpol=interpol, sigmas_up=up, sigmas_down=down), slice(None, -2)
+
+    def _stage(self, i, first):
+        """(:413-423)"""
+        if first:
+            return self.sigmas[i], self.sigmas_interpol[i], None, None
+        return self.sigmas[i - 1], self.sigmas_interpol[i - 1], self.sigmas_down[i - 1], self.sigmas_up[i - 1]
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, *, noise=None):
+        """``noise`` (extension): this evaluation's draw, otherwise ``torch.randn`` from ``generator`` -- at every evaluation, the
+        first-order ones included, where it is not used"""
+        self._begin(timestep)
+        if noise is None:
+            noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+        return self._advance(model_output, sample, noise, return_dict)
 
 
 class DPMSolverMultistepScheduler:
