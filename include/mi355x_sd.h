@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 19
+#define MI355X_SD_ABI_VERSION 20
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -609,6 +609,43 @@ int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* 
  *    MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, sample, out or coef, batch <= 0, per_sample < 1, and
  *    per_sample < 2 with guidance_rescale > 0. */
 int mi355x_sd_dpm2_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* sample, float* out,
+                          const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                          void* stream);
+
+/* One model evaluation of PLMS sampling (PNDMScheduler with skip_prk_steps, the scheduler of the SD-1.x checkpoints: a linear multistep
+ * method over up to four model outputs; n steps are n + 1 evaluations, the second of which averages two outputs and steps again from
+ * the loop's first sample) in one launch: guidance combine, guidance rescale, the history combination, the update, the history and
+ * the parked sample. `park` (P) is one caller-owned plane of batch * per_sample fp32 values; `hist` is a caller-owned RING of three
+ * such planes, batch * per_sample values apart, that holds the last three guided model outputs. With h1 / h2 / h3 the ring planes
+ * slot - 1 / slot - 2 / slot - 3 (mod 3) and e the guided (and rescaled) model output as in mi355x_sd_multistep_update, per element:
+ *   m   = w0*e [+ w1*h1] [+ w2*h2] [+ w3*h3]       a term whose weight is 0 is not formed and its plane is NOT read
+ *   S   = from_park != 0 ? P : x                   from_park: x is NOT read; otherwise P is NOT read
+ *   m   = p*S + q*m                                only if p != 0 (v-prediction); p == 0: the product with S is not formed
+ *   out = a*S + b*m
+ *   plane[slot] <- e                               unless from_park; e as it came from the guidance, before the p / q conversion
+ *   P   <- x (bit copy)                            only if park != 0 and from_park == 0
+ * Rules:
+ *  - coef is 12 fp32 values (a, b, p, q, w0, w1, w2, w3, slot, park, from_park, 0) in device memory, read by the kernel
+ *    (PNDMScheduler.plms_coefficients; the twelfth pads the row to 48 bytes and is not read): a captured graph of one node replays a
+ *    whole loop, every kind of evaluation, with only the row changing and park / hist at fixed addresses.
+ *  - slot is 0, 1 or 2: the number of outputs stored before this one, mod 3. The oldest plane (slot - 3 = slot) is the one e replaces;
+ *    each element of it is read (for w3) before it is written, by the same lane, so the ring advances by the row alone and the
+ *    launch copies no plane. Any other device value is taken as the nearest of 0, 1, 2 (NaN: 0): nothing outside hist is touched.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - from_park, park, p == 0 and each weight == 0 are wave-uniform branches on the device values. State an evaluation does not need
+ *    is not dereferenced: park and hist need no initialising before a loop's first launch (its row has w1 = w2 = w3 = 0 and
+ *    from_park = 0), and stale or NaN contents of P, of a ring plane or of x cannot reach out where the row does not use them.
+ *  - operation order: as written above, the terms of m summed left to right; which product contracts into which sum is the
+ *    compiler's choice, as in mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when x, park, hist, out and the eps planes are 16-byte aligned and batch * per_sample is
+ *    a multiple of 4 (every plane of the ring aligned), and a scalar tail. No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap of out, park or the three planes of hist with each other, x, eps_uncond,
+ *    eps_text or coef is MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, park, hist, out or coef, batch <= 0,
+ *    per_sample < 1, and per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_plms_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream);
 

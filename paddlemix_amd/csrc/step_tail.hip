@@ -1,8 +1,9 @@
 // The fused step tails (gfx950): the guidance combine, the guidance rescale and one scheduler step in one launch over the fp32 latents.
 //
-// One skeleton, six step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
+// One skeleton, seven step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
 // multistep), UniPCStep, AncestralStep (Euler a), HeunStep (Heun: two stages), MidpointStep (DPM2 and DPM2 a: two stages, the second
-// with noise) -- that holds the operand pointers of its step and states its arithmetic once:
+// with noise), PlmsStep (PNDM's PLMS: a ring of three model outputs and a parked sample) -- that holds the operand pointers of its
+// step and states its arithmetic once:
 //   operands            the leading members, filled by the public launcher (aggregate initialisation; the rest is set on the device)
 //   FLAT                whether the form has an elementwise kernel here (LinearStep: no, see there)
 //   vector_ok()         host: the operands allow the 16-byte vector loop (alignment, and whatever else the form needs)
@@ -22,7 +23,7 @@
 //   the steps                            schedulers/scheduling_euler_discrete.py, scheduling_ddim.py, scheduling_dpmsolver_multistep.py,
 //                                        scheduling_unipc_multistep.py, scheduling_euler_ancestral_discrete.py,
 //                                        scheduling_heun_discrete.py, scheduling_k_dpm_2_discrete.py,
-//                                        scheduling_k_dpm_2_ancestral_discrete.py
+//                                        scheduling_k_dpm_2_ancestral_discrete.py, scheduling_pndm.py (step_plms)
 #include "common.h"
 #include "kernels.h"
 
@@ -602,6 +603,93 @@ struct MidpointStep {
 int launch_dpm2_update(const float* x, const float* eu, const float* et, const float* noise, float* sample, float* out,
                        const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream) {
   return launch_step(MidpointStep{x, noise, sample, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
+}
+
+// One model evaluation of PLMS sampling (PNDMScheduler with skip_prk_steps: a linear multistep method over up to four model outputs,
+// whose second evaluation averages two outputs and steps again from the first sample) in one launch: the guidance combine, the
+// guidance rescale, the history combination, _get_prev_sample, the history and the parked sample. The state lives in caller-owned
+// planes: P (`park`, the sample the loop started from) and a RING of three planes (`hist`, batch * per_sample elements apart) with
+// the last three guided outputs. With coef = (a, b, p, q, w0, w1, w2, w3, slot, park, from_park, 0) in device memory (12 fp32: the
+// row is padded to 48 bytes), h1 / h2 / h3 the ring planes slot - 1 / slot - 2 / slot - 3 mod 3, per element and IN THIS ORDER
+// (tests/plms_bounds.py derives its bound from it; which product fuses with which sum is the compiler's choice, as in multistep_elem):
+//   e   = the guided (and rescaled) model output, as in the ancestral step
+//   m   = w0 * e
+//   m   = m + w1 * h1                            only if w1 != 0; likewise w2 * h2, then w3 * h3: a plane is read for its term only
+//   S   = from_park != 0 ? P : x                 from_park: x is NOT read; otherwise P is NOT read
+//   m   = p * S + q * m                          only if p != 0 (v-prediction); epsilon: the product with S is not formed
+//   out = a * S + b * m
+//   plane[slot] <- e                             unless from_park: the UNCONVERTED guided (and rescaled) output
+//   P   <- x (bit copy)                          only if park != 0 (and not from_park)
+// The oldest plane, slot - 3 = slot mod 3, is the one e replaces: the same lane reads it (for w3) at the same element before it writes
+// e there, so the ring advances by the row's slot alone and no plane is ever copied. slot is 0, 1 or 2; any other device value is
+// taken as the nearest of them (NaN: 0), so that a wrong row cannot index outside hist. All flags, every weight != 0 and p != 0 are
+// uniform branches on the device values, set once in load(): one captured node replays every evaluation of a loop with only the row
+// changing and every pointer fixed. State an evaluation does not need never enters the arithmetic -- a fresh loop's ring and P are
+// uninitialised, and 0 * NaN would poison the latents. S is read and out written by the same lane in the last pass only: out may be x.
+// P and the ring are touched by that same lane at the same element; they overlap nothing else.
+struct PlCoef {
+  float a, b, p, q, w0, w1, w2, w3, slot, park, from_park;
+};
+
+__device__ __forceinline__ float plms_elem(const PlCoef& k, bool r1, bool r2, bool r3, bool px, float S, float e, float h1, float h2,
+                                           float h3) {
+  float m = k.w0 * e;
+  if (r1) m += k.w1 * h1;
+  if (r2) m += k.w2 * h2;
+  if (r3) m += k.w3 * h3;
+  if (px) m = k.p * S + k.q * m;
+  return k.a * S + k.b * m;
+}
+
+struct PlmsStep {
+  static constexpr bool FLAT = true;
+  const float* x;
+  float *park, *hist;
+  long plane;   // the planes of hist are batch * per_sample elements apart, for every sample
+  float* out;
+  PlCoef k;
+  float *h1, *h2, *h3;          // the ring planes slot - 1, slot - 2 and slot (= slot - 3: the oldest, and where e goes)
+  bool fp, pk, px, r1, r2, r3;   // S = P; P <- x; p != 0; the planes that are read
+
+  bool vector_ok() const { return !((ptr_bits(x) | ptr_bits(park) | ptr_bits(hist) | ptr_bits(out)) & 15) && !(plane & 3); }
+  __device__ __forceinline__ void load(const float* __restrict__ c) {
+    k = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10]};
+    const int s = k.slot >= 1.5f ? 2 : k.slot >= 0.5f ? 1 : 0;
+    h1 = hist + (s == 0 ? 2 : s - 1) * plane;
+    h2 = hist + (s == 2 ? 0 : s + 1) * plane;
+    h3 = hist + s * plane;
+    fp = k.from_park != 0.0f;
+    pk = !fp && k.park != 0.0f;
+    px = k.p != 0.0f;
+    r1 = k.w1 != 0.0f, r2 = k.w2 != 0.0f, r3 = k.w3 != 0.0f;
+  }
+  __device__ __forceinline__ void to_sample(long base) { x += base, park += base, h1 += base, h2 += base, h3 += base, out += base; }
+  __device__ __forceinline__ void elem(long i, float e) const {
+    const float S = fp ? park[i] : x[i];
+    out[i] = plms_elem(k, r1, r2, r3, px, S, e, r1 ? h1[i] : 0.f, r2 ? h2[i] : 0.f, r3 ? h3[i] : 0.f);
+    if (!fp) h3[i] = e;
+    if (pk) park[i] = S;
+  }
+  template <class E>
+  __device__ __forceinline__ void vec(long i, E&& guided) const {
+    f32x4 *p4 = reinterpret_cast<f32x4*>(park), *w4 = reinterpret_cast<f32x4*>(h3);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 Sv = fp ? p4[i] : reinterpret_cast<const f32x4*>(x)[i], ev = guided();
+    f32x4 v1 = zero, v2 = zero, v3 = zero, ov;
+    if (r1) v1 = reinterpret_cast<const f32x4*>(h1)[i];
+    if (r2) v2 = reinterpret_cast<const f32x4*>(h2)[i];
+    if (r3) v3 = w4[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ov[j] = plms_elem(k, r1, r2, r3, px, Sv[j], ev[j], v1[j], v2[j], v3[j]);
+    reinterpret_cast<f32x4*>(out)[i] = ov;
+    if (!fp) w4[i] = ev;
+    if (pk) p4[i] = Sv;
+  }
+};
+
+int launch_plms_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
+                       float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  return launch_step(PlmsStep{x, park, hist, (long)batch * per_sample, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
 }
 
 }  // namespace sd

@@ -443,6 +443,29 @@ def dpm2_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise
     return out
 
 
+def plms_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park: Tensor, hist: Tensor, coef: Tensor,
+                guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One model evaluation of PLMS sampling (``PNDMScheduler``, ``skip_prk_steps``) in one launch -> out; ``park`` (the parked sample
+    P) and ``hist`` (a ring of the last three guided model outputs) are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),
+    park: contiguous fp32 [B, ...] of one shape; hist: contiguous fp32 [3, B, ...]; coef: fp32 GPU (a, b, p, q, w0, w1, w2, w3, slot,
+    park, from_park, 0) of ``PNDMScheduler.plms_coefficients``. With e the guided (and, with guidance_rescale > 0, rescaled) model
+    output and h_k = hist[(slot - k) % 3]: m = w0 e + w1 h1 + w2 h2 + w3 h3, S = P if from_park else x, m = p S + q m if p != 0,
+    out = a S + b m; then hist[slot] = e unless from_park, and P = x if park. A term with a zero weight does not read its plane, and
+    only one of x and P is read. out may be x."""
+    lib = _lib.load()
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (park, "park", False), (out, "out", True)),
+               coef, 12, "coef: expected a contiguous fp32 GPU tensor of the 12 values of a PLMS row",
+               eps_text is not None and guidance_rescale > 0.0)
+    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] != 3 or hist.shape[1:] != x.shape:
+        raise ValueError(f"hist: expected [3, {', '.join(map(str, x.shape))}]")
+    _flat_f32(hist, "hist")
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_plms_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), park.data_ptr(), hist.data_ptr(),
+                                    out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
+                                    x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
                  guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
     """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),

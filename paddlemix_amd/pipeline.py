@@ -209,8 +209,25 @@ class _Dpm2Tail(_FusedTail):
                                               lat.shape[0], lat.numel() // lat.shape[0], stream)
 
 
+class _PlmsTail(_FusedTail):
+    """``plms_coefficients`` (PNDM with ``skip_prk_steps``: PLMS): one launch per model evaluation, n + 1 for n steps; the 12 values =
+    row i - first of a table [evaluations, 12] over the timesteps the loop RUNS (the kind of evaluation depends on how many this loop
+    has made, not on its place in the schedule). The tail owns the parked sample and the ring of three model outputs; the first row
+    reads neither and every later one only what an earlier launch wrote, so fresh ones are not initialised, no plane is ever copied
+    and their pointers stay fixed for the whole loop"""
+
+    walk, entry = "plms_coefficients", "mi355x_sd_plms_update"
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:
+            self.history, self.park, self.first = lat.new_empty((3,) + tuple(lat.shape)), torch.empty_like(lat), i
+        return self.lib.mi355x_sd_plms_update(lat.data_ptr(), eps, eps_text, self.park.data_ptr(), self.history.data_ptr(),
+                                              out.data_ptr(), self.coef.data_ptr() + 48 * (i - self.first), gs, gr, lat.shape[0],
+                                              lat.numel() // lat.shape[0], stream)
+
+
 # in priority order: the first whose walk the scheduler has
-_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _Dpm2Tail, _LinearTail)
+_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _Dpm2Tail, _PlmsTail, _LinearTail)
 
 
 class _VaeSwitches:

@@ -30,6 +30,8 @@ The Heun step has two stages, each linear in the sample, the model output and th
 derivative): ``HeunDiscreteScheduler.heun_coefficients`` returns (p, q, h, g, second) for the library's ``mi355x_sd_heun_update``.
 The DPM2 step is a midpoint method of the same two-stage shape that parks the sample alone, and its ancestral variant adds noise in
 the second stage: ``dpm2_coefficients`` of both classes returns (p, q, h, c, second) for the library's ``mi355x_sd_dpm2_update``.
+The PLMS step (PNDM with ``skip_prk_steps``) is linear in the sample, the model output, up to three stored model outputs and one parked
+sample: ``PNDMScheduler.plms_coefficients`` returns its row of 12 for the library's ``mi355x_sd_plms_update``.
 """
 from __future__ import annotations
 
@@ -70,6 +72,11 @@ def _coefficient_walk(*fields):
                 setattr(self, k, v)
 
     return coefficient_walk
+
+
+# what a ``*_coefficients`` walk leaves where ``step`` would leave a tensor: UniPCMultistepScheduler.last_sample ("a predictor has
+# run"), the entries of PNDMScheduler.ets and its cur_sample
+_WALKED = object()
 
 
 class DDIMScheduler:
@@ -294,6 +301,61 @@ class PNDMScheduler:
         coeff = float((a_prev / a_t) ** 0.5)
         denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
         return coeff * sample - float((a_prev - a_t) / denom) * model_output
+
+    coefficient_walk = _coefficient_walk("counter", "ets", "cur_sample", "cur_model_output")   # (plms_coefficients)
+
+    # the exact rationals of step_plms by (counter, len(ets) after the append), newest model output first
+    _PLMS_WEIGHTS = {(0, 1): (1.0, 0.0, 0.0, 0.0), (1, 1): (1 / 2, 1 / 2, 0.0, 0.0), (2, 2): (3 / 2, -1 / 2, 0.0, 0.0),
+                     (3, 3): (23 / 12, -16 / 12, 5 / 12, 0.0), (4, 4): (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+
+    def plms_coefficients(self, timestep) -> Tuple[float, ...]:
+        """This model evaluation of ``step_plms`` (``skip_prk_steps=True``) as a linear map of the sample x the loop holds, the model
+        output e, the stored outputs h1, h2, h3 = ``ets[-2], [-3], [-4]`` after the append (on the averaging evaluation, where nothing
+        is appended, h1 = ``ets[-1]``) and the parked sample P -> (a, b, p, q, w0, w1, w2, w3, slot, park, from_park, 0.0):
+            m    = w0 e + w1 h1 + w2 h2 + w3 h3          a weight of 0.0: the term is not formed
+            S    = P if from_park else x                  (from_park = 1.0: the second evaluation, counter == 1; nothing is appended)
+            m    = p S + q m                              v-prediction; epsilon: p = 0.0 and the line is skipped
+            prev = a S + b m
+        and afterwards e (unconverted) is the newest stored output unless from_park, and P = x where park = 1.0 (counter == 0).
+        ``slot`` is where a ring of three planes takes e: the number of outputs stored before it, mod 3, so that h1, h2, h3 are the
+        planes slot - 1, slot - 2, slot - 3 (= slot, the oldest, read before e replaces it) mod 3. The twelfth value pads the row to
+        48 bytes. Advances ``counter`` and the length of ``ets`` as ``step_plms`` does, with placeholders for the tensors (and for
+        ``cur_sample``). t and t_prev are derived from ``timestep`` and ``counter`` as ``step_plms`` derives them, so a loop that starts
+        inside the schedule gets that method's own second evaluation. Every schedule value is the float32 numpy expression of
+        ``_get_prev_sample``; the weights are the exact rationals. NotImplementedError: the Runge-Kutta warm-up (``skip_prk_steps=False``),
+        a prediction type other than epsilon / v_prediction, a history that does not come from a walk started at ``counter == 0`` (its
+        tensors live on the host, not in the ring), a coefficient that is not finite."""
+        self._require_steps()
+        cfg = self.config
+        if not cfg.skip_prk_steps:
+            raise NotImplementedError("the fused form is PLMS alone: the Runge-Kutta warm-up is not linear in one evaluation's state")
+        if cfg.prediction_type not in ("epsilon", "v_prediction"):
+            raise NotImplementedError("the fused form is for epsilon or v prediction")
+        c = self.counter
+        if any(e is not _WALKED for e in self.ets) or len(self.ets) != (min(c - 1, 4) if c >= 2 else c):
+            raise NotImplementedError("the history of this scheduler was not built by a coefficient walk from counter == 0")
+        step = cfg.num_train_timesteps // self.num_inference_steps
+        t = int(timestep)
+        t_prev = t - step
+        if c != 1:
+            self.ets = self.ets[-3:] + [_WALKED]
+        else:
+            t_prev, t = t, t + step
+        w = self._PLMS_WEIGHTS[(min(c, 4), len(self.ets))]
+        self.cur_sample = _WALKED if c == 0 else None if c == 1 else self.cur_sample
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[t_prev] if t_prev >= 0 else self.final_alpha_cumprod
+        b_t, b_prev = 1 - a_t, 1 - a_prev
+        p, q = (float(b_t ** 0.5), float(a_t ** 0.5)) if cfg.prediction_type == "v_prediction" else (0.0, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = float((a_prev / a_t) ** 0.5)
+            denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
+            b = -float((a_prev - a_t) / denom)
+        self.counter += 1
+        row = (a, b, p, q) + w + (float(max(c - 1, 0) % 3) if c != 1 else 1.0, float(c == 0), float(c == 1), 0.0)
+        if not all(np.isfinite(v) for v in row):
+            raise NotImplementedError("a PLMS coefficient of this evaluation is not finite")
+        return row
 
     def add_noise(self, original_samples, noise, timesteps):
         a = torch.as_tensor(self.alphas_cumprod)[timesteps].to(original_samples.device)
@@ -1164,9 +1226,6 @@ class DPMSolverMultistepScheduler:
 
     def __len__(self):
         return self.config.num_train_timesteps
-
-
-_WALKED = object()   # UniPCMultistepScheduler.last_sample after unipc_coefficients: "a predictor has run", without its tensor
 
 
 class UniPCMultistepScheduler:
