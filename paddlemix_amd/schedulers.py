@@ -32,10 +32,34 @@ The DPM2 step is a midpoint method of the same two-stage shape that parks the sa
 the second stage: ``dpm2_coefficients`` of both classes returns (p, q, h, c, second) for the library's ``mi355x_sd_dpm2_update``.
 The PLMS step (PNDM with ``skip_prk_steps``) is linear in the sample, the model output, up to three stored model outputs and one parked
 sample: ``PNDMScheduler.plms_coefficients`` returns its row of 12 for the library's ``mi355x_sd_plms_update``.
+
+The schedule pieces. Every class below is put together from module-level functions that are each written once, and from one base
+plus one mixin:
+  _make_betas, _train_table          the training table (alphas_cumprod, sigmas) in one of two arithmetics; ``_train_table`` says why two
+  _spaced_timesteps                  the linspace / leading / trailing inference timesteps; point count, rounding and dtype are arguments
+  _karras_schedule, _sigma_to_t      the Karras sigma ramp and the (fractional) training timestep of each of its sigmas
+  _check_prediction_type, _sigma_x0, _sigma_derivative_pq
+                                     sigma space: the accepted prediction types, x0 from the model output, and the derivative
+                                     (x - x0) / sigma as the linear form p*x + q*model_output
+  _alpha_convert, _alpha_convert_pq, _multistep_schedule
+                                     alpha space (DPM-Solver, UniPC): the converted model output, its linear form, the sigma table
+  _Schedule                          base of every class with a beta schedule: config capture, the training table, ``__len__``,
+                                     ``step_index``, the alpha-space ``add_noise``, the identity ``scale_model_input``, and the
+                                     construction sequence, which ends in the class's ``_reset`` -- the step state that
+                                     ``set_timesteps`` resets too
+  _SigmaSpace                        mixin of the sigma-schedule classes (Euler, Euler a, Heun, DPM2, DPM2 a): ``_init_step_index``,
+                                     ``index_for_timestep``, ``model_input_scale``, ``scale_model_input``, ``add_noise``,
+                                     ``init_noise_sigma`` and ``_spaced_sigmas``, ``set_timesteps`` up to the class's table layout
+A new scheduler class states its constructor signature (``self._capture(locals())`` records it), what it refuses, its table layout
+in ``set_timesteps``, its ``_reset``, its ``step`` and its ``*_coefficients``. Where its arithmetic differs from a sibling's in a way
+that shows in a bit of a result, that is a named class attribute or argument (``_train_arithmetic``, ``_float32_init_sigma``,
+``_karras_ends_as_float``, ``_karras_rounded``, ``_spacing_hint``), never a second copy of the expression.
+scripts/compare_schedulers.py walks every class over its options against an older copy of this file, bit for bit.
 """
 from __future__ import annotations
 
 from contextlib import contextmanager
+from math import isfinite
 from types import SimpleNamespace
 from typing import Optional, Tuple
 
@@ -43,12 +67,183 @@ import numpy as np
 import torch
 
 
-def _make_betas(n: int, beta_start: float, beta_end: float, schedule: str) -> np.ndarray:
+def _make_betas(n: int, beta_start: float, beta_end: float, schedule: str, tensor: bool = False, who=None):
+    """float32 betas: a numpy array (``np.linspace`` in float64, rounded to float32) or, with `tensor`, a torch tensor
+    (``torch.linspace`` in float32). `who` names the class in the refusal, for the classes whose reference does."""
+    if tensor:
+        def linspace(lo, hi): return torch.linspace(lo, hi, n, dtype=torch.float32)
+    else:
+        def linspace(lo, hi): return np.linspace(lo, hi, n, dtype=np.float32)
     if schedule == "linear":
-        return np.linspace(beta_start, beta_end, n, dtype=np.float32)
+        return linspace(beta_start, beta_end)
     if schedule == "scaled_linear":  # the latent-diffusion schedule
-        return np.linspace(beta_start ** 0.5, beta_end ** 0.5, n, dtype=np.float32) ** 2
-    raise NotImplementedError(f"{schedule} is not implemented")
+        return linspace(beta_start ** 0.5, beta_end ** 0.5) ** 2
+    raise NotImplementedError(f"{schedule} is not implemented" if who is None else f"{schedule} does is not implemented for {who}")
+
+
+def _sigmas_of(alphas_cumprod):
+    return ((1 - alphas_cumprod) / alphas_cumprod) ** 0.5
+
+
+def _train_table(n: int, beta_start: float, beta_end: float, schedule: str, arithmetic: str, who=None):
+    """-> (alphas_cumprod, training sigmas), float32 numpy arrays, in one of two arithmetics:
+      "numpy"   ``_make_betas``' float64 linspace rounded to float32, then ``np.cumprod`` in float32: what the first classes here were
+                pinned with (DDIM, PNDM, Euler, DPM-Solver, UniPC, LCM), and what their golden loops hold them to.
+      "tensor"  float32 TENSOR operations throughout -- linspace, cumprod, the sigmas' division and square root -- as the reference
+                builds its tables. The numpy table ends 9 float32 steps away at sigma_max (8.6e-6 at 14.6), and a loop that divides by
+                sigma^2 at every step (Euler a, Heun, DPM2, DPM2 a) carries that into the latents: on ``ea_leading_offset1`` it put 2
+                of 512 elements at 1.2 times the test's elementwise tolerance (tests/golden/euler_ancestral/README.md).
+    A class names its choice in ``_train_arithmetic``; tests/test_schedule_pieces.py pins the choice per class."""
+    if arithmetic == "tensor":
+        a = torch.cumprod(1.0 - _make_betas(n, beta_start, beta_end, schedule, True, who), 0)
+        return a.numpy(), _sigmas_of(a).numpy()
+    if arithmetic != "numpy":
+        raise ValueError(f"arithmetic {arithmetic!r}: 'numpy' or 'tensor'")
+    a = np.cumprod(1.0 - _make_betas(n, beta_start, beta_end, schedule, False, who), dtype=np.float32)
+    return a, _sigmas_of(a)
+
+
+_SPACING_HINT = ". Please make sure to choose one of 'linspace', 'leading' or 'trailing'."
+
+
+def _spaced_timesteps(spacing: str, T: int, n: int, steps_offset: int, *, dtype, round_linspace: bool = True,
+                      drop_last: bool = False, hint: bool = True) -> np.ndarray:
+    """The `n` inference timesteps of a `T`-step training schedule, descending, as `dtype`.
+      drop_last       "linspace" and "leading" place n + 1 points and drop the lowest (DPM-Solver, UniPC); "trailing" has no such form
+      round_linspace  False: the "linspace" points stay fractional (the sigma-schedule classes interpolate their sigmas at them)
+      hint            whether the unsupported-spacing message names the choices (each class keeps its reference's wording)
+    `steps_offset` shifts "leading" alone."""
+    m = n + 1 if drop_last else n
+    if spacing == "linspace":
+        ts = np.linspace(0, T - 1, m)
+        ts = ts.round() if round_linspace else ts
+    elif spacing == "leading":
+        ts = (np.arange(0, m) * (T // m)).round()
+    elif spacing == "trailing":
+        return np.arange(T, 0, -T / n).round().astype(dtype) - 1
+    else:
+        raise ValueError(f"{spacing} is not supported" + (_SPACING_HINT if hint else ""))
+    ts = (ts[::-1][:-1] if drop_last else ts[::-1]).copy().astype(dtype)
+    return ts + steps_offset if spacing == "leading" else ts
+
+
+def _sigma_to_t(sigma, log_sigmas):
+    """the fractional training timestep at which the table of `log_sigmas`, interpolated, gives log `sigma`"""
+    log_sigma = np.log(np.maximum(sigma, 1e-10))
+    dists = log_sigma - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
+
+
+def _karras_schedule(lo, hi, n: int, log_sigmas, rounded: bool, rho: float = 7.0):
+    """-> (sigmas, timesteps): the noise levels of Karras et al. (2022) from `hi` down to `lo`, float64, and the training timestep of
+    each. The end points' roots are taken in the arithmetic `lo` and `hi` arrive in -- float32 numpy scalars (DPM-Solver), float64
+    numpy scalars (Euler) or Python floats (Heun, DPM2, UniPC) -- which is why the callers convert them, not this function.
+    `rounded`: DPM2, DPM-Solver and UniPC round the timesteps, Euler and Heun keep the fractions."""
+    lo, hi = lo ** (1 / rho), hi ** (1 / rho)
+    sigmas = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
+    ts = np.array([_sigma_to_t(s, log_sigmas) for s in sigmas])
+    return sigmas, ts.round() if rounded else ts
+
+
+def _check_prediction_type(pt: str, accepted=("epsilon", "v_prediction")):
+    """the sigma-schedule classes' check: "sample" outside `accepted` is unimplemented, anything else outside it is refused"""
+    if pt == "sample" and pt not in accepted:
+        raise NotImplementedError("prediction_type not implemented yet: sample")
+    if pt not in accepted:
+        raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+
+
+def _sigma_x0(pt: str, sample, model_output, sigma):
+    """x0 of a sigma-space step (after ``_check_prediction_type``: what is neither epsilon nor v is a sample prediction). `sigma`: a
+    float, or a 0-dim tensor, in whose dtype the scalar expressions are then rounded."""
+    if pt == "epsilon":
+        return sample - sigma * model_output
+    if pt == "v_prediction":
+        return model_output * (-sigma / (sigma ** 2 + 1) ** 0.5) + (sample / (sigma ** 2 + 1))
+    return model_output
+
+
+def _sigma_derivative_pq(pt: str, sigma) -> Tuple[float, float]:
+    """(p, q) with (x - x0) / sigma = p*x + q*model_output for the x0 of ``_sigma_x0``, in float64:
+      epsilon       x0 = x - s e                                 ->  e
+      v_prediction  x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1)     ->  x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+      sample        x0 = e                                       ->  (x - e) / s
+    sigma = 0 gives inf or nan, which the caller refuses."""
+    with np.errstate(all="ignore"):
+        s_in = np.float64(sigma)
+        if pt == "epsilon":
+            return 0.0, 1.0
+        if pt == "v_prediction":
+            return float(s_in / (s_in ** 2 + 1)), float(1.0 / (s_in ** 2 + 1) ** 0.5)
+        return float(1.0 / s_in), float(-1.0 / s_in)
+
+
+def _euler_ab(pt: str, s: float, dt: float) -> Tuple[float, float]:
+    """(a, b) with x + dt * (x - x0) / s = a*x + b*model_output for epsilon or v prediction: the row of Euler (which writes it out
+    in ``step_coefficients``, where a call would show in the row's host time) and Euler a. Not
+    ``1 + dt * p, dt * q`` of ``_sigma_derivative_pq``: here dt * s is formed before the division, which rounds differently from
+    dt * (s / (s^2 + 1)) in the last bit, and the rows both classes were recorded with hold that bit."""
+    if pt == "v_prediction":
+        return 1.0 + dt * s / (s ** 2 + 1), dt / (s ** 2 + 1) ** 0.5
+    return 1.0, dt
+
+
+def _sigma_to_alpha_sigma_t(sigma):
+    alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
+    return alpha_t, sigma * alpha_t
+
+
+def _check_alpha_prediction_type(pt: str, who: str):
+    if pt not in ("epsilon", "sample", "v_prediction"):
+        raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction` for the {who}.")
+
+
+def _alpha_convert(pt: str, to_x0: bool, a: float, s: float, sample, model_output):
+    """model output -> x0 prediction (`to_x0`: dpmsolver++, UniPC's predict_x0) or epsilon prediction, at alpha_t = a, sigma_t = s"""
+    if to_x0:
+        return (sample - s * model_output) / a if pt == "epsilon" else model_output if pt == "sample" else a * sample - s * model_output
+    return model_output if pt == "epsilon" else (sample - a * model_output) / s if pt == "sample" else a * model_output + s * sample
+
+
+def _alpha_convert_pq(pt: str, to_x0: bool, a: float, s: float) -> Tuple[float, float]:
+    """(p, q) with ``_alpha_convert`` = p * sample + q * model_output"""
+    if to_x0:
+        return (1.0 / a, -s / a) if pt == "epsilon" else (0.0, 1.0) if pt == "sample" else (a, -s)
+    return (0.0, 1.0) if pt == "epsilon" else (1.0 / s, -a / s) if pt == "sample" else (s, a)
+
+
+def _multistep_schedule(alphas_cumprod, c, n: int, karras_ends_as_float: bool):
+    """-> (sigmas, timesteps) of the alpha-space multistep classes (DPM-Solver, UniPC): n + 1 spacing points with the last dropped,
+    the sigmas interpolated at them or a Karras ramp over the whole training table, and one closing sigma -- the training table's
+    smallest, or on a Karras schedule the ramp's last once more. `karras_ends_as_float`: UniPC takes the ramp's end points through
+    ``.item()`` (float64 roots), DPM-Solver as the table's float32 numpy scalars (float32 roots)."""
+    ts = _spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, n, c.steps_offset, dtype=np.int64, drop_last=True)
+    sigmas = np.array(_sigmas_of(alphas_cumprod))
+    if c.use_karras_sigmas:
+        lo, hi = (sigmas[0].item(), sigmas[-1].item()) if karras_ends_as_float else (sigmas[0], sigmas[-1])
+        s, ts = _karras_schedule(lo, hi, n, np.log(sigmas), rounded=True)
+        sigmas = np.concatenate([s, s[-1:]]).astype(np.float32)
+    else:
+        sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
+        sigmas = np.concatenate([sigmas, [_sigmas_of(alphas_cumprod[0])]]).astype(np.float32)
+    return sigmas, ts.astype(np.int64)
+
+
+def _init_multistep_index(self, timestep):
+    """``_init_step_index`` of DPM-Solver and UniPC"""
+    c = np.nonzero(self.timesteps == int(timestep))[0]
+    # "the sigma index that is taken for the **very** first `step` is always the second index": an img2img start on a
+    # duplicated timestep must not skip a sigma. A timestep that is not in the schedule: the last index
+    self._step_index = len(self.timesteps) - 1 if len(c) == 0 else int(c[1] if len(c) > 1 else c[0])
+
+
+def _alpha_sigma_floats(sigma) -> Tuple[float, float]:
+    a, s = _sigma_to_alpha_sigma_t(sigma)
+    return float(a), float(s)
 
 
 def _out(prev, return_dict, **extra):
@@ -78,42 +273,181 @@ def _coefficient_walk(*fields):
 # run"), the entries of PNDMScheduler.ets and its cur_sample
 _WALKED = object()
 
+_NO_STEPS = "Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler"
 
-class DDIMScheduler:
+
+class _Schedule:
+    """What every class with a beta schedule shares; on its own, the base of the alpha-space classes (DDIM, PNDM, DPM-Solver,
+    UniPC, LCM). ``__init__`` of a class:  ``self._capture(locals())`` , its refusals, ``self._build()`` ."""
     order = 1
+    _train_arithmetic = "numpy"       # see _train_table
+    _names_class_in_refusal = False   # the beta-schedule refusal of Heun and DPM2 names the class, as their reference's does
 
+    def _capture(self, arguments):
+        self.config = SimpleNamespace(**{k: v for k, v in arguments.items() if k != "self"})
+
+    def _build(self):
+        """the training table, the state of a scheduler that no ``set_timesteps`` has run on ("all values"), the class's ``_reset``"""
+        c = self.config
+        if getattr(c, "trained_betas", None) is not None:
+            raise NotImplementedError(f"{self.__class__.__name__}(mi355x): trained_betas is not implemented")
+        self.alphas_cumprod, train_sigmas = _train_table(c.num_train_timesteps, c.beta_start, c.beta_end, c.beta_schedule,
+                                                         self._train_arithmetic, self.__class__ if self._names_class_in_refusal else None)
+        self._all_values(train_sigmas)
+        self._reset()
+
+    def _all_values(self, train_sigmas):
+        """alpha space: the whole training schedule, descending (a class that needs sigmas takes them from ``alphas_cumprod`` as it
+        stands when ``set_timesteps`` runs)"""
+        c = self.config
+        if hasattr(c, "set_alpha_to_one"):
+            self.final_alpha_cumprod = np.float32(1.0) if c.set_alpha_to_one else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = np.arange(0, c.num_train_timesteps)[::-1].copy().astype(np.int64)
+
+    def _reset(self):
+        """the step state, which ``__init__`` and ``set_timesteps`` both leave like this (DDIM has none)"""
+
+    @property
+    def step_index(self):
+        return vars(self).get("_step_index")   # (DDIM and PNDM keep none; no class-level default, which would slow every read of it)
+
+    def _require_steps(self):
+        if self.num_inference_steps is None:
+            raise ValueError(_NO_STEPS)
+
+    def scale_model_input(self, sample, timestep=None, *args, **kwargs):
+        return sample
+
+    def _table_index(self, timesteps):
+        return timesteps
+
+    def add_noise(self, original_samples, noise, timesteps):
+        a = torch.as_tensor(self.alphas_cumprod)[self._table_index(timesteps)].to(original_samples.device)
+        while a.dim() < original_samples.dim():
+            a = a.unsqueeze(-1)
+        return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
+
+    def __len__(self):
+        return self.config.num_train_timesteps
+
+
+class _SigmaSpace:
+    """Mixin of the sigma-schedule classes, in front of ``_Schedule`` in their bases: the model sees  sample / sqrt(sigma^2 + 1) ,
+    noise enters as  sigma * noise , and ``set_timesteps`` interpolates the training sigmas at fractional float32 timesteps. A class
+    adds its table layout to ``set_timesteps``, its ``_reset``, its stage logic and its coefficients."""
+    _spacing_hint = True               # Euler's unsupported-spacing message does not name the choices
+    _float32_init_sigma = False        # Heun, DPM2: sqrt(max^2 + 1) in float32, their reference's tensor expression; Euler (a): float64
+    _karras_ends_as_float = True       # Euler hands the interpolated end points to the ramp as float64 numpy scalars
+    _karras_rounded = False            # DPM2 rounds the Karras timesteps
+    _all_values_by_set_timesteps = False
+    _index_counter = None              # Heun, DPM2: {timestep: ``step`` calls seen}; Euler and Euler a do not count
+
+    def _all_values(self, train_sigmas):
+        """Euler, Euler a: the training schedule itself; Heun, DPM2: ``set_timesteps`` over all of it, as their reference's do"""
+        T = self.config.num_train_timesteps
+        self._train_sigmas = train_sigmas
+        if self._all_values_by_set_timesteps:
+            return self.set_timesteps(T)
+        self.sigmas = np.concatenate([train_sigmas[::-1], [0.0]]).astype(np.float32)
+        self.timesteps = np.linspace(0, T - 1, T, dtype=float)[::-1].astype(np.float32)
+        self.num_inference_steps = None
+
+    def _reset(self):
+        self._step_index = None
+
+    @property
+    def init_noise_sigma(self):
+        m = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return float(m)
+        if self._float32_init_sigma:
+            return float(np.sqrt(m * m + np.float32(1.0)))
+        return (float(m) ** 2 + 1) ** 0.5
+
+    def _interpolated_sigmas(self, ts, sig_all, n):
+        return np.interp(ts, np.arange(0, len(sig_all)), sig_all)
+
+    def _spaced_sigmas(self, n: int, T: Optional[int] = None):
+        """the part of ``set_timesteps`` every sigma-schedule class shares -> (the n sigmas and a closing 0.0, the n timesteps), float32"""
+        c = self.config
+        self.num_inference_steps = n
+        ts = _spaced_timesteps(c.timestep_spacing, T or c.num_train_timesteps, n, c.steps_offset, dtype=np.float32,
+                               round_linspace=False, hint=self._spacing_hint)
+        sig_all = np.array(self._train_sigmas)
+        sig = self._interpolated_sigmas(ts, sig_all, n)
+        if getattr(c, "use_karras_sigmas", False):
+            lo, hi = (sig[-1].item(), sig[0].item()) if self._karras_ends_as_float else (sig[-1], sig[0])
+            sig, ts = _karras_schedule(lo, hi, n, np.log(sig_all), self._karras_rounded)
+        return np.concatenate([sig, [0.0]]).astype(np.float32), ts.astype(np.float32)
+
+    def set_timesteps(self, num_inference_steps: int):
+        self.sigmas, self.timesteps = self._spaced_sigmas(num_inference_steps)
+        self._reset()
+
+    def _init_step_index(self, timestep):
+        t = float(timestep)
+        idx = np.nonzero(self.timesteps == np.float32(t))[0]
+        # "the sigma index that is taken for the **very** first step is always the second index" (duplicates)
+        self._step_index = int(idx[1] if len(idx) > 1 else idx[0])
+
+    def index_for_timestep(self, timestep, schedule_timesteps=None):
+        """The index ``add_noise`` takes a timestep's sigma from. A class that counts its ``step`` calls (Heun, DPM2, whose timesteps
+        repeat): before any step the second of two matching indices (the only one if single), afterwards the one the counter of
+        ``step`` calls at this timestep points to. Euler and Euler a: the first match."""
+        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
+        t = float(timestep)
+        idx = np.nonzero(np.asarray(ts) == np.float32(t))[0]
+        if self._index_counter is None:
+            pos = 0
+        elif len(self._index_counter) == 0:
+            pos = 1 if len(idx) > 1 else 0
+        else:
+            pos = self._index_counter.setdefault(t, 0)
+        return int(idx[pos])
+
+    def _count_step(self, timestep):
+        t = float(timestep)
+        self._index_counter[t] = self._index_counter.get(t, 0) + 1
+
+    def scale_model_input(self, sample, timestep):
+        """(Heun and DPM2 divide by a 0-dim tensor instead of a float, DPM2 at its own sigma: their own)"""
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return sample / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
+
+    def model_input_scale(self, timestep) -> float:
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        return 1.0 / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
+
+    def add_noise(self, original_samples, noise, timesteps):   # (sigma space; _Schedule's is the alpha-space one)
+        """x + noise * sigma[``index_for_timestep`` of each timestep in the current schedule]"""
+        ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps, dtype=np.float32))
+        idx = [self.index_for_timestep(t) for t in ts]
+        sigma = torch.as_tensor(np.asarray(self.sigmas, dtype=np.float32)[idx]).to(original_samples.device,
+                                                                                  original_samples.dtype)
+        while sigma.dim() < original_samples.dim():
+            sigma = sigma.unsqueeze(-1)
+        return original_samples + noise * sigma
+
+
+class DDIMScheduler(_Schedule):
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", clip_sample: bool = True, set_alpha_to_one: bool = True,
                  steps_offset: int = 0, prediction_type: str = "epsilon", clip_sample_range: float = 1.0,
                  timestep_spacing: str = "leading"):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
-        self.timesteps = np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64)
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
+        self._capture(locals())
+        self._build()
 
     def set_timesteps(self, num_inference_steps: int):
         c = self.config
         if num_inference_steps > c.num_train_timesteps:
             raise ValueError("`num_inference_steps` cannot be larger than `num_train_timesteps`")
         self.num_inference_steps = num_inference_steps
-        if c.timestep_spacing == "leading":
-            step_ratio = c.num_train_timesteps // num_inference_steps
-            ts = (np.arange(0, num_inference_steps) * step_ratio).round()[::-1].copy().astype(np.int64)
-            ts += c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = np.round(np.arange(c.num_train_timesteps, 0, -c.num_train_timesteps / num_inference_steps))
-            ts = ts.astype(np.int64) - 1
-        elif c.timestep_spacing == "linspace":
-            ts = np.linspace(0, c.num_train_timesteps - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported")
-        self.timesteps = ts
+        self.timesteps = _spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, num_inference_steps, c.steps_offset,
+                                           dtype=np.int64, hint=False)
 
     def _alphas(self, timestep: int) -> Tuple[float, float]:
         prev_t = timestep - self.config.num_train_timesteps // self.num_inference_steps
@@ -142,9 +476,7 @@ class DDIMScheduler:
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
              generator=None, variance_noise=None, return_dict: bool = True):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating "
-                             "the scheduler")
+        self._require_steps()
         c = self.config
         t = int(timestep)
         a_t, a_prev = (float(v) for v in self._alphas(t))
@@ -175,48 +507,29 @@ class DDIMScheduler:
             prev = prev + std * variance_noise
         return _out(prev, return_dict, pred_original_sample=x0)
 
-    def add_noise(self, original_samples, noise, timesteps):
-        a = torch.as_tensor(self.alphas_cumprod)[timesteps].to(original_samples.device)
-        while a.dim() < original_samples.dim():
-            a = a.unsqueeze(-1)
-        return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
 
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-
-class PNDMScheduler:
+class PNDMScheduler(_Schedule):
     """Pseudo numerical methods for diffusion models: Runge-Kutta warm-up (``step_prk``) + linear multistep (``step_plms``);
     Stable Diffusion uses ``skip_prk_steps=True`` (crowsonkb's PLMS, scheduling_pndm.py:216-223)."""
-    order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", skip_prk_steps: bool = False, set_alpha_to_one: bool = False,
                  prediction_type: str = "epsilon", timestep_spacing: str = "leading", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
-        self.init_noise_sigma = 1.0
+        self._capture(locals())
         self.pndm_order = 4
-        self.cur_model_output, self.counter, self.cur_sample, self.ets = 0, 0, None, []
-        self.num_inference_steps = None
-        self._timesteps = np.arange(0, num_train_timesteps)[::-1].copy()
+        self.cur_sample = None
+        self._build()
+        self._timesteps = self.timesteps
         self.prk_timesteps = self.plms_timesteps = self.timesteps = None
+
+    def _reset(self):
+        self.ets, self.counter, self.cur_model_output = [], 0, 0
 
     def set_timesteps(self, num_inference_steps: int):
         c = self.config
         self.num_inference_steps = n = num_inference_steps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, c.num_train_timesteps - 1, n).round().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (c.num_train_timesteps // n)).round().astype(np.int64) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = np.round(np.arange(c.num_train_timesteps, 0, -c.num_train_timesteps / n))[::-1].astype(np.int64) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        self._timesteps = ts
+        self._timesteps = ts = _spaced_timesteps(c.timestep_spacing, c.num_train_timesteps, n, c.steps_offset,
+                                                 dtype=np.int64)[::-1].copy()   # ascending
         if c.skip_prk_steps:
             self.prk_timesteps = np.array([], dtype=np.int64)
             self.plms_timesteps = np.concatenate([ts[:-1], ts[-2:-1], ts[-1:]])[::-1].copy()
@@ -226,19 +539,12 @@ class PNDMScheduler:
             self.prk_timesteps = (prk[:-1].repeat(2)[1:-1])[::-1].copy()
             self.plms_timesteps = ts[:-3][::-1].copy()
         self.timesteps = np.concatenate([self.prk_timesteps, self.plms_timesteps]).astype(np.int64)
-        self.ets, self.counter, self.cur_model_output = [], 0, 0
-
-    def scale_model_input(self, sample, *args, **kwargs):
-        return sample
+        self._reset()
 
     def step(self, model_output, timestep, sample, return_dict: bool = True):
         if self.counter < len(self.prk_timesteps) and not self.config.skip_prk_steps:
             return self.step_prk(model_output, timestep, sample, return_dict)
         return self.step_plms(model_output, timestep, sample, return_dict)
-
-    def _require_steps(self):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
 
     def step_prk(self, model_output, timestep, sample, return_dict: bool = True):
         self._require_steps()
@@ -265,14 +571,7 @@ class PNDMScheduler:
         if not self.config.skip_prk_steps and len(self.ets) < 3:
             raise ValueError(f"{self.__class__} can only be run AFTER scheduler has been run in 'prk' mode for at least 12 "
                              "iterations")
-        step = self.config.num_train_timesteps // self.num_inference_steps
-        timestep = int(timestep)
-        prev_timestep = timestep - step
-        if self.counter != 1:
-            self.ets = self.ets[-3:]
-            self.ets.append(model_output)
-        else:
-            prev_timestep, timestep = timestep, timestep + step
+        timestep, prev_timestep = self._plms_evaluation(timestep, model_output)
         e = self.ets
         if len(e) == 1 and self.counter == 0:
             self.cur_sample = sample
@@ -289,18 +588,37 @@ class PNDMScheduler:
         self.counter += 1
         return _out(prev, return_dict)
 
-    def _get_prev_sample(self, sample, timestep, prev_timestep, model_output):
-        """formula (9) of the PNDM paper (scheduling_pndm.py:410-453), coefficients in float32 like the reference's tables"""
+    def _plms_evaluation(self, timestep, entry):
+        """-> (t, t_prev) of this evaluation of ``step_plms``, after `entry` has become the newest of ``ets``. The second evaluation
+        (counter == 1) stores nothing and is made one step up: it repeats the first step with the average of both outputs."""
+        step = self.config.num_train_timesteps // self.num_inference_steps
+        t = int(timestep)
+        if self.counter == 1:
+            return t + step, t
+        self.ets = self.ets[-3:] + [entry]
+        return t, t - step
+
+    def _prev_sample_scalars(self, timestep, prev_timestep) -> Tuple[float, float, float, float]:
+        """(a, b, p, q) of formula (9) of the PNDM paper (scheduling_pndm.py:410-453):  prev = a*sample - b*m , where for v-prediction
+        m = p*sample + q*model_output  first. Float32 numpy expressions, like the reference's tables; a_t = 0 gives inf or nan (b
+        keeps the reference's sign for that: negating a NaN flips its sign bit)."""
         a_t = self.alphas_cumprod[timestep]
         a_prev = self.alphas_cumprod[prev_timestep] if prev_timestep >= 0 else self.final_alpha_cumprod
         b_t, b_prev = 1 - a_t, 1 - a_prev
-        if self.config.prediction_type == "v_prediction":
-            model_output = float(a_t ** 0.5) * model_output + float(b_t ** 0.5) * sample
-        elif self.config.prediction_type != "epsilon":
+        p, q = (float(b_t ** 0.5), float(a_t ** 0.5)) if self.config.prediction_type == "v_prediction" else (0.0, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = float((a_prev / a_t) ** 0.5)
+            denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
+            b = float((a_prev - a_t) / denom)
+        return a, b, p, q
+
+    def _get_prev_sample(self, sample, timestep, prev_timestep, model_output):
+        if self.config.prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"prediction_type given as {self.config.prediction_type} must be one of `epsilon` or `v_prediction`")
-        coeff = float((a_prev / a_t) ** 0.5)
-        denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
-        return coeff * sample - float((a_prev - a_t) / denom) * model_output
+        a, b, p, q = self._prev_sample_scalars(timestep, prev_timestep)
+        if self.config.prediction_type == "v_prediction":
+            model_output = q * model_output + p * sample
+        return a * sample - b * model_output
 
     coefficient_walk = _coefficient_walk("counter", "ets", "cur_sample", "cur_model_output")   # (plms_coefficients)
 
@@ -320,9 +638,9 @@ class PNDMScheduler:
         ``slot`` is where a ring of three planes takes e: the number of outputs stored before it, mod 3, so that h1, h2, h3 are the
         planes slot - 1, slot - 2, slot - 3 (= slot, the oldest, read before e replaces it) mod 3. The twelfth value pads the row to
         48 bytes. Advances ``counter`` and the length of ``ets`` as ``step_plms`` does, with placeholders for the tensors (and for
-        ``cur_sample``). t and t_prev are derived from ``timestep`` and ``counter`` as ``step_plms`` derives them, so a loop that starts
-        inside the schedule gets that method's own second evaluation. Every schedule value is the float32 numpy expression of
-        ``_get_prev_sample``; the weights are the exact rationals. NotImplementedError: the Runge-Kutta warm-up (``skip_prk_steps=False``),
+        ``cur_sample``). t and t_prev come from ``_plms_evaluation``, as ``step_plms``' do, so a loop that starts inside the schedule
+        gets that method's own second evaluation. The schedule values are those of ``_prev_sample_scalars``, which ``step_plms`` reads
+        too; the weights are the exact rationals. NotImplementedError: the Runge-Kutta warm-up (``skip_prk_steps=False``),
         a prediction type other than epsilon / v_prediction, a history that does not come from a walk started at ``counter == 0`` (its
         tensors live on the host, not in the ring), a coefficient that is not finite."""
         self._require_steps()
@@ -334,133 +652,50 @@ class PNDMScheduler:
         c = self.counter
         if any(e is not _WALKED for e in self.ets) or len(self.ets) != (min(c - 1, 4) if c >= 2 else c):
             raise NotImplementedError("the history of this scheduler was not built by a coefficient walk from counter == 0")
-        step = cfg.num_train_timesteps // self.num_inference_steps
-        t = int(timestep)
-        t_prev = t - step
-        if c != 1:
-            self.ets = self.ets[-3:] + [_WALKED]
-        else:
-            t_prev, t = t, t + step
+        t, t_prev = self._plms_evaluation(timestep, _WALKED)
         w = self._PLMS_WEIGHTS[(min(c, 4), len(self.ets))]
         self.cur_sample = _WALKED if c == 0 else None if c == 1 else self.cur_sample
-        a_t = self.alphas_cumprod[t]
-        a_prev = self.alphas_cumprod[t_prev] if t_prev >= 0 else self.final_alpha_cumprod
-        b_t, b_prev = 1 - a_t, 1 - a_prev
-        p, q = (float(b_t ** 0.5), float(a_t ** 0.5)) if cfg.prediction_type == "v_prediction" else (0.0, 1.0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            a = float((a_prev / a_t) ** 0.5)
-            denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
-            b = -float((a_prev - a_t) / denom)
+        a, b, p, q = self._prev_sample_scalars(t, t_prev)
         self.counter += 1
-        row = (a, b, p, q) + w + (float(max(c - 1, 0) % 3) if c != 1 else 1.0, float(c == 0), float(c == 1), 0.0)
-        if not all(np.isfinite(v) for v in row):
+        row = (a, -b, p, q) + w + (float(max(c - 1, 0) % 3) if c != 1 else 1.0, float(c == 0), float(c == 1), 0.0)
+        if not all(map(isfinite, row)):
             raise NotImplementedError("a PLMS coefficient of this evaluation is not finite")
         return row
 
-    def add_noise(self, original_samples, noise, timesteps):
-        a = torch.as_tensor(self.alphas_cumprod)[timesteps].to(original_samples.device)
-        while a.dim() < original_samples.dim():
-            a = a.unsqueeze(-1)
-        return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
 
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-
-class EulerDiscreteScheduler:
-    order = 1
+class EulerDiscreteScheduler(_SigmaSpace, _Schedule):
+    _spacing_hint = False
+    _karras_ends_as_float = False
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", prediction_type: str = "epsilon", interpolation_type: str = "linear",
                  use_karras_sigmas: bool = False, timestep_spacing: str = "linspace", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self._train_sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
-        self.sigmas = np.concatenate([self._train_sigmas[::-1], [0.0]]).astype(np.float32)
-        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=float)[::-1].astype(
-            np.float32)
-        self.num_inference_steps = None
-        self._step_index: Optional[int] = None
-
-    @property
-    def init_noise_sigma(self):
-        m = float(self.sigmas.max())
-        if self.config.timestep_spacing in ("linspace", "trailing"):
-            return m
-        return (m ** 2 + 1) ** 0.5
-
-    @property
-    def step_index(self):
-        return self._step_index
+        self._capture(locals())
+        self._build()
 
     coefficient_walk = _coefficient_walk("_step_index")   # (step_coefficients, model_input_scale)
 
-    def set_timesteps(self, num_inference_steps: int):
-        c = self.config
-        self.num_inference_steps = n = num_inference_steps
-        T = c.num_train_timesteps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported")
-        sig_all = np.array(self._train_sigmas)
-        log_sig = np.log(sig_all)
-        if c.interpolation_type == "linear":
-            sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
-        elif c.interpolation_type == "log_linear":
-            sig = np.exp(np.linspace(np.log(sig_all[-1]), np.log(sig_all[0]), n + 1))
-        else:
-            raise ValueError(f"{c.interpolation_type} is not implemented")
-        if c.use_karras_sigmas:
-            rho = 7.0
-            lo, hi = sig[-1] ** (1 / rho), sig[0] ** (1 / rho)
-            sig = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
-            ts = np.array([self._sigma_to_t(s, log_sig) for s in sig])
-        self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
-        self.timesteps = ts.astype(np.float32)
-        self._step_index = None
-
-    @staticmethod
-    def _sigma_to_t(sigma, log_sigmas):
-        log_sigma = np.log(np.maximum(sigma, 1e-10))
-        dists = log_sigma - log_sigmas[:, np.newaxis]
-        low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
-        high_idx = low_idx + 1
-        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
-        w = np.clip((low - log_sigma) / (low - high), 0, 1)
-        return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
-
-    def _init_step_index(self, timestep):
-        t = float(timestep)
-        idx = np.nonzero(self.timesteps == np.float32(t))[0]
-        # "the sigma index that is taken for the **very** first step is always the second index" (duplicates)
-        self._step_index = int(idx[1] if len(idx) > 1 else idx[0])
-
-    def scale_model_input(self, sample, timestep):
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        return sample / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
-
-    def model_input_scale(self, timestep) -> float:
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        return 1.0 / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
+    def _interpolated_sigmas(self, ts, sig_all, n):
+        kind = self.config.interpolation_type
+        if kind == "linear":
+            return super()._interpolated_sigmas(ts, sig_all, n)
+        if kind == "log_linear":
+            return np.exp(np.linspace(np.log(sig_all[-1]), np.log(sig_all[0]), n + 1))
+        raise ValueError(f"{kind} is not implemented")
 
     def step_coefficients(self, timestep) -> Tuple[float, float]:
         """(a, b) with prev = a*sample + b*model_output for epsilon or v prediction, s_churn = 0; advances the index."""
-        if self.config.prediction_type not in ("epsilon", "v_prediction"):
+        pt = self.config.prediction_type
+        if pt not in ("epsilon", "v_prediction"):
             raise NotImplementedError("linear-update form is for epsilon or v prediction")
         if self._step_index is None:
             self._init_step_index(timestep)
-        s, s_next = float(self.sigmas[self._step_index]), float(self.sigmas[self._step_index + 1])
-        self._step_index += 1
-        if self.config.prediction_type == "v_prediction":
-            # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
+        i = self._step_index
+        s, s_next = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        self._step_index = i + 1
+        # _euler_ab(pt, s, s_next - s), written out: a call is a tenth of this row's host time (tests/test_schedule_pieces.py holds
+        # the two to the same bits)
+        if pt == "v_prediction":
             return 1.0 + (s_next - s) * s / (s ** 2 + 1), (s_next - s) / (s ** 2 + 1) ** 0.5
         return 1.0, s_next - s
 
@@ -476,108 +711,34 @@ class EulerDiscreteScheduler:
                                 dtype=model_output.dtype)
             sample = sample + noise * s_noise * (sigma_hat ** 2 - sigma ** 2) ** 0.5
         pt = self.config.prediction_type
-        if pt in ("original_sample", "sample"):
-            x0 = model_output
-        elif pt == "epsilon":
-            x0 = sample - sigma_hat * model_output
-        elif pt == "v_prediction":
-            x0 = model_output * (-sigma / (sigma ** 2 + 1) ** 0.5) + (sample / (sigma ** 2 + 1))
-        else:
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+        _check_prediction_type(pt, ("epsilon", "v_prediction", "sample", "original_sample"))
+        # (the reference's epsilon form takes the churned sigma_hat, its v form the schedule's sigma)
+        x0 = _sigma_x0(pt, sample, model_output, sigma if pt == "v_prediction" else sigma_hat)
         derivative = (sample - x0) / sigma_hat
         dt = float(self.sigmas[self._step_index + 1]) - sigma_hat
         prev = sample + derivative * dt
         self._step_index += 1
         return _out(prev, return_dict, pred_original_sample=x0)
 
-    def add_noise(self, original_samples, noise, timesteps):
-        """scheduling_euler_discrete.py:480-500: x + noise * sigma[index of each timestep in the current schedule]"""
-        ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps, dtype=np.float32))
-        idx = [int(np.nonzero(self.timesteps == t)[0][0]) for t in ts]
-        sigma = torch.as_tensor(np.asarray(self.sigmas, dtype=np.float32)[idx]).to(original_samples.device,
-                                                                                  original_samples.dtype)
-        while sigma.dim() < original_samples.dim():
-            sigma = sigma.unsqueeze(-1)
-        return original_samples + noise * sigma
 
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-
-class EulerAncestralDiscreteScheduler:
+class EulerAncestralDiscreteScheduler(_SigmaSpace, _Schedule):
     """"Euler a" (scheduling_euler_ancestral_discrete.py:130-389): an Euler step down to sigma_down and fresh noise of sigma_up back
     up, every step. epsilon and v prediction, the three spacings; ``trained_betas`` is not implemented. The step is linear in the
     sample, the model output and the noise: ``ancestral_coefficients`` returns (a, b, c) with  prev = a*sample + b*model_output +
     c*noise  for the library's ``mi355x_sd_ancestral_update``."""
-    order = 1
+    _train_arithmetic = "tensor"
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", trained_betas=None, prediction_type: str = "epsilon",
                  timestep_spacing: str = "linspace", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        if trained_betas is not None:
-            raise NotImplementedError("EulerAncestralDiscreteScheduler(mi355x): trained_betas is not implemented")
-        # The training table in float32 TENSOR arithmetic, as the reference builds it (:141-161: linspace, cumprod and the sigmas are
-        # float32 tensor operations). _make_betas' float64 linspace rounded to float32 ends 9 float32 steps away at sigma_max, and an
-        # ancestral loop, whose every step divides by sigma^2, carries that into the latents (tests/golden/euler_ancestral/README.md)
-        if beta_schedule == "linear":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{beta_schedule} is not implemented")
-        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
-        self.alphas_cumprod = alphas_cumprod.numpy()
-        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
-        self.sigmas = np.concatenate([self._train_sigmas[::-1], [0.0]]).astype(np.float32)
-        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=float)[::-1].astype(np.float32)
-        self.num_inference_steps = None
-        self._step_index: Optional[int] = None
-
-    @property
-    def init_noise_sigma(self):
-        m = float(self.sigmas.max())
-        if self.config.timestep_spacing in ("linspace", "trailing"):
-            return m
-        return (m ** 2 + 1) ** 0.5
-
-    @property
-    def step_index(self):
-        return self._step_index
+        self._capture(locals())
+        self._build()
 
     coefficient_walk = _coefficient_walk("_step_index")   # (ancestral_coefficients, model_input_scale)
 
-    def set_timesteps(self, num_inference_steps: int):
-        c, T = self.config, self.config.num_train_timesteps
-        self.num_inference_steps = n = num_inference_steps
-        if c.timestep_spacing == "linspace":   # (not rounded)
-            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        sig_all = np.array(self._train_sigmas)
-        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
-        self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
-        self.timesteps = ts.astype(np.float32)
-        self._step_index = None
-
-    _init_step_index = EulerDiscreteScheduler._init_step_index
-    scale_model_input = EulerDiscreteScheduler.scale_model_input
-    model_input_scale = EulerDiscreteScheduler.model_input_scale
-    add_noise = EulerDiscreteScheduler.add_noise
-
     def _check(self, timestep):
-        pt = self.config.prediction_type
-        if pt == "sample":
-            raise NotImplementedError("prediction_type not implemented yet: sample")
-        if pt not in ("epsilon", "v_prediction"):
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        _check_prediction_type(self.config.prediction_type)
+        self._require_steps()
         if self._step_index is None:
             self._init_step_index(timestep)
 
@@ -595,12 +756,8 @@ class EulerAncestralDiscreteScheduler:
         self._check(timestep)
         s, c, dt = (float(v) for v in self._ancestral_sigmas())
         self._step_index += 1
-        if self.config.prediction_type == "v_prediction":
-            # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
-            a, b = 1.0 + dt * s / (s ** 2 + 1), dt / (s ** 2 + 1) ** 0.5
-        else:
-            a, b = 1.0, dt
-        if not all(np.isfinite(v) for v in (a, b, c)):
+        a, b = _euler_ab(self.config.prediction_type, s, dt)
+        if not all(map(isfinite, (a, b, c))):
             raise NotImplementedError("a non-finite row has no linear-update form")
         return a, b, c
 
@@ -612,10 +769,7 @@ class EulerAncestralDiscreteScheduler:
                              "is not supported. Make sure to pass one of the `scheduler.timesteps` as a timestep.")
         self._check(timestep)
         s, s_up, dt = (float(v) for v in self._ancestral_sigmas())
-        if self.config.prediction_type == "epsilon":
-            x0 = sample - s * model_output
-        else:
-            x0 = model_output * (-s / (s ** 2 + 1) ** 0.5) + (sample / (s ** 2 + 1))
+        x0 = _sigma_x0(self.config.prediction_type, sample, model_output, s)
         derivative = (sample - x0) / s
         prev = sample + derivative * dt
         if noise is None:
@@ -624,11 +778,8 @@ class EulerAncestralDiscreteScheduler:
         self._step_index += 1
         return _out(prev, return_dict, pred_original_sample=x0)
 
-    def __len__(self):
-        return self.config.num_train_timesteps
 
-
-class HeunDiscreteScheduler:
+class HeunDiscreteScheduler(_SigmaSpace, _Schedule):
     """"Heun" (scheduling_heun_discrete.py:71-480): the second-order k-diffusion sampler, two model evaluations per step. Every
     timestep but the first appears twice; the first evaluation of a pair takes an Euler step and parks the sample, the derivative and
     dt, the second averages the two derivatives and steps again from the parked sample; the last step (to sigma = 0) is a plain Euler
@@ -636,38 +787,18 @@ class HeunDiscreteScheduler:
     implemented. Both stages are linear in the current sample, the model output and the parked state: ``heun_coefficients`` returns
     (p, q, h, g, second) for the library's ``mi355x_sd_heun_update``."""
     order = 2
+    _train_arithmetic = "tensor"
+    _names_class_in_refusal = True
+    _float32_init_sigma = True
+    _all_values_by_set_timesteps = True
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  beta_schedule: str = "linear", trained_betas=None, prediction_type: str = "epsilon",
                  use_karras_sigmas: bool = False, clip_sample: bool = False, clip_sample_range: float = 1.0,
                  timestep_spacing: str = "linspace", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        if trained_betas is not None:
-            raise NotImplementedError("HeunDiscreteScheduler(mi355x): trained_betas is not implemented")
-        # the training table in float32 TENSOR arithmetic, as the reference builds it (:128-146) and as
-        # EulerAncestralDiscreteScheduler does here (see there for what the float64 linspace of _make_betas costs)
-        if beta_schedule == "linear":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{beta_schedule} does is not implemented for {self.__class__}")
-        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
-        self.alphas_cumprod = alphas_cumprod.numpy()
-        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
+        self._capture(locals())
+        self._build()
         self.use_karras_sigmas = use_karras_sigmas
-        self.set_timesteps(num_train_timesteps)   # "set all values" (:149)
-
-    @property
-    def init_noise_sigma(self):
-        m = np.float32(self.sigmas.max())
-        if self.config.timestep_spacing in ("linspace", "trailing"):
-            return float(m)
-        return float(np.sqrt(m * m + np.float32(1.0)))   # float32, as the reference's tensor expression (max ** 2 + 1) ** 0.5
-
-    @property
-    def step_index(self):
-        return self._step_index
 
     @property
     def state_in_first_order(self):
@@ -676,47 +807,16 @@ class HeunDiscreteScheduler:
     coefficient_walk = _coefficient_walk("_step_index", "dt")   # (heun_coefficients, model_input_scale)
 
     def set_timesteps(self, num_inference_steps: int):
-        c, T = self.config, self.config.num_train_timesteps
-        self.num_inference_steps = n = num_inference_steps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        sig_all = np.array(self._train_sigmas)
-        log_sig = np.log(sig_all)
-        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
-        if c.use_karras_sigmas:   # (:304-327; the timesteps are not rounded)
-            rho = 7.0
-            lo, hi = sig[-1].item() ** (1 / rho), sig[0].item() ** (1 / rho)
-            sig = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
-            ts = np.array([EulerDiscreteScheduler._sigma_to_t(s, log_sig) for s in sig])
-        sig = np.concatenate([sig, [0.0]]).astype(np.float32)
-        ts = ts.astype(np.float32)
+        sig, ts = self._spaced_sigmas(num_inference_steps)   # (:213-277; the Karras timesteps are not rounded, :304-327)
         # [s0, s1, s1, ..., s_{n-1}, s_{n-1}, 0] and [t0, t1, t1, ..., t_{n-1}, t_{n-1}]: 2n sigmas, 2n - 1 timesteps
         self.sigmas = np.concatenate([sig[:1], np.repeat(sig[1:-1], 2), sig[-1:]])
         self.timesteps = np.concatenate([ts[:1], np.repeat(ts[1:], 2)])
+        self._reset()
+
+    def _reset(self):
         self.prev_derivative = self.dt = self.sample = None
         self._step_index: Optional[int] = None
         self._index_counter = {}
-
-    def index_for_timestep(self, timestep, schedule_timesteps=None):
-        """(:154-170) before any step: the second of two matching indices (the only one if single); afterwards the one the
-        counter of ``step`` calls at this timestep points to"""
-        ts = self.timesteps if schedule_timesteps is None else schedule_timesteps
-        t = float(timestep)
-        idx = np.nonzero(np.asarray(ts) == np.float32(t))[0]
-        if len(self._index_counter) == 0:
-            pos = 1 if len(idx) > 1 else 0
-        else:
-            pos = self._index_counter.setdefault(t, 0)
-        return int(idx[pos])
-
-    _init_step_index = EulerDiscreteScheduler._init_step_index
 
     def _sigma(self, i, dtype):
         """sigmas[i] as a 0-dim tensor of `dtype`: the reference casts its sigma tensor to the model output's dtype (:376-377), so the
@@ -729,15 +829,8 @@ class HeunDiscreteScheduler:
         sigma = self._sigma(self._step_index, sample.dtype)
         return sample / ((sigma ** 2 + 1) ** 0.5)
 
-    def model_input_scale(self, timestep) -> float:
-        if self._step_index is None:
-            self._init_step_index(timestep)
-        return 1.0 / ((float(self.sigmas[self._step_index]) ** 2 + 1) ** 0.5)
-
     def _check(self, timestep):
-        pt = self.config.prediction_type
-        if pt not in ("epsilon", "v_prediction", "sample"):
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
+        _check_prediction_type(self.config.prediction_type, ("epsilon", "v_prediction", "sample"))
         if self._step_index is None:
             self._init_step_index(timestep)
 
@@ -760,25 +853,15 @@ class HeunDiscreteScheduler:
             s_in, h, g, second = float(self.sigmas[i]), float(self.dt) / 2, 1.0, 1.0
             self.dt = None
         self._step_index += 1
-        pt = self.config.prediction_type
-        with np.errstate(all="ignore"):
-            s_in = np.float64(s_in)
-            if pt == "epsilon":
-                p, q = 0.0, 1.0
-            elif pt == "v_prediction":
-                # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
-                p, q = float(s_in / (s_in ** 2 + 1)), float(1.0 / (s_in ** 2 + 1) ** 0.5)
-            else:
-                p, q = float(1.0 / s_in), float(-1.0 / s_in)
-        if not all(np.isfinite(v) for v in (p, q, h)):
+        p, q = _sigma_derivative_pq(self.config.prediction_type, s_in)
+        if not all(map(isfinite, (p, q, h))):
             raise NotImplementedError("a non-finite row has no linear-update form")
         return p, q, h, g, second
 
     def step(self, model_output, timestep, sample, return_dict: bool = True):
         """(:349-455) line by line; the sigmas enter as 0-dim tensors of the model output's dtype"""
         self._check(timestep)
-        t = float(timestep)
-        self._index_counter[t] = self._index_counter.get(t, 0) + 1
+        self._count_step(timestep)
         i, dtype, c = self._step_index, model_output.dtype, self.config
         first = self.state_in_first_order
         if first:
@@ -786,13 +869,7 @@ class HeunDiscreteScheduler:
         else:   # 2nd order / Heun's method
             sigma, sigma_next = self._sigma(i - 1, dtype), self._sigma(i, dtype)
         sigma_hat = sigma   # gamma = 0
-        sigma_input = sigma_hat if first else sigma_next
-        if c.prediction_type == "epsilon":
-            x0 = sample - sigma_input * model_output
-        elif c.prediction_type == "v_prediction":
-            x0 = model_output * (-sigma_input / (sigma_input ** 2 + 1) ** 0.5) + (sample / (sigma_input ** 2 + 1))
-        else:
-            x0 = model_output
+        x0 = _sigma_x0(c.prediction_type, sample, model_output, sigma_hat if first else sigma_next)
         if c.clip_sample:
             x0 = x0.clip(-c.clip_sample_range, c.clip_sample_range)
         if first:
@@ -808,21 +885,8 @@ class HeunDiscreteScheduler:
         self._step_index += 1
         return _out(prev, return_dict)
 
-    def add_noise(self, original_samples, noise, timesteps):
-        """(:457-477) x + noise * sigma[index_for_timestep of each timestep]"""
-        ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps, dtype=np.float32))
-        idx = [self.index_for_timestep(t) for t in ts]
-        sigma = torch.as_tensor(np.asarray(self.sigmas, dtype=np.float32)[idx]).to(original_samples.device,
-                                                                                  original_samples.dtype)
-        while sigma.dim() < original_samples.dim():
-            sigma = sigma.unsqueeze(-1)
-        return original_samples + noise * sigma
 
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-
-class KDPM2DiscreteScheduler:
+class KDPM2DiscreteScheduler(_SigmaSpace, _Schedule):
     """"DPM2" (scheduling_k_dpm_2_discrete.py:71-487): the second-order k-diffusion midpoint sampler, two model evaluations per step.
     The first evaluation of a step takes an Euler step to ``sigma_interpol``, the geometric mean of the step's two sigmas, and parks
     the sample; the second is made there (its timestep comes from ``_sigma_to_t``) and takes the whole step from the parked sample
@@ -836,30 +900,17 @@ class KDPM2DiscreteScheduler:
     (``sigmas_interpol``, and the ancestral class's ``sigmas_up`` / ``sigmas_down``) float32, and so does ``step`` -- but for a float64
     model output, which takes them in float64 too (the float64 loops of the tests are this project's measuring stick)."""
     order = 2
+    _train_arithmetic = "tensor"
+    _names_class_in_refusal = True
+    _float32_init_sigma = True
+    _karras_rounded = True   # (:252)
+    _all_values_by_set_timesteps = True
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  beta_schedule: str = "linear", trained_betas=None, use_karras_sigmas: bool = False,
                  prediction_type: str = "epsilon", timestep_spacing: str = "linspace", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        if trained_betas is not None:
-            raise NotImplementedError(f"{self.__class__.__name__}(mi355x): trained_betas is not implemented")
-        # the training table in float32 TENSOR arithmetic, as HeunDiscreteScheduler builds it
-        if beta_schedule == "linear":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        elif beta_schedule == "scaled_linear":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        else:
-            raise NotImplementedError(f"{beta_schedule} does is not implemented for {self.__class__}")
-        alphas_cumprod = torch.cumprod(1.0 - betas, 0)
-        self.alphas_cumprod = alphas_cumprod.numpy()
-        self._train_sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
-        self.set_timesteps(num_train_timesteps, num_train_timesteps)   # "set all values" (:142)
-
-    init_noise_sigma = HeunDiscreteScheduler.init_noise_sigma
-
-    @property
-    def step_index(self):
-        return self._step_index
+        self._capture(locals())
+        self._build()
 
     @property
     def state_in_first_order(self):
@@ -881,43 +932,23 @@ class KDPM2DiscreteScheduler:
         return self.sigmas[i - 1], self.sigmas_interpol[i], self.sigmas[i], None
 
     def set_timesteps(self, num_inference_steps: int, num_train_timesteps: Optional[int] = None):
-        c, T = self.config, num_train_timesteps or self.config.num_train_timesteps
-        self.num_inference_steps = n = num_inference_steps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n, dtype=np.float32)[::-1].copy()
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (T // n)).round()[::-1].copy().astype(np.float32) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = (np.arange(T, 0, -T / n)).round().copy().astype(np.float32) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        sig_all = np.array(self._train_sigmas)
-        log_sig = np.log(sig_all)
-        sig = np.interp(ts, np.arange(0, len(sig_all)), sig_all)
-        if c.use_karras_sigmas:   # (here the timesteps ARE rounded, :252)
-            rho = 7.0
-            lo, hi = sig[-1].item() ** (1 / rho), sig[0].item() ** (1 / rho)
-            sig = (hi + np.linspace(0, 1, n) * (lo - hi)) ** rho
-            ts = np.array([EulerDiscreteScheduler._sigma_to_t(s, log_sig) for s in sig]).round()
-        sig = torch.from_numpy(np.concatenate([sig, [0.0]]).astype(np.float32))
+        sig, ts = self._spaced_sigmas(num_inference_steps, num_train_timesteps)
+        sig = torch.from_numpy(sig)
         # entries no evaluation reads go through log(0) and inf - inf on the way, as in the reference
         tables, between = self._tables(sig)
         for k, v in dict(tables, sigmas=sig).items():   # [v0, v1, v1, ..., vn, vn, vn]: 2n + 2 entries
             setattr(self, k, torch.cat([v[:1], v[1:].repeat_interleave(2), v[-1:]]).numpy())
         with np.errstate(all="ignore"):
             # (one call over the array: the per-element arithmetic of the reference's loop over _sigma_to_t)
-            t_interpol = EulerDiscreteScheduler._sigma_to_t(tables["sigmas_interpol"].numpy(), log_sig).astype(np.float32)
-        ts = ts.astype(np.float32)
+            t_interpol = _sigma_to_t(tables["sigmas_interpol"].numpy(), np.log(np.array(self._train_sigmas))).astype(np.float32)
         # [t0, t'0, t1, t'1, ..., t_{n-1}]: 2n - 1 timesteps, t'k the timestep of the sigma stage 2 of step k is evaluated at
         self.timesteps = np.concatenate([ts[:1], np.stack((t_interpol[between], ts[1:]), axis=-1).reshape(-1)])
+        self._reset()
+
+    def _reset(self):
         self.sample = None
         self._step_index: Optional[int] = None
         self._index_counter = {}
-
-    index_for_timestep = HeunDiscreteScheduler.index_for_timestep
-    _init_step_index = EulerDiscreteScheduler._init_step_index
-    add_noise = HeunDiscreteScheduler.add_noise
 
     def _sigma_in(self):
         """the float32 sigma the model is evaluated at now: ``sigmas`` in stage 1, ``sigmas_interpol`` in stage 2 (:200-204)"""
@@ -935,13 +966,6 @@ class KDPM2DiscreteScheduler:
             self._init_step_index(timestep)
         return 1.0 / ((float(self._sigma_in()) ** 2 + 1) ** 0.5)
 
-    def _check_prediction_type(self):
-        pt = self.config.prediction_type
-        if pt == "sample":
-            raise NotImplementedError("prediction_type not implemented yet: sample")
-        if pt not in ("epsilon", "v_prediction"):
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, or `v_prediction`")
-
     def dpm2_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
         """(p, q, h, c, second): the row of the evaluation ``step`` would take now, composed in float64 from the float32 schedule
         values ``step`` uses; advances the index and the stage as ``step`` does. With d = p*sample + q*model_output, the derivative
@@ -952,7 +976,7 @@ class KDPM2DiscreteScheduler:
         A non-finite row has no such form: NotImplementedError."""
         if self._step_index is None:
             self._init_step_index(timestep)
-        self._check_prediction_type()
+        _check_prediction_type(self.config.prediction_type)
         i, first = self._step_index, self.state_in_first_order
         s, s_interpol, s_to, s_up = (None if v is None else float(v) for v in self._stage(i, first))
         if first:
@@ -962,35 +986,25 @@ class KDPM2DiscreteScheduler:
             s_in, h, c, second = s_interpol, s_to - s, 0.0 if s_up is None else s_up, 1.0
             self.sample = None
         self._step_index += 1
-        with np.errstate(all="ignore"):
-            s_in = np.float64(s_in)
-            if self.config.prediction_type == "epsilon":
-                p, q = 0.0, 1.0
-            else:   # step(): x0 = x / (s^2 + 1) - v s / sqrt(s^2 + 1), so (x - x0) / s = x s / (s^2 + 1) + v / sqrt(s^2 + 1)
-                p, q = float(s_in / (s_in ** 2 + 1)), float(1.0 / (s_in ** 2 + 1) ** 0.5)
-        if not all(np.isfinite(v) for v in (p, q, h, c)):
+        p, q = _sigma_derivative_pq(self.config.prediction_type, s_in)
+        if not all(map(isfinite, (p, q, h, c))):
             raise NotImplementedError("a non-finite row has no linear-update form")
         return p, q, h, c, second
 
     def _begin(self, timestep):
         if self._step_index is None:
             self._init_step_index(timestep)
-        t = float(timestep)
-        self._index_counter[t] = self._index_counter.get(t, 0) + 1
+        self._count_step(timestep)
 
     def _advance(self, model_output, sample, noise, return_dict):
         """(:411-462, ancestral :425-478) line by line from the prediction-type branch on"""
         i, dtype, first = self._step_index, model_output.dtype, self.state_in_first_order
-        other = torch.promote_types(torch.float32, dtype)
+        other = torch.promote_types(torch.float32, dtype)   # (the tables beside ``sigmas`` stay float32 in the reference)
         s, s_interpol, s_to, s_up = self._stage(i, first)
         sigma_hat = torch.tensor(float(s), dtype=dtype)   # gamma = 0
         sigma_interpol = torch.tensor(float(s_interpol), dtype=other)
-        self._check_prediction_type()
-        sigma_input = sigma_hat if first else sigma_interpol
-        if self.config.prediction_type == "epsilon":
-            x0 = sample - sigma_input * model_output
-        else:
-            x0 = model_output * (-sigma_input / (sigma_input ** 2 + 1) ** 0.5) + (sample / (sigma_input ** 2 + 1))
+        _check_prediction_type(self.config.prediction_type)
+        x0 = _sigma_x0(self.config.prediction_type, sample, model_output, sigma_hat if first else sigma_interpol)
         if first:
             derivative = (sample - x0) / sigma_hat
             dt = sigma_interpol - sigma_hat
@@ -1009,9 +1023,6 @@ class KDPM2DiscreteScheduler:
     def step(self, model_output, timestep, sample, return_dict: bool = True):
         self._begin(timestep)
         return self._advance(model_output, sample, None, return_dict)
-
-    def __len__(self):
-        return self.config.num_train_timesteps
 
 
 class KDPM2AncestralDiscreteScheduler(KDPM2DiscreteScheduler):
@@ -1047,12 +1058,11 @@ class KDPM2AncestralDiscreteScheduler(KDPM2DiscreteScheduler):
         return self._advance(model_output, sample, noise, return_dict)
 
 
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_Schedule):
     """The fast multistep solver most SD pipelines switch to (20-25 steps; the reference's DiT example uses it). Implemented:
     ``algorithm_type`` "dpmsolver++" / "dpmsolver", ``solver_order`` 1-2, "midpoint" / "heun", epsilon / v_prediction / sample,
     ``lower_order_final``, ``euler_at_final``, Karras sigmas. Not implemented (NotImplementedError): the SDE variants,
     third order, thresholding, ``use_lu_lambdas``, a finite ``lambda_min_clipped``."""
-    order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", solver_order: int = 2, prediction_type: str = "epsilon",
@@ -1061,7 +1071,7 @@ class DPMSolverMultistepScheduler:
                  euler_at_final: bool = False, use_karras_sigmas: bool = False, use_lu_lambdas: bool = False,
                  lambda_min_clipped: float = -float("inf"), variance_type: Optional[str] = None,
                  timestep_spacing: str = "linspace", steps_offset: int = 0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        self._capture(locals())
         if algorithm_type not in ("dpmsolver", "dpmsolver++"):
             raise NotImplementedError(f"{algorithm_type} is not implemented for {self.__class__}")
         if solver_type not in ("midpoint", "heun"):
@@ -1069,166 +1079,101 @@ class DPMSolverMultistepScheduler:
         if solver_order not in (1, 2) or thresholding or use_lu_lambdas or lambda_min_clipped != -float("inf") or variance_type:
             raise NotImplementedError("DPMSolverMultistepScheduler(mi355x): solver_order 3, thresholding, use_lu_lambdas, "
                                       "lambda_min_clipped and learned variance are not implemented")
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
-        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy().astype(np.int64)
-        self.model_outputs = [None] * solver_order
+        self._build()
+
+    def _reset(self):
+        self.model_outputs = [None] * self.config.solver_order
         self.lower_order_nums = 0
         self._step_index = None
-
-    @property
-    def step_index(self):
-        return self._step_index
 
     coefficient_walk = _coefficient_walk("_step_index", "lower_order_nums", "model_outputs")   # (multistep_coefficients)
 
     def set_timesteps(self, num_inference_steps: int):
-        c, n = self.config, num_inference_steps
-        last = c.num_train_timesteps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, last - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n + 1) * (last // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = np.arange(last, 0, -c.num_train_timesteps / n).round().copy().astype(np.int64) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        sigmas = np.array(((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5)
-        log_sigmas = np.log(sigmas)
-        if c.use_karras_sigmas:
-            s = np.flip(sigmas).copy()
-            rho, ramp = 7.0, np.linspace(0, 1, n)
-            s = (s[0] ** (1 / rho) + ramp * (s[-1] ** (1 / rho) - s[0] ** (1 / rho))) ** rho
-            ts = np.array([EulerDiscreteScheduler._sigma_to_t(x, log_sigmas) for x in s]).round()
-            sigmas = np.concatenate([s, s[-1:]]).astype(np.float32)
-        else:
-            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
-            sigma_last = ((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5
-            sigmas = np.concatenate([sigmas, [sigma_last]]).astype(np.float32)
-        self.sigmas, self.timesteps = sigmas, ts.astype(np.int64)
-        self.num_inference_steps = len(ts)
-        self.model_outputs = [None] * c.solver_order
-        self.lower_order_nums = 0
-        self._step_index = None
-
-    def scale_model_input(self, sample, *args, **kwargs):
-        return sample
-
-    @staticmethod
-    def _sigma_to_alpha_sigma_t(sigma):
-        alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
-        return alpha_t, sigma * alpha_t
+        self.sigmas, self.timesteps = _multistep_schedule(self.alphas_cumprod, self.config, num_inference_steps,
+                                                          karras_ends_as_float=False)
+        self.num_inference_steps = len(self.timesteps)
+        self._reset()
 
     def convert_model_output(self, model_output, sample):
         """model output -> x0 prediction (dpmsolver++) or epsilon prediction (dpmsolver), :407-506"""
-        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[self._step_index]))
-        pt = self.config.prediction_type
-        if pt not in ("epsilon", "sample", "v_prediction"):
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction` for the "
-                             "DPMSolverMultistepScheduler.")
-        if self.config.algorithm_type == "dpmsolver++":
-            return (sample - s * model_output) / a if pt == "epsilon" else model_output if pt == "sample" else a * sample - s * model_output
-        return model_output if pt == "epsilon" else (sample - a * model_output) / s if pt == "sample" else a * model_output + s * sample
+        c = self.config
+        a, s = _alpha_sigma_floats(self.sigmas[self._step_index])
+        _check_alpha_prediction_type(c.prediction_type, "DPMSolverMultistepScheduler")
+        return _alpha_convert(c.prediction_type, c.algorithm_type == "dpmsolver++", a, s, sample, model_output)
 
-    def _init_step_index(self, timestep):
-        c = np.nonzero(self.timesteps == int(timestep))[0]
-        self._step_index = len(self.timesteps) - 1 if len(c) == 0 else int(c[1] if len(c) > 1 else c[0])
+    _init_step_index = _init_multistep_index
+    _sigma_to_alpha_sigma_t = staticmethod(_sigma_to_alpha_sigma_t)
 
-    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
-        if self._step_index is None:
-            self._init_step_index(timestep)
+    def _update_scalars(self):
+        """The scalars of the update from sigma index ``_step_index`` to the next -> (A, b, c, plus, r_inv), each a float of a float32
+        numpy expression (alpha_t, sigma_t, lambda, h and the coefficients, as the reference's float32 tensors give them):
+            prev = A x - b m0                                  first order (:508-575), c = plus = r_inv = None
+            prev = A x - b m0 -/+ c (r_inv (m0 - m1))          second-order multistep (:577-698), r_inv = 1 / r0; + where `plus`
+        ``step`` and ``multistep_coefficients`` both read this and nothing else of the schedule. b and c come with the sign the
+        reference's expressions give them, and `plus` apart, not folded in: a Karras schedule repeats its last sigma, h = 0 gives
+        r_inv = 0 like the reference and heun's 0 / 0 a NaN c, and negating a NaN flips the sign bit ``step`` then returns."""
         c, n, i = self.config, len(self.timesteps), self._step_index
         lower_order_final = i == n - 1 and (c.euler_at_final or (c.lower_order_final and n < 15))
-        lower_order_second = i == n - 2 and c.lower_order_final and n < 15
-        m = self.convert_model_output(model_output, sample)
-        self.model_outputs = self.model_outputs[1:] + [m]
-        at, st = self._sigma_to_alpha_sigma_t(self.sigmas[i + 1])
-        a0, s0 = self._sigma_to_alpha_sigma_t(self.sigmas[i])
+        at, st = _sigma_to_alpha_sigma_t(self.sigmas[i + 1])
+        a0, s0 = _sigma_to_alpha_sigma_t(self.sigmas[i])
         lt, l0 = np.log(at) - np.log(st), np.log(a0) - np.log(s0)
         h = lt - l0
-        pp = c.algorithm_type == "dpmsolver++"
-        f = float
-        if c.solver_order == 1 or self.lower_order_nums < 1 or lower_order_final:    # first-order update (:508-575)
-            prev = (f(st / s0) * sample - f(at * (np.exp(-h) - 1.0)) * m) if pp else (f(at / a0) * sample - f(st * (np.exp(h) - 1.0)) * m)
-        else:                                                                          # second-order multistep (:577-698)
-            a1, s1 = self._sigma_to_alpha_sigma_t(self.sigmas[i - 1])
-            h_0 = l0 - (np.log(a1) - np.log(s1))
-            with np.errstate(divide="ignore"):   # Karras schedules repeat the last sigma: h = 0 -> 1 / r0 = 0, like the reference
-                r_inv = f(1.0 / (h_0 / h))
-            d0, d1 = self.model_outputs[-1], r_inv * (self.model_outputs[-1] - self.model_outputs[-2])
-            if pp:
-                prev = f(st / s0) * sample - f(at * (np.exp(-h) - 1.0)) * d0
-                prev = prev - f(0.5 * at * (np.exp(-h) - 1.0)) * d1 if c.solver_type == "midpoint" else \
-                    prev + f(at * ((np.exp(-h) - 1.0) / h + 1.0)) * d1
-            else:
-                prev = f(at / a0) * sample - f(st * (np.exp(h) - 1.0)) * d0
-                prev = prev - f(0.5 * st * (np.exp(h) - 1.0)) * d1 if c.solver_type == "midpoint" else \
-                    prev - f(st * ((np.exp(h) - 1.0) / h - 1.0)) * d1
-        _ = lower_order_second   # (with solver_order <= 2 the second-order branch is taken whenever history exists)
-        if self.lower_order_nums < c.solver_order:
+        pp, f = c.algorithm_type == "dpmsolver++", float
+        A, b = (f(st / s0), f(at * (np.exp(-h) - 1.0))) if pp else (f(at / a0), f(st * (np.exp(h) - 1.0)))
+        if c.solver_order == 1 or self.lower_order_nums < 1 or lower_order_final:
+            return A, b, None, None, None
+        # (with solver_order <= 2 the second-order branch is taken whenever history exists)
+        a1, s1 = _sigma_to_alpha_sigma_t(self.sigmas[i - 1])
+        h_0 = l0 - (np.log(a1) - np.log(s1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r_inv = f(1.0 / (h_0 / h))
+            if c.solver_type == "midpoint":
+                return A, b, f(0.5 * at * (np.exp(-h) - 1.0)) if pp else f(0.5 * st * (np.exp(h) - 1.0)), False, r_inv
+            return A, b, f(at * ((np.exp(-h) - 1.0) / h + 1.0)) if pp else f(st * ((np.exp(h) - 1.0) / h - 1.0)), pp, r_inv
+
+    def _advance(self):
+        if self.lower_order_nums < self.config.solver_order:
             self.lower_order_nums += 1
         self._step_index += 1
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
+        self._require_steps()
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        m = self.convert_model_output(model_output, sample)
+        self.model_outputs = self.model_outputs[1:] + [m]
+        A, b, c, plus, r_inv = self._update_scalars()
+        prev = A * sample - b * m
+        if c is not None:
+            d1 = r_inv * (m - self.model_outputs[-2])
+            prev = prev + c * d1 if plus else prev - c * d1
+        self._advance()
         return _out(prev, return_dict)
 
     def multistep_coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
         """(p, q, A, B, D) of this step's update as a linear map of the sample x, the model output e and the previous step's
         converted output m1:  m0 = p x + q e  (``convert_model_output``),  prev = A x + B m0 + D (m0 - m1) ; D = 0 on a first-order
-        step. Advances ``_step_index`` and ``lower_order_nums`` as ``step`` does. Every schedule value (alpha_t, sigma_t, lambda, h and
-        the coefficient expressions) is the float32 numpy expression of ``step`` / ``convert_model_output``, so both see the same
-        numbers; the five are composed from them in float64. NotImplementedError when one of them is not finite (heun's 0 / 0 on
-        a Karras schedule's repeated last sigma, where ``step`` itself yields NaN)."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        step. Advances ``_step_index`` and ``lower_order_nums`` as ``step`` does. The schedule values are ``_update_scalars``' and the
+        alpha_t, sigma_t of ``convert_model_output``, the very numbers ``step`` reads; the five are composed from them in float64.
+        NotImplementedError when one of them is not finite (heun's 0 / 0 on a Karras schedule's repeated last sigma, where ``step``
+        itself yields NaN)."""
+        self._require_steps()
         if self._step_index is None:
             self._init_step_index(timestep)
-        c, n, i = self.config, len(self.timesteps), self._step_index
-        lower_order_final = i == n - 1 and (c.euler_at_final or (c.lower_order_final and n < 15))
-        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[i]))
-        pt, pp, f = c.prediction_type, c.algorithm_type == "dpmsolver++", float
-        if pt not in ("epsilon", "sample", "v_prediction"):
-            raise NotImplementedError(f"prediction_type {pt}")
-        if pp:
-            p, q = (1.0 / a, -s / a) if pt == "epsilon" else (0.0, 1.0) if pt == "sample" else (a, -s)
-        else:
-            p, q = (0.0, 1.0) if pt == "epsilon" else (1.0 / s, -a / s) if pt == "sample" else (s, a)
-        at, st = self._sigma_to_alpha_sigma_t(self.sigmas[i + 1])
-        a0, s0 = self._sigma_to_alpha_sigma_t(self.sigmas[i])
-        lt, l0 = np.log(at) - np.log(st), np.log(a0) - np.log(s0)
-        h = lt - l0
-        A, B = (f(st / s0), -f(at * (np.exp(-h) - 1.0))) if pp else (f(at / a0), -f(st * (np.exp(h) - 1.0)))
-        D = 0.0
-        if not (c.solver_order == 1 or self.lower_order_nums < 1 or lower_order_final):
-            a1, s1 = self._sigma_to_alpha_sigma_t(self.sigmas[i - 1])
-            h_0 = l0 - (np.log(a1) - np.log(s1))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                r_inv = f(1.0 / (h_0 / h))
-                if c.solver_type == "midpoint":
-                    D = -f(0.5 * at * (np.exp(-h) - 1.0)) * r_inv if pp else -f(0.5 * st * (np.exp(h) - 1.0)) * r_inv
-                else:
-                    D = f(at * ((np.exp(-h) - 1.0) / h + 1.0)) * r_inv if pp else -f(st * ((np.exp(h) - 1.0) / h - 1.0)) * r_inv
-        if self.lower_order_nums < c.solver_order:
-            self.lower_order_nums += 1
-        self._step_index += 1
-        if not all(np.isfinite(v) for v in (p, q, A, B, D)):
+        cfg = self.config
+        if cfg.prediction_type not in ("epsilon", "sample", "v_prediction"):
+            raise NotImplementedError(f"prediction_type {cfg.prediction_type}")
+        a, s = _alpha_sigma_floats(self.sigmas[self._step_index])
+        p, q = _alpha_convert_pq(cfg.prediction_type, cfg.algorithm_type == "dpmsolver++", a, s)
+        A, b, c, plus, r_inv = self._update_scalars()
+        B, D = -b, 0.0 if c is None else (c if plus else -c) * r_inv
+        self._advance()
+        if not all(map(isfinite, (p, q, A, B, D))):
             raise NotImplementedError("a multistep coefficient of this step is not finite")
         return p, q, A, B, D
 
-    def add_noise(self, original_samples, noise, timesteps):
-        a = torch.as_tensor(self.alphas_cumprod)[timesteps].to(original_samples.device)
-        while a.dim() < original_samples.dim():
-            a = a.unsqueeze(-1)
-        return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
 
-    def __len__(self):
-        return self.config.num_train_timesteps
-
-
-class UniPCMultistepScheduler:
+class UniPCMultistepScheduler(_Schedule):
     """UniPC (scheduling_unipc_multistep.py:31-846): a B(h) predictor of order 1-3 (``multistep_uni_p_bh_update``) whose output the
     next step corrects with the model output it was evaluated at (``multistep_uni_c_bh_update``), usable at 8-15 steps. Implemented:
     ``solver_order`` 1-3, "bh1" / "bh2" ("midpoint" / "heun" / "logrho" become "bh2"), ``predict_x0``, epsilon / sample / v_prediction,
@@ -1236,7 +1181,6 @@ class UniPCMultistepScheduler:
     thresholding, ``solver_p``, ``trained_betas``.
     Both halves are linear in the tensors with scalars of the schedule alone: ``unipc_coefficients`` returns them as one row for the
     library's ``mi355x_sd_unipc_update``."""
-    order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", trained_betas=None, solver_order: int = 2, prediction_type: str = "epsilon",
@@ -1248,76 +1192,36 @@ class UniPCMultistepScheduler:
             if solver_type not in ("midpoint", "heun", "logrho"):
                 raise NotImplementedError(f"{solver_type} is not implemented for {self.__class__}")
             solver_type = "bh2"
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
+        self._capture(locals())
         if thresholding or solver_p is not None or trained_betas is not None or solver_order not in (1, 2, 3):
             raise NotImplementedError("UniPCMultistepScheduler(mi355x): thresholding, solver_p, trained_betas and solver_order "
                                       "outside 1-3 are not implemented")
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self.init_noise_sigma = 1.0
         self.predict_x0, self.disable_corrector, self.solver_p = predict_x0, disable_corrector, None
-        self.num_inference_steps = None
-        self.timesteps = np.linspace(0, num_train_timesteps - 1, num_train_timesteps, dtype=np.float32)[::-1].copy().astype(np.int64)
-        self.model_outputs = [None] * solver_order
         self.timestep_list = [None] * solver_order
+        self.this_order = None
+        self._build()
+
+    def _reset(self):
+        self.model_outputs = [None] * self.config.solver_order
         self.lower_order_nums = 0
         self.last_sample = None
-        self.this_order = None
         self._step_index = None
-
-    @property
-    def step_index(self):
-        return self._step_index
 
     coefficient_walk = _coefficient_walk("_step_index", "lower_order_nums", "model_outputs", "timestep_list", "last_sample",
                                          "this_order")   # (unipc_coefficients)
 
     def set_timesteps(self, num_inference_steps: int):
-        c, n, T = self.config, num_inference_steps, self.config.num_train_timesteps
-        if c.timestep_spacing == "linspace":
-            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif c.timestep_spacing == "leading":
-            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
-        elif c.timestep_spacing == "trailing":
-            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64) - 1
-        else:
-            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', "
-                             "'leading' or 'trailing'.")
-        sigmas = np.array(((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5)
-        if c.use_karras_sigmas:
-            log_sigmas = np.log(sigmas)
-            s = np.flip(sigmas).copy()
-            rho, ramp = 7.0, np.linspace(0, 1, n)
-            lo, hi = s[-1].item() ** (1 / rho), s[0].item() ** (1 / rho)
-            s = (hi + ramp * (lo - hi)) ** rho
-            ts = np.array([EulerDiscreteScheduler._sigma_to_t(x, log_sigmas) for x in s]).round()
-            sigmas = np.concatenate([s, s[-1:]]).astype(np.float32)
-        else:
-            sigmas = np.interp(ts, np.arange(0, len(sigmas)), sigmas)
-            sigma_last = ((1 - self.alphas_cumprod[0]) / self.alphas_cumprod[0]) ** 0.5
-            sigmas = np.concatenate([sigmas, [sigma_last]]).astype(np.float32)
-        self.sigmas, self.timesteps = sigmas, ts.astype(np.int64)
-        self.num_inference_steps = len(ts)
-        self.model_outputs = [None] * c.solver_order
-        self.lower_order_nums = 0
-        self.last_sample = None
-        self._step_index = None
+        self.sigmas, self.timesteps = _multistep_schedule(self.alphas_cumprod, self.config, num_inference_steps,
+                                                          karras_ends_as_float=True)
+        self.num_inference_steps = len(self.timesteps)
+        self._reset()
 
-    def scale_model_input(self, sample, *args, **kwargs):
-        return sample
+    _init_step_index = _init_multistep_index
+    _sigma_to_alpha_sigma_t = staticmethod(_sigma_to_alpha_sigma_t)
 
-    _sigma_to_alpha_sigma_t = staticmethod(DPMSolverMultistepScheduler._sigma_to_alpha_sigma_t)
-
-    def _convert_pq(self):
-        """(p, q) with convert_model_output = p * sample + q * model_output, from this step's float32 alpha_t and sigma_t"""
-        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[self._step_index]))
-        pt = self.config.prediction_type
-        if pt not in ("epsilon", "sample", "v_prediction"):
-            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction` for the "
-                             "UniPCMultistepScheduler.")
-        if self.predict_x0:
-            return (1.0 / a, -s / a) if pt == "epsilon" else (0.0, 1.0) if pt == "sample" else (a, -s)
-        return (0.0, 1.0) if pt == "epsilon" else (1.0 / s, -a / s) if pt == "sample" else (s, a)
+    def _alpha_sigma(self) -> Tuple[float, float]:
+        _check_alpha_prediction_type(self.config.prediction_type, "UniPCMultistepScheduler")
+        return _alpha_sigma_floats(self.sigmas[self._step_index])
 
     def convert_model_output(self, model_output, *args, sample=None, **kwargs):
         """model output -> x0 prediction (predict_x0) or epsilon prediction, :368-436"""
@@ -1325,12 +1229,7 @@ class UniPCMultistepScheduler:
             if len(args) < 2:
                 raise ValueError("missing `sample` as a required keyward argument")
             sample = args[1]
-        a, s = (float(v) for v in self._sigma_to_alpha_sigma_t(self.sigmas[self._step_index]))
-        pt = self.config.prediction_type
-        self._convert_pq()   # (the prediction_type check)
-        if self.predict_x0:
-            return (sample - s * model_output) / a if pt == "epsilon" else model_output if pt == "sample" else a * sample - s * model_output
-        return model_output if pt == "epsilon" else (sample - a * model_output) / s if pt == "sample" else a * model_output + s * sample
+        return _alpha_convert(self.config.prediction_type, self.predict_x0, *self._alpha_sigma(), sample, model_output)
 
     def _bh_scalars(self, i_t: int, i_s0: int, older, order: int, corrector: bool):
         """The float32 scalars of one B(h) update from sigma index i_s0 to i_t (:490-546 / :625-683), ``older`` the sigma indices of
@@ -1404,12 +1303,6 @@ class UniPCMultistepScheduler:
         return self._bh_update(last_sample, self.model_outputs[-1], [self.model_outputs[-(k + 1)] for k in range(1, order)],
                                this_model_output, sc)
 
-    def _init_step_index(self, timestep):
-        c = np.nonzero(self.timesteps == int(timestep))[0]
-        # "the sigma index that is taken for the **very** first `step` is always the second index": an img2img start on a
-        # duplicated timestep must not skip a sigma
-        self._step_index = len(self.timesteps) - 1 if len(c) == 0 else int(c[1] if len(c) > 1 else c[0])
-
     def _use_corrector(self):
         return self._step_index > 0 and self._step_index - 1 not in self.disable_corrector and self.last_sample is not None
 
@@ -1419,8 +1312,7 @@ class UniPCMultistepScheduler:
         return min(this_order, self.lower_order_nums + 1)   # warm-up of the multistep history
 
     def step(self, model_output, timestep, sample, return_dict: bool = True):
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        self._require_steps()
         if self._step_index is None:
             self._init_step_index(timestep)
         m = self.convert_model_output(model_output, sample=sample)   # at the UNCORRECTED sample, as the reference does
@@ -1448,12 +1340,11 @@ class UniPCMultistepScheduler:
         Every schedule value is the float32 numpy expression of ``step``; the row is composed from them in float64.
         NotImplementedError when a coefficient is not finite (a third-order solve on a Karras schedule's repeated last sigma,
         where ``step`` itself yields NaN)."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        self._require_steps()
         if self._step_index is None:
             self._init_step_index(timestep)
         i, f = self._step_index, float
-        p, q = self._convert_pq()
+        p, q = _alpha_convert_pq(self.config.prediction_type, self.predict_x0, *self._alpha_sigma())
         row = [p, q] + [0.0] * 10
         with np.errstate(divide="ignore", invalid="ignore"):
             if self._use_corrector():
@@ -1472,11 +1363,11 @@ class UniPCMultistepScheduler:
         if self.lower_order_nums < self.config.solver_order:
             self.lower_order_nums += 1
         self._step_index += 1
-        if not all(np.isfinite(v) for v in row):
+        if not all(map(isfinite, row)):
             raise NotImplementedError("a UniPC coefficient of this step is not finite")
         return tuple(row)
 
-    def add_noise(self, original_samples, noise, timesteps):
+    def add_noise(self, original_samples, noise, timesteps):   # (not _Schedule's: the CURRENT schedule's sigmas, not the table)
         """:822-843: alpha_t x + sigma_t noise with the sigma of each timestep's index in the CURRENT schedule"""
         ts = np.atleast_1d(np.asarray(timesteps.detach().cpu() if torch.is_tensor(timesteps) else timesteps)).astype(np.int64)
         idx = [int(np.nonzero(self.timesteps == t)[0].item()) for t in ts]
@@ -1486,9 +1377,6 @@ class UniPCMultistepScheduler:
         while alpha_t.dim() < original_samples.dim():
             alpha_t, sigma_t = alpha_t.unsqueeze(-1), sigma_t.unsqueeze(-1)
         return alpha_t * original_samples + sigma_t * noise
-
-    def __len__(self):
-        return self.config.num_train_timesteps
 
 
 class FlowMatchEulerDiscreteScheduler:
@@ -1528,32 +1416,21 @@ class FlowMatchEulerDiscreteScheduler:
         return _out(prev, return_dict)
 
 
-class LCMScheduler:
+class LCMScheduler(_Schedule):
     """Multistep consistency sampling for latent-consistency models / LCM-LoRA (scheduling_lcm.py:140-631): the schedule is a
     subset of the ``original_inference_steps`` distillation schedule, each step predicts x0, applies the boundary-condition
     scalings (c_skip, c_out) and -- except on the last step -- re-noises to the next timestep with fresh noise."""
-    order = 1
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  beta_schedule: str = "scaled_linear", original_inference_steps: int = 50, clip_sample: bool = False,
                  clip_sample_range: float = 1.0, set_alpha_to_one: bool = True, steps_offset: int = 0,
                  prediction_type: str = "epsilon", timestep_spacing: str = "leading", timestep_scaling: float = 10.0):
-        self.config = SimpleNamespace(**{k: v for k, v in locals().items() if k != "self"})
-        betas = _make_betas(num_train_timesteps, beta_start, beta_end, beta_schedule)
-        self.alphas_cumprod = np.cumprod(1.0 - betas, dtype=np.float32)
-        self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
-        self.timesteps = np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64)
+        self._capture(locals())
         self.custom_timesteps = False
-        self._step_index: Optional[int] = None
+        self._build()
 
-    @property
-    def step_index(self):
-        return self._step_index
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
+    def _reset(self):
+        self._step_index = None
 
     def set_timesteps(self, num_inference_steps: Optional[int] = None, original_inference_steps: Optional[int] = None,
                       timesteps=None, strength: float = 1.0):
@@ -1592,9 +1469,9 @@ class LCMScheduler:
             idx = np.floor(np.linspace(0, len(rev), num=num_inference_steps, endpoint=False)).astype(np.int64)
             ts = rev[idx]
         self.timesteps = ts.astype(np.int64)
-        self._step_index = None
+        self._reset()
 
-    def _init_step_index(self, timestep):
+    def _init_step_index(self, timestep):   # (not _Schedule's: a timestep outside the schedule is an IndexError here)
         idx = np.nonzero(self.timesteps == int(timestep))[0]
         self._step_index = int(idx[1] if len(idx) > 1 else idx[0])
 
@@ -1606,9 +1483,7 @@ class LCMScheduler:
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, *, noise=None):
         """-> prev_sample (and ``denoised``, the x0 estimate the LCM pipeline decodes). ``noise`` (extension): the re-noising
         draw, otherwise ``torch.randn`` from ``generator``."""
-        if self.num_inference_steps is None:
-            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating "
-                             "the scheduler")
+        self._require_steps()
         if self._step_index is None:
             self._init_step_index(timestep)
         c, t = self.config, int(timestep)
@@ -1641,11 +1516,5 @@ class LCMScheduler:
             return (prev, denoised)
         return SimpleNamespace(prev_sample=prev, denoised=denoised)
 
-    def add_noise(self, original_samples, noise, timesteps):
-        a = torch.as_tensor(self.alphas_cumprod)[torch.as_tensor(timesteps).long().cpu()].to(original_samples.device)
-        while a.dim() < original_samples.dim():
-            a = a.unsqueeze(-1)
-        return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
-
-    def __len__(self):
-        return self.config.num_train_timesteps
+    def _table_index(self, timesteps):
+        return torch.as_tensor(timesteps).long().cpu()   # (the other classes index the table with the timesteps as they come)
