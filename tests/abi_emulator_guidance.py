@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from tests.abi_emulator import Emulator, _flat
+from tests.step_forms import FORMS
 
 F32 = torch.float32
 THREADS = 1024
@@ -37,33 +38,57 @@ def tree_sum(v):
     return w[:, 0]
 
 
-def emulate(x, eu, et, coef, gs, gr, variance="two_pass"):
-    """x, eu, et fp32 [batch, n]; coef fp32 (a, b) -> fp32 [batch, n]"""
-    n = x.shape[1]
+def guided(eu, et, gs, gr, variance="two_pass", always=False):
+    """the guided (and rescaled) model output every step form starts from: eu, et (or None: no guidance) fp32 [batch, n] -> e fp32.
+    The rescale runs at gr > 0 (always: whatever gr is, as cfg_rescale_axpby's kernel does)"""
+    if et is None:
+        return eu
+    n = eu.shape[1]
     gs, gr = torch.tensor(gs, dtype=F32), torch.tensor(gr, dtype=F32)
     one = torch.tensor(1.0, dtype=F32)
-    c = (eu.double() + gs.double() * (et - eu).double()).to(F32)   # fma(gs, fl(t - u), u): one rounding after the exact product
-    inv_n, inv_nm1 = one / torch.tensor(float(n), dtype=F32), one / torch.tensor(float(n - 1), dtype=F32)
-    q = []
-    for v in (et, c):
-        s = tree_sum(v)
-        if variance == "one_pass":
-            q.append(tree_sum(v * v) - (s * inv_n) * s)
-        else:
-            d = v - (s * inv_n)[:, None]
-            q.append(tree_sum(d * d))
-    r = torch.sqrt(q[0] * inv_nm1) / torch.sqrt(q[1] * inv_nm1)
-    k = gr * r + (one - gr)
-    return coef[0] * x + coef[1] * (c * k[:, None])
+    e = (eu.double() + gs.double() * (et - eu).double()).to(F32)   # fma(gs, fl(t - u), u): one rounding after the exact product
+    if gr > 0 or always:
+        inv_n, inv_nm1 = one / torch.tensor(float(n), dtype=F32), one / torch.tensor(float(n - 1), dtype=F32)
+        q = []
+        for v in (et, e):
+            s = tree_sum(v)
+            if variance == "one_pass":
+                q.append(tree_sum(v * v) - (s * inv_n) * s)
+            else:
+                d = v - (s * inv_n)[:, None]
+                q.append(tree_sum(d * d))
+        r = torch.sqrt(q[0] * inv_nm1) / torch.sqrt(q[1] * inv_nm1)
+        e = e * (gr * r + (one - gr))[:, None]
+    return e
+
+
+def emulate(x, eu, et, coef, gs, gr, variance="two_pass"):
+    """x, eu, et fp32 [batch, n]; coef fp32 (a, b) -> fp32 [batch, n]"""
+    return coef[0] * x + coef[1] * guided(eu, et, gs, gr, variance, always=True)
 
 
 class GuidanceEmulator(Emulator):
+    def step_args(self, form, ptr, batch, per_sample, rescale, order=None):
+        """The argument rule of the step-tail entries, asserted once for all of them: what check_step_args of csrc/capi.hip refuses.
+        ptr: the pointers by operand name (tests/step_forms.py). No null but an optional operand; batch > 0 and per_sample >= 1
+        (>= 2 with the rescale); a written span overlaps no other written span and nothing read, unless the two are a pair of
+        form.same and one pointer. -> the operands as fp32 views of the memory, [planes,] batch, per_sample (None for a null; coef
+        flat): a plane the launch writes is written through its view."""
+        self.calls.append(form.entry)
+        assert all(p or k in form.optional for k, p in ptr.items()), "null pointer"
+        assert batch > 0 and per_sample >= (2 if rescale else 1)
+        planes = {k: form.written.get(k, 1) or order for k in ptr}
+        size = {k: form.width if k == "coef" else planes[k] * batch * per_sample for k in ptr}
+        for i, w in enumerate(form.written):
+            for r in list(form.written)[i + 1:] + [k for k in ptr if k not in form.written]:
+                apart = not ptr[r] or ptr[w] + 4 * size[w] <= ptr[r] or ptr[r] + 4 * size[r] <= ptr[w]
+                assert apart or ((w, r) in form.same and ptr[w] == ptr[r]), (w, r)
+        return {k: None if not p else _flat(p, size[k], F32) if k == "coef" else
+                _flat(p, size[k], F32).reshape(((planes[k],) if form.written.get(k, 1) != 1 else ()) + (batch, per_sample))
+                for k, p in ptr.items()}
+
     def mi355x_sd_cfg_rescale_axpby(self, x, eu, et, out, coef, gs, gr, batch, per_sample, stream):
-        self.calls.append("cfg_rescale_axpby")
-        assert batch > 0 and per_sample >= 2
-        n = batch * per_sample
-        assert out == x or out + 4 * n <= x or x + 4 * n <= out
-        assert all(out + 4 * n <= p or p + 4 * n <= out for p in (eu, et))
-        v = [_flat(p, n, F32).reshape(batch, per_sample) for p in (x, eu, et)]
-        _flat(out, n, F32).copy_(emulate(*v, _flat(coef, 2, F32), gs, gr).reshape(-1))
+        assert coef   # (its two floats are outside the overlap rule of this entry)
+        v = self.step_args(FORMS["guidance"], dict(x=x, eu=eu, et=et, out=out), batch, per_sample, True)
+        v["out"].copy_(emulate(v["x"], v["eu"], v["et"], _flat(coef, 2, F32), gs, gr))
         return 0

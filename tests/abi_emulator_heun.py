@@ -2,8 +2,7 @@
 ``on_emulator(UNet2DConditionModel, cfg, P, backend=HeunEmulator())``.
 
 emulate() restates the device kernels (csrc/step_tail.hip HeunStep in step_flat_kernel / step_rescale_kernel) in torch fp32, one
-rounding per operation and in the kernel's own order; the statistics of the rescale go through tree_sum of
-tests/abi_emulator_guidance.py. It is NOT scheduler.step: that is the generic loop the fused loop is compared against. ``fault``
+rounding per operation and in the kernel's own order; the guided (and rescaled) model output is guided() of tests/abi_emulator_guidance.py. It is NOT scheduler.step: that is the generic loop the fused loop is compared against. ``fault``
 restates a FAULT for tests/test_heun_bounds.py: "from_x" (stage 2 starts from x instead of the parked sample), "mul_nan" (the terms
 over state a stage must not read are formed with a zero weight instead of skipped: stage 1 adds 0 * S + 0 * D, stage 2 at g == 0
 forms g * D), "bf16_deriv" (the parked derivative rounded to bfloat16 before use)."""
@@ -11,28 +10,15 @@ from __future__ import annotations
 
 import torch
 
-from tests.abi_emulator import _flat
-from tests.abi_emulator_guidance import F32, GuidanceEmulator, tree_sum
+from tests.abi_emulator_guidance import F32, GuidanceEmulator, guided
+from tests.step_forms import FORMS
 
 
 def emulate(x, eu, et, S, D, coef, gs, gr, fault=None):
     """x, eu, et (or None), S, D fp32 [batch, n]; coef fp32 (p, q, h, g, second) -> (out, S, D) fp32 [batch, n]: the planes as the
     launch leaves them (stage 1: new ones; stage 2: the very tensors passed in)"""
-    n = x.shape[1]
     p, q, h, g, second = coef.to(F32)
-    e = eu
-    if et is not None:
-        gs, gr = torch.tensor(gs, dtype=F32), torch.tensor(gr, dtype=F32)
-        one = torch.tensor(1.0, dtype=F32)
-        e = (eu.double() + gs.double() * (et - eu).double()).to(F32)   # fma(gs, fl(t - u), u): one rounding after the exact product
-        if gr > 0:
-            inv_n, inv_nm1 = one / torch.tensor(float(n), dtype=F32), one / torch.tensor(float(n - 1), dtype=F32)
-            ss = []
-            for v in (et, e):
-                d = v - (tree_sum(v) * inv_n)[:, None]
-                ss.append(tree_sum(d * d))
-            r = torch.sqrt(ss[0] * inv_nm1) / torch.sqrt(ss[1] * inv_nm1)
-            e = e * (gr * r + (one - gr))[:, None]
+    e = guided(eu, et, gs, gr)
     d = p * x + q * e if p != 0 else q * e
     if second == 0:
         out = x + h * d
@@ -48,19 +34,10 @@ def emulate(x, eu, et, S, D, coef, gs, gr, fault=None):
 
 class HeunEmulator(GuidanceEmulator):
     def mi355x_sd_heun_update(self, x, eu, et, sample, deriv, out, coef, gs, gr, batch, per_sample, stream):
-        self.calls.append("heun_update")
-        assert x and eu and sample and deriv and out and coef and batch > 0 and per_sample >= (2 if et and gr > 0 else 1)
-        n = batch * per_sample
-        apart = lambda p, q, nq: p + 4 * n <= q or q + 4 * nq <= p  # noqa: E731
-        written = (out, sample, deriv)
-        assert out == x or apart(out, x, n)
-        assert all(apart(w, p, n) for w in written for p in (eu, et) if p) and all(apart(w, coef, 5) for w in written)
-        assert apart(sample, x, n) and apart(deriv, x, n) and apart(out, sample, n) and apart(out, deriv, n) and apart(sample, deriv, n)
-        k = _flat(coef, 5, F32)
-        v = [_flat(p, n, F32).reshape(batch, per_sample) if p else None for p in (x, eu, et, sample, deriv)]
-        o, S, D = emulate(*v, k, gs, gr if et else 0.0)
-        if k[4] == 0:
-            _flat(sample, n, F32).copy_(S.reshape(-1))
-            _flat(deriv, n, F32).copy_(D.reshape(-1))
-        _flat(out, n, F32).copy_(o.reshape(-1))
+        v = self.step_args(FORMS["heun"], dict(x=x, eu=eu, et=et, S=sample, D=deriv, out=out, coef=coef), batch, per_sample, et and gr > 0)
+        o, S, D = emulate(v["x"], v["eu"], v["et"], v["S"], v["D"], v["coef"], gs, gr if et else 0.0)
+        if v["coef"][4] == 0:
+            v["S"].copy_(S)
+            v["D"].copy_(D)
+        v["out"].copy_(o)
         return 0

@@ -2,7 +2,7 @@
 ``on_emulator(UNet2DConditionModel, cfg, P, backend=UniPCEmulator())``.
 
 emulate() restates the device kernels (csrc/misc.hip unipc_kernel / unipc_rescale_kernel) in torch fp32, one rounding per operation
-and in the kernel's own order; the guided (and rescaled) model output is the multistep emulation's (its m0 at p = 0, q = 1). It is NOT
+and in the kernel's own order; the guided (and rescaled) model output is guided() of tests/abi_emulator_guidance.py. It is NOT
 scheduler.step: that is the generic loop the fused loop is compared against. ``fault`` restates a FAULT for
 tests/test_unipc_bounds.py: "regroup" (the coefficient applied before the difference: C h_k - C h1, D h_k - D m_t), "mul_nan" (every
 term formed whatever its coefficient, the corrector blended in as corr * x_c + (1 - corr) * x instead of skipped)."""
@@ -10,17 +10,16 @@ from __future__ import annotations
 
 import torch
 
-from tests.abi_emulator import _flat
-from tests.abi_emulator_guidance import F32
+from tests.abi_emulator_guidance import F32, guided
 from tests.abi_emulator_multistep import MultistepEmulator
-from tests.abi_emulator_multistep import emulate as multistep_emulate
+from tests.step_forms import FORMS
 
 
 def emulate(x, eu, et, last, hist, coef, gs, gr, order, fault=None):
     """x, eu, et (or None), last fp32 [batch, n]; hist fp32 [order, batch, n]; coef fp32 (12,) -> (out, last', hist') fp32"""
     p, q, Ac, Bc, C2, C3, Ct, Ap, Bp, D1, D2, corr = coef.to(F32)
     zero = torch.zeros_like(x)
-    e = multistep_emulate(zero, eu, et, zero, torch.tensor([0.0, 1.0, 0.0, 0.0, 0.0]), gs, gr)[1]   # 0 * 0 + 1 * e = e, exactly
+    e = guided(eu, et, gs, gr)
     every = fault == "mul_nan"
     h = [hist[j] if j < order else None for j in range(3)]
 
@@ -52,20 +51,12 @@ def emulate(x, eu, et, last, hist, coef, gs, gr, order, fault=None):
 
 class UniPCEmulator(MultistepEmulator):
     def mi355x_sd_unipc_update(self, x, eu, et, last, hist, order, out, coef, gs, gr, batch, per_sample, stream):
-        self.calls.append("unipc_update")
-        assert x and eu and last and hist and out and coef and order in (1, 2, 3) and batch > 0
-        assert per_sample >= (2 if et and gr > 0 else 1) and coef % 16 == 0
-        n = batch * per_sample
-        spans = {"out": (out, 4 * n), "last": (last, 4 * n), "hist": (hist, 4 * n * order), "x": (x, 4 * n), "eu": (eu, 4 * n),
-                 "et": (et, 4 * n), "coef": (coef, 48)}
-        apart = lambda a, b: not a[0] or not b[0] or a[0] + a[1] <= b[0] or b[0] + b[1] <= a[0]  # noqa: E731
-        for w in ("out", "last", "hist"):
-            for r in spans:
-                assert r == w or (w == "out" and r == "x" and out == x) or apart(spans[w], spans[r]), (w, r)
-        v = [_flat(ptr, n, F32).reshape(batch, per_sample) if ptr else None for ptr in (x, eu, et, last)]
-        H = _flat(hist, n * order, F32).reshape(order, batch, per_sample)
-        o, xc, Hn = emulate(*v, H, _flat(coef, 12, F32), gs, gr if et else 0.0, order)
-        _flat(last, n, F32).copy_(xc.reshape(-1))   # (before out: at corr == 0 x_c IS x's memory, which out may be)
-        _flat(out, n, F32).copy_(o.reshape(-1))
+        assert order in (1, 2, 3) and coef % 16 == 0
+        v = self.step_args(FORMS["unipc"], dict(x=x, eu=eu, et=et, last=last, hist=hist, out=out, coef=coef), batch, per_sample,
+                           et and gr > 0, order)
+        H = v["hist"].reshape(order, batch, per_sample)
+        o, xc, Hn = emulate(v["x"], v["eu"], v["et"], v["last"], H, v["coef"], gs, gr if et else 0.0, order)
+        v["last"].copy_(xc)   # (before out: at corr == 0 x_c IS x's memory, which out may be)
+        v["out"].copy_(o)
         H.copy_(Hn)
         return 0

@@ -29,9 +29,10 @@ E_0 = u |x_0| if the start was scaled by init_noise_sigma != 1 (one fp32 product
 import torch
 
 from paddlemix_amd.schedulers import EulerAncestralDiscreteScheduler
-from tests.guidance_bounds import RESIDENT, Recording, Replay  # noqa: F401  (Recording / Replay: re-exported)
+from tests.guidance_bounds import RESIDENT
 from tests.multistep_bounds import guided
-from tests.rowmap_bounds import U32, check  # noqa: F401
+from tests.rowmap_bounds import U32, check
+from tests.step_pieces import base_inputs
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 
@@ -75,18 +76,11 @@ CASES = {   # name: batch, per_sample and what differs from gs = 7.5, gr = 0, ro
 def inputs(name):
     """dict(x, eu, et (None: no guidance), z, coef, gs, gr) of a case: CPU fp32 [batch, n], seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     z = torch.randn(shape, generator=g)
     if s.get("nan_noise"):
         z = torch.full(shape, float("nan"))
-    return dict(x=x, eu=eu, et=et if s.get("cfg", True) else None, z=z, coef=torch.tensor(ROW[s.get("row", "mid")], dtype=torch.float32),
+    return dict(x=x, eu=eu, et=et, z=z, coef=torch.tensor(ROW[s.get("row", "mid")], dtype=torch.float32),
                 gs=s.get("gs", 7.5), gr=s.get("gr", 0.0))
 
 
@@ -130,20 +124,3 @@ def accumulated(xs, zs, outs, coef64, gs, gr, cfg=True, sigma0=1.0):
             + 2 * U32 * r["out"].abs() + r["e_out"]
         res.append(E_x.reshape(x.shape))
     return res
-
-
-def counting(sch, widen=False):
-    """``sch`` with ``step`` counted in ``sch.step_calls``. widen: for the generic loop run in FLOAT64. torch.randn draws other numbers
-    in float64 than in float32 from the same seed, so a float64 model output would get noise the fused loop never saw; the wrapped step
-    draws what ``step`` draws for the fused loop's dtype -- float32, the same call on the same generator -- and hands it over widened,
-    through the ``noise=`` extension. Everything else of the generic loop is the pipeline's own."""
-    sch.step_calls = 0
-    step = sch.step
-
-    def counted(model_output, timestep, sample, generator=None, return_dict=True, *, noise=None):
-        sch.step_calls += 1
-        if widen and noise is None:
-            noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32).double()
-        return step(model_output, timestep, sample, generator=generator, return_dict=return_dict, noise=noise)
-    sch.step = counted
-    return sch

@@ -9,7 +9,6 @@ Prints one JSON line.
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -18,28 +17,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import ancestral_bounds as AB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.norm_child import CANARY32, _counts  # noqa: E402
-
-PAD = 64   # elements (256 bytes) of canary / NaN in front of and behind every view
-
-
-def _in(vals, off=0):
-    """the values inside a NaN buffer, `off` elements past a 16-byte boundary"""
-    n = vals.numel()
-    buf = torch.full((n + 2 * PAD,), float("nan"), device="cuda")
-    buf[PAD + off:PAD + off + n] = vals.reshape(-1).cuda()
-    return buf[PAD + off:PAD + off + n]
-
-
-def _out(n, off=0):
-    """(view of n floats inside a canary buffer, its bits, the mask of the view)"""
-    bits = torch.full((n + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
-    inside = torch.zeros(n + 2 * PAD, dtype=torch.bool, device="cuda")
-    inside[PAD + off:PAD + off + n] = True
-    return bits.view(torch.float32)[PAD + off:PAD + off + n], bits, inside
-
+from tests.step_child import _in, _out, capture, launched, main, refusals, replay_rows, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay, counting  # noqa: E402
 
 def _call(lib, x, eu, et, z, out, coef, gs, gr, batch, n, st):
     return lib.mi355x_sd_ancestral_update(x.data_ptr(), eu.data_ptr(), ops._p(et), ops._p(z), out.data_ptr(), coef.data_ptr(), gs, gr,
@@ -65,13 +45,8 @@ def run_case(name):
             xin = out
         else:
             xin = _in(v["x"], int(mis == "x"))
-        res["rc"] = _call(lib, xin, eu, et, z, out, cin, v["gs"], v["gr"], batch, n, st)
-        if res["rc"] == 3:   # MI355X_SD_ERR_HIP: nothing more is launched by this child
-            raise RuntimeError(f"{name}: MI355X_SD_ERR_HIP at launch")
-        torch.cuda.synchronize()
-        uw, ow = _counts(bits, inside, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow
+        res["rc"] = launched(name, _call(lib, xin, eu, et, z, out, cin, v["gs"], v["gr"], batch, n, st))
+        tally(res, bits, inside)
         got.append(out.clone())
     dev = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in v.items()}
     res["ratio"] = AB.ratio(dev, got[0])
@@ -103,51 +78,28 @@ def run_graph():
         direct.append(x.clone())
     res = {"rc_direct": rc, "finite": bool(torch.isfinite(direct[-1]).all().item()), "last_c": float(table[2, 2].item())}
     x, cur, z = v["x"].clone(), torch.zeros(3, device="cuda"), torch.zeros(batch, n, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        res["rc"] = _call(lib, x, v["eu"], v["et"], z, x, cur, gs, gr, batch, n, torch.cuda.current_stream().cuda_stream)
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    g = capture(res, lambda st: _call(lib, x, v["eu"], v["et"], z, x, cur, gs, gr, batch, n, st))
     x.copy_(v["x"])   # (the capture launched nothing, but the loop starts from the inputs whatever it did)
-    off = 0
-    for i in range(3):
-        cur.copy_(table[i])
-        z.copy_(planes[i])
-        g.replay()
-        torch.cuda.synchronize()
-        off += RB.exact_off(x, direct[i])
-    res["replay_off"] = off
+    res["replay_off"] = replay_rows(g, cur, table, (x,), [(d,) for d in direct], before_row=lambda i: z.copy_(planes[i]))
     return res
+
+
+def _deviations(but, n, x, eu, et, z, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out overlaps noise": but(out=z + 4 * (n - 1)),
+            "out is noise": but(out=z),
+            "out overlaps noise, no rescale": but(out=z - 4, gr=0.0),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null out": but(out=None), "null coef": but(coef=None)}
 
 
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((12 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, z, out, coef = (p + 4 * n * k for k in (0, 1, 2, 3, 5, 7))
-    ok = (x, eu, et, z, out, coef, 7.5, 0.7, 1, n)
-
-    def but(**kw):
-        names = ("x", "eu", "et", "z", "out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out overlaps noise": but(out=z + 4 * (n - 1)),
-             "out is noise": but(out=z),
-             "out overlaps noise, no rescale": but(out=z - 4, gr=0.0),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null out": but(out=None), "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_ancestral_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["ancestral"], 12, (0, 1, 2, 3, 5, 7), _deviations)
 
 
 def run_pipeline():
@@ -163,8 +115,8 @@ def run_pipeline():
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 8, 8)))
     gen = lambda: torch.Generator(device="cuda").manual_seed(seed)  # noqa: E731
-    sch = AB.counting(EulerAncestralDiscreteScheduler(**AB.SCHED))
-    unet = AB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    sch = counting(EulerAncestralDiscreteScheduler(**AB.SCHED))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs, g_fused = [], gen()
     kw = dict(num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr)
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, latents=lat0.clone(), generator=g_fused,
@@ -189,8 +141,8 @@ def run_pipeline():
         o = ops.ancestral_update(xs[i], unet.outs[i][:2].contiguous(), unet.outs[i][2:].contiguous(), zs[i],
                                  torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, gr)
         replay_off += RB.exact_off(o, xs[i + 1])
-    sch64, g64 = AB.counting(EulerAncestralDiscreteScheduler(**AB.SCHED), widen=True), gen()
-    generic = StableDiffusionDenoiser(AB.Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), generator=g64,
+    sch64, g64 = counting(EulerAncestralDiscreteScheduler(**AB.SCHED), widen=True), gen()
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), generator=g64,
                                                                                fused_update=False, **kw)
     same_state = same_state and bool(torch.equal(torch.randn(5, generator=g64, device="cuda"), torch.randn(5, generator=after(), device="cuda")))
     E = AB.accumulated(xs[:-1], zs, unet.outs, coef64, gs, gr, sigma0=sigma0)
@@ -200,23 +152,7 @@ def run_pipeline():
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [("pipeline", run_pipeline)]
-    if sys.argv[1:] != ["pipeline"]:
-        todo = [(k, (lambda k=k: run_case(k))) for k in AB.CASES] + [("graph", run_graph), ("refusals", run_refusals)] + todo
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("ANCESTRAL_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("ANCESTRAL_JSON", [(k, (lambda k=k: run_case(k))) for k in AB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])

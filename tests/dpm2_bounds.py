@@ -38,21 +38,19 @@ formulas (x0, (x - x0) / sigma, the sums) are 2^-29 of these and are not counted
 import torch
 
 from paddlemix_amd.schedulers import KDPM2AncestralDiscreteScheduler, KDPM2DiscreteScheduler
-from tests.ancestral_bounds import counting as counting_noisy
-from tests.guidance_bounds import RESIDENT, Recording, Replay  # noqa: F401  (Recording / Replay: re-exported)
-from tests.heun_bounds import counting as counting_plain
+from tests.guidance_bounds import RESIDENT
 from tests.multistep_bounds import guided
-from tests.rowmap_bounds import U32, check  # noqa: F401
+from tests.rowmap_bounds import U32, check
+from tests.step_pieces import base_inputs, counting
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 CLASSES = {"dpm2": KDPM2DiscreteScheduler, "dpm2a": KDPM2AncestralDiscreteScheduler}
 
 
 def scheduler(which, widen=False, **kw):
-    """a counted scheduler of CLASSES[which] on the SD betas; widen: see tests/ancestral_bounds.py counting (the ancestral class's
+    """a counted scheduler of CLASSES[which] on the SD betas; widen: see tests/step_pieces.py counting (the ancestral class's
     float64 generic loop is handed its generator's float32 draws)"""
-    sch = CLASSES[which](**dict(SCHED, **kw))
-    return counting_noisy(sch, widen) if which == "dpm2a" else counting_plain(sch)
+    return counting(CLASSES[which](**dict(SCHED, **kw)), widen and which == "dpm2a")
 
 
 def schedule_rows(which, steps=20, **kw):
@@ -110,18 +108,11 @@ CASES = {   # name: batch, per_sample and what differs from gs = 7.5, gr = 0, CF
 def inputs(name):
     """dict(x, eu, et (None: no guidance), z, S, coef, gs, gr) of a case: CPU fp32 [batch, n], seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     v = dict(x=x, S=3.0 * torch.randn(shape, generator=g), z=torch.randn(shape, generator=g))   # S is NOT near x: a stage 2 from x shows
     for k in s.get("nan", ()):
         v[k] = torch.full(shape, float("nan"))
-    return dict(v, eu=eu, et=et if s.get("cfg", True) else None, coef=torch.tensor(ROW[s["row"]], dtype=torch.float32),
+    return dict(v, eu=eu, et=et, coef=torch.tensor(ROW[s["row"]], dtype=torch.float32),
                 gs=s.get("gs", 7.5), gr=s.get("gr", 0.0))
 
 

@@ -9,7 +9,6 @@ runs alone (the IEEE-half build).
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -18,10 +17,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import dpm2_bounds as DB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.ancestral_child import _in, _out  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.norm_child import CANARY32, _counts  # noqa: E402
+from tests.step_child import _in, _out, capture, launched, main, refusals, replay_rows, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay  # noqa: E402
 
 
 def _call(lib, x, eu, et, z, S, out, coef, gs, gr, batch, n, st):
@@ -53,19 +51,12 @@ def run_case(name):
             xin = out
         else:
             xin = _in(v["x"], int(mis == "x"))
-        res["rc"] = _call(lib, xin, eu, et, z, S, out, cin, v["gs"], v["gr"], batch, n, st)
-        if res["rc"] == 3:   # MI355X_SD_ERR_HIP: nothing more is launched by this child
-            raise RuntimeError(f"{name}: MI355X_SD_ERR_HIP at launch")
-        torch.cuda.synchronize()
-        uw, ow = _counts(bits, inside, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow
+        res["rc"] = launched(name, _call(lib, xin, eu, et, z, S, out, cin, v["gs"], v["gr"], batch, n, st))
+        tally(res, bits, inside)
         if second:   # nothing of the buffer changes, inside the view or outside
             res["overwritten"] += int((s_bits != before).sum().item())
         else:
-            uw, ow = _counts(s_bits, s_inside, CANARY32)
-            res["unwritten"] += uw
-            res["overwritten"] += ow
+            tally(res, s_bits, s_inside)
         got.append((out.clone(), S.clone()))
     dev = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in v.items()}
     r = DB.ratios(dev, *got[0])
@@ -102,57 +93,34 @@ def run_graph():
     res = {"rc_direct": rc, "finite": bool(all(torch.isfinite(t).all().item() for d in direct for t in d)),
            "stages": [float(table[i, 4].item()) for i in range(3)], "noisy": [bool(table[i, 3].item() != 0.0) for i in range(3)]}
     x, S, z, cur = v["x"].clone(), nan(), nan(), torch.zeros(5, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        res["rc"] = _call(lib, x, v["eu"], v["et"], z, S, x, cur, gs, gr, batch, n, torch.cuda.current_stream().cuda_stream)
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    g = capture(res, lambda st: _call(lib, x, v["eu"], v["et"], z, S, x, cur, gs, gr, batch, n, st))
     x.copy_(v["x"])   # (the capture launched nothing, but the loop starts from the inputs whatever it did)
     S.copy_(nan())
-    off = 0
-    for i in range(3):
-        cur.copy_(table[i])
-        z.copy_(zs[i])
-        g.replay()
-        torch.cuda.synchronize()
-        off += sum(RB.exact_off(a, b) for a, b in zip((x, S), direct[i]))
-    res["replay_off"] = off
+    res["replay_off"] = replay_rows(g, cur, table, (x, S), direct, before_row=lambda i: z.copy_(zs[i]))
     return res
+
+
+def _deviations(but, n, x, eu, et, z, S, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "out is noise": but(out=z), "out overlaps noise": but(out=z + 4 * (n - 1)),
+            "sample is out": but(S=out), "sample overlaps out": but(S=out + 4 * (n - 1)),
+            "sample overlaps out, no rescale": but(S=out - 4, gr=0.0),
+            "sample is x": but(S=x), "sample overlaps x": but(S=x + 4 * (n - 1)),
+            "sample overlaps eps_uncond": but(S=eu + 4), "sample overlaps eps_text": but(S=et - 4),
+            "sample is noise": but(S=z), "sample overlaps noise": but(S=z - 4 * (n - 1)),
+            "sample overlaps coef": but(S=coef - 4 * (n - 1)), "sample overlaps coef's end": but(S=coef + 16),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null sample": but(S=None), "null out": but(out=None),
+            "null coef": but(coef=None)}
 
 
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((16 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, z, S, out, coef = (p + 4 * n * k for k in (0, 1, 2, 4, 6, 8, 10))
-    ok = (x, eu, et, z, S, out, coef, 7.5, 0.7, 1, n)
-
-    def but(**kw):
-        names = ("x", "eu", "et", "z", "S", "out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "out is noise": but(out=z), "out overlaps noise": but(out=z + 4 * (n - 1)),
-             "sample is out": but(S=out), "sample overlaps out": but(S=out + 4 * (n - 1)),
-             "sample overlaps out, no rescale": but(S=out - 4, gr=0.0),
-             "sample is x": but(S=x), "sample overlaps x": but(S=x + 4 * (n - 1)),
-             "sample overlaps eps_uncond": but(S=eu + 4), "sample overlaps eps_text": but(S=et - 4),
-             "sample is noise": but(S=z), "sample overlaps noise": but(S=z - 4 * (n - 1)),
-             "sample overlaps coef": but(S=coef - 4 * (n - 1)), "sample overlaps coef's end": but(S=coef + 16),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null sample": but(S=None), "null out": but(out=None),
-             "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_dpm2_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["dpm2"], 16, (0, 1, 2, 4, 6, 8, 10), _deviations)
 
 
 def run_pipeline(which):
@@ -170,7 +138,7 @@ def run_pipeline(which):
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 16, 16)))
     gen = lambda: torch.Generator(device="cuda").manual_seed(seed)  # noqa: E731
     sch = DB.scheduler(which)
-    unet = DB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs, g_fused = [], gen()
     kw = dict(num_inference_steps=steps, guidance_scale=gs)
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, latents=lat0.clone(), generator=g_fused,
@@ -192,7 +160,7 @@ def run_pipeline(which):
                             torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, 0.0)
         replay_off += RB.exact_off(o, xs[i + 1])
     sch64, g64 = DB.scheduler(which, widen=True), gen()
-    generic = StableDiffusionDenoiser(DB.Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), generator=g64,
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), generator=g64,
                                                                                fused_update=False, **kw)
     same_state = same_state and bool(torch.equal(g64.get_state(), g2.get_state()))
     E = DB.accumulated(xs[:-1], Ss, zs, unet.outs, coef64, gs, 0.0, sigma0=sigma0)
@@ -202,23 +170,7 @@ def run_pipeline(which):
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [(f"pipeline {w}", (lambda w=w: run_pipeline(w))) for w in ("dpm2", "dpm2a")]
-    if sys.argv[1:] != ["pipeline"]:
-        todo = [(k, (lambda k=k: run_case(k))) for k in DB.CASES] + [("graph", run_graph), ("refusals", run_refusals)] + todo
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("DPM2_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("DPM2_JSON", [(k, (lambda k=k: run_case(k))) for k in DB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [(f"pipeline {w}", (lambda w=w: run_pipeline(w))) for w in ("dpm2", "dpm2a")])

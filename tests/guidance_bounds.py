@@ -48,6 +48,7 @@ import torch
 
 from tests.norm_bounds import RCP, fp32, gamma
 from tests.rowmap_bounds import U32
+from tests.step_pieces import base_inputs
 
 THREADS, RES = 1024, 32          # csrc/misc.hip CRA_THREADS, CRA_RES: block size, register-resident values per lane and array
 RESIDENT = THREADS * RES         # the largest sample that is read once; above it the kernel loops and re-reads
@@ -71,14 +72,7 @@ CASES = {   # name: batch, per_sample and what differs from gs = 7.5, gr = 0.7, 
 def inputs(name):
     """(x, eu, et, coef, gs, gr) of a case: CPU fp32 [batch, n], seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     return x, eu, et, torch.tensor(COEF), s.get("gs", 7.5), s.get("gr", 0.7)
 
 
@@ -136,26 +130,3 @@ def accumulated(xs, outs, coef64, gs, gr, sigma0=1.0):
         E = abs(a) * E + 2 * U32 * ref.abs() + e + abs(a32 - a) * x.flatten(1).double().abs() + abs(b32 - b) * ck.abs()
         res.append(E.reshape(x.shape))
     return res
-
-
-class Recording:
-    """a UNet wrapper that keeps every model output of a run (what Replay then returns)"""
-
-    def __init__(self, unet):
-        self.unet, self.config, self._lib, self._emulated, self.outs = unet, unet.config, unet._lib, unet._emulated, []
-
-    def __call__(self, *args, **kwargs):
-        out = self.unet(*args, **kwargs)
-        self.outs.append(out[0].detach().clone())
-        return out
-
-
-class Replay:
-    """stands in the `unet` slot of the generic loop: returns the recorded outputs in order, as `dtype`, whatever the input"""
-
-    def __init__(self, config, outs, dtype=torch.float64):
-        self.config, self.outs, self.dtype, self.i = config, outs, dtype, 0
-
-    def __call__(self, *args, **kwargs):
-        self.i += 1
-        return (self.outs[self.i - 1].to(self.dtype),)

@@ -5,7 +5,6 @@ element, the second must equal it bit for bit. Then a torch.cuda.graph replayed 
 
   python tests/guidance_child.py
 """
-import ctypes
 import os
 import sys
 
@@ -16,33 +15,30 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import guidance_bounds as GB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.norm_child import CANARY32, _canary, _counts  # noqa: E402
-from tests.rowmap_child import _flat_in  # noqa: E402
+from tests.step_child import _in, _out, capture, main, refusals, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay  # noqa: E402
 
 
 def run_case(name):
     lib, st = _lib.load(), ops._stream()
     x, eu, et, coef, gs, gr = GB.inputs(name)
     batch, n = x.shape
-    both = _flat_in(torch.cat([eu.reshape(-1), et.reshape(-1)]).cuda())   # the two halves of one tensor, as pipeline.py calls it
-    cin = _flat_in(coef.cuda())
+    both = _in(torch.cat([eu.reshape(-1), et.reshape(-1)]))   # the two halves of one tensor, as pipeline.py calls it
+    cin = _in(coef)
     res = {"unwritten": 0, "overwritten": 0}
     outs = []
     for _ in range(2):
-        view, bits, inside = _canary((1, batch * n), batch * n, 32)
-        out = view[0]
+        out, bits, inside = _out(batch * n)
         if GB.CASES[name].get("alias"):   # out = x, as a loop updates its latents in place
             out.copy_(x.reshape(-1))
             xin = out
         else:
-            xin = _flat_in(x.reshape(-1).cuda())
+            xin = _in(x)
         res["rc"] = lib.mi355x_sd_cfg_rescale_axpby(xin.data_ptr(), both.data_ptr(), both.data_ptr() + 4 * batch * n, out.data_ptr(),
                                                     cin.data_ptr(), gs, gr, batch, n, st)
         torch.cuda.synchronize()
-        uw, ow = _counts(bits, inside, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow
+        tally(res, bits, inside)
         outs.append(out.clone())
     xd, ud, td = x.cuda(), eu.cuda(), et.cuda()
     ref, e, _ = GB.cfg_rescale_axpby(xd, ud, td, coef, gs, gr)
@@ -55,21 +51,6 @@ def run_case(name):
     return res
 
 
-def _graph_shape(g):
-    """(nodes, root nodes, edges) of a captured graph, asked of the HIP runtime the process already has loaded"""
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    graph = ctypes.c_void_p(g.raw_cuda_graph())
-    got = []
-    for fn, args in ((hip.hipGraphGetNodes, (None,)), (hip.hipGraphGetRootNodes, (None,)), (hip.hipGraphGetEdges, (None, None))):
-        k = ctypes.c_size_t(0)
-        fn.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * len(args) + [ctypes.POINTER(ctypes.c_size_t)]
-        fn.restype = ctypes.c_int
-        assert fn(graph, *args, ctypes.byref(k)) == 0, fn
-        got.append(k.value)
-    return got
-
-
 def run_graph():
     """one capture, two replays with different (a, b) in the device buffer the launch reads"""
     lib = _lib.load()
@@ -77,15 +58,9 @@ def run_graph():
     batch, n = x.shape
     rows = torch.tensor([GB.COEF, (1.0127, -0.0423)])
     cur, out = torch.zeros(2, device="cuda"), torch.zeros_like(x)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        rc = lib.mi355x_sd_cfg_rescale_axpby(x.data_ptr(), eu.data_ptr(), et.data_ptr(), out.data_ptr(), cur.data_ptr(), gs, gr, batch, n,
-                                             torch.cuda.current_stream().cuda_stream)
-    res = {"rc": rc, "unwritten": 0, "overwritten": 0}
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    res = {"unwritten": 0, "overwritten": 0}
+    g = capture(res, lambda st: lib.mi355x_sd_cfg_rescale_axpby(x.data_ptr(), eu.data_ptr(), et.data_ptr(), out.data_ptr(), cur.data_ptr(),
+                                                                gs, gr, batch, n, st))
     worst = 0.0
     for row in rows:
         cur.copy_(row.cuda())
@@ -97,22 +72,17 @@ def run_graph():
     return res
 
 
+def _deviations(but, n, x, eu, et, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "per_sample 1": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null": but(eu=None)}
+
+
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((8 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, out, coef = p, p + 4 * n, p + 8 * n, p + 16 * n, p + 24 * n
-    calls = {"out overlaps eps_text": (x, eu, et, et + 4 * (n - 1), coef, 7.5, 0.7, 1, n),
-             "out overlaps eps_uncond": (x, eu, et, eu - 4, coef, 7.5, 0.7, 1, n),
-             "out overlaps x partly": (x, eu, et, x + 4, coef, 7.5, 0.7, 1, n // 2),
-             "per_sample 1": (x, eu, et, out, coef, 7.5, 0.7, n, 1),
-             "batch 0": (x, eu, et, out, coef, 7.5, 0.7, 0, n),
-             "null": (x, None, et, out, coef, 7.5, 0.7, 1, n)}
-    res = {k: lib.mi355x_sd_cfg_rescale_axpby(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["guidance"], 8, (0, 1, 2, 4, 6), _deviations)
 
 
 def run_pipeline():
@@ -126,7 +96,7 @@ def run_pipeline():
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 8, 8)))
     sch = EulerDiscreteScheduler(prediction_type="v_prediction", beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
-    unet = GB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs = []
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr,
                                                latents=lat0.clone(),
@@ -137,26 +107,14 @@ def run_pipeline():
     xs = [lat0 * sigma0] + xs
     coef64 = [sch.step_coefficients(t) for t in sch.timesteps]
     sch._step_index = None
-    generic = StableDiffusionDenoiser(GB.Replay(unet.config, unet.outs), sch)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
         pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr, latents=lat0.double(), fused_update=False)
     E = GB.accumulated(xs[:-1], unet.outs, coef64, gs, gr, sigma0)
     return {"steps": len(unet.outs), "stepped": stepped, "finite": bool(torch.isfinite(fused).all().item()),
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    ops.init(0)
-    res = {}
-    for name, fn in [(k, (lambda k=k: run_case(k))) for k in GB.CASES] + [("graph", run_graph), ("refusals", run_refusals),
-                                                                          ("pipeline", run_pipeline)]:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    emit("GUIDANCE_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("GUIDANCE_JSON", [(k, (lambda k=k: run_case(k))) for k in GB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])

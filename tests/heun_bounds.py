@@ -38,9 +38,10 @@ formulas (x0, (x - x0) / sigma, the average) are 2^-29 of these and are not coun
 import torch
 
 from paddlemix_amd.schedulers import HeunDiscreteScheduler
-from tests.guidance_bounds import RESIDENT, Recording, Replay  # noqa: F401  (Recording / Replay: re-exported)
+from tests.guidance_bounds import RESIDENT
 from tests.multistep_bounds import guided
-from tests.rowmap_bounds import U32, check  # noqa: F401
+from tests.rowmap_bounds import U32, check
+from tests.step_pieces import base_inputs
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 
@@ -92,19 +93,12 @@ CASES = {   # name: batch, per_sample and what differs from gs = 7.5, gr = 0, CF
 def inputs(name):
     """dict(x, eu, et (None: no guidance), S, D, coef, gs, gr) of a case: CPU fp32 [batch, n], seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     S, D = 3.0 * torch.randn(shape, generator=g), torch.randn(shape, generator=g)   # S is NOT near x: a stage 2 from x shows
     nan = s.get("nan", ())
     S = torch.full(shape, float("nan")) if "S" in nan else S
     D = torch.full(shape, float("nan")) if "D" in nan else D
-    return dict(x=x, eu=eu, et=et if s.get("cfg", True) else None, S=S, D=D, coef=torch.tensor(ROW[s["row"]], dtype=torch.float32),
+    return dict(x=x, eu=eu, et=et, S=S, D=D, coef=torch.tensor(ROW[s["row"]], dtype=torch.float32),
                 gs=s.get("gs", 7.5), gr=s.get("gr", 0.0))
 
 
@@ -179,15 +173,3 @@ def accumulated(xs, states, outs, coef64, gs, gr, cfg=True, sigma0=1.0):
             E_x = E_S + abs(h) * (abs(g) * E_D + dd) + dh * r["m"].abs() + store
         res.append(E_x.reshape(x.shape))
     return res
-
-
-def counting(sch):
-    """``sch`` with ``step`` counted in ``sch.step_calls``"""
-    sch.step_calls = 0
-    step = sch.step
-
-    def counted(*a, **k):
-        sch.step_calls += 1
-        return step(*a, **k)
-    sch.step = counted
-    return sch

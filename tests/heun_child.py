@@ -8,7 +8,6 @@ launches; the refusals; and an 8-step (15-launch) pipeline run. Prints one JSON 
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -17,10 +16,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import heun_bounds as HB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.ancestral_child import _in, _out  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.norm_child import CANARY32, _counts  # noqa: E402
+from tests.step_child import _in, _out, capture, launched, main, refusals, replay_rows, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay, counting  # noqa: E402
 
 
 def _call(lib, x, eu, et, S, D, out, coef, gs, gr, batch, n, st):
@@ -53,20 +51,13 @@ def run_case(name):
         else:
             xin = _in(v["x"], int(mis == "x"))
         S, D = planes[0][0], planes[1][0]
-        res["rc"] = _call(lib, xin, eu, et, S, D, out, cin, v["gs"], v["gr"], batch, n, st)
-        if res["rc"] == 3:   # MI355X_SD_ERR_HIP: nothing more is launched by this child
-            raise RuntimeError(f"{name}: MI355X_SD_ERR_HIP at launch")
-        torch.cuda.synchronize()
-        uw, ow = _counts(bits, inside, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow
+        res["rc"] = launched(name, _call(lib, xin, eu, et, S, D, out, cin, v["gs"], v["gr"], batch, n, st))
+        tally(res, bits, inside)
         for (_, b, ins), b0 in zip(planes, before):
             if second:   # nothing of the buffer changes, inside the view or outside
                 res["overwritten"] += int((b != b0).sum().item())
             else:
-                uw, ow = _counts(b, ins, CANARY32)
-                res["unwritten"] += uw
-                res["overwritten"] += ow
+                tally(res, b, ins)
         got.append((out.clone(), S.clone(), D.clone()))
     dev = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in v.items()}
     r = HB.ratios(dev, *got[0])
@@ -100,57 +91,35 @@ def run_graph():
     res = {"rc_direct": rc, "finite": bool(all(torch.isfinite(t).all().item() for d in direct for t in d)),
            "stages": [float(table[i, 4].item()) for i in range(3)]}
     x, S, D, cur = v["x"].clone(), nan(), nan(), torch.zeros(5, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        res["rc"] = _call(lib, x, v["eu"], v["et"], S, D, x, cur, gs, gr, batch, n, torch.cuda.current_stream().cuda_stream)
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    g = capture(res, lambda st: _call(lib, x, v["eu"], v["et"], S, D, x, cur, gs, gr, batch, n, st))
     x.copy_(v["x"])   # (the capture launched nothing, but the loop starts from the inputs whatever it did)
     S.copy_(nan())
     D.copy_(nan())
-    off = 0
-    for i in range(3):
-        cur.copy_(table[i])
-        g.replay()
-        torch.cuda.synchronize()
-        off += sum(RB.exact_off(a, b) for a, b in zip((x, S, D), direct[i]))
-    res["replay_off"] = off
+    res["replay_off"] = replay_rows(g, cur, table, (x, S, D), direct)
     return res
+
+
+def _deviations(but, n, x, eu, et, S, D, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "sample is out": but(S=out), "sample overlaps out": but(S=out + 4 * (n - 1)),
+            "deriv is out": but(D=out), "deriv overlaps out, no rescale": but(D=out - 4, gr=0.0),
+            "sample is x": but(S=x), "sample overlaps x": but(S=x + 4 * (n - 1)),
+            "deriv is x": but(D=x), "deriv overlaps eps_uncond": but(D=eu + 4),
+            "sample overlaps eps_text": but(S=et - 4), "sample overlaps coef": but(S=coef - 4 * (n - 1)),
+            "deriv overlaps coef": but(D=coef + 16),
+            "sample is deriv": but(S=D), "sample overlaps deriv": but(S=D - 4 * (n - 1)),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null sample": but(S=None), "null deriv": but(D=None),
+            "null out": but(out=None), "null coef": but(coef=None)}
 
 
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((16 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, S, D, out, coef = (p + 4 * n * k for k in (0, 1, 2, 4, 6, 8, 10))
-    ok = (x, eu, et, S, D, out, coef, 7.5, 0.7, 1, n)
-
-    def but(**kw):
-        names = ("x", "eu", "et", "S", "D", "out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "sample is out": but(S=out), "sample overlaps out": but(S=out + 4 * (n - 1)),
-             "deriv is out": but(D=out), "deriv overlaps out, no rescale": but(D=out - 4, gr=0.0),
-             "sample is x": but(S=x), "sample overlaps x": but(S=x + 4 * (n - 1)),
-             "deriv is x": but(D=x), "deriv overlaps eps_uncond": but(D=eu + 4),
-             "sample overlaps eps_text": but(S=et - 4), "sample overlaps coef": but(S=coef - 4 * (n - 1)),
-             "deriv overlaps coef": but(D=coef + 16),
-             "sample is deriv": but(S=D), "sample overlaps deriv": but(S=D - 4 * (n - 1)),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null sample": but(S=None), "null deriv": but(D=None),
-             "null out": but(out=None), "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_heun_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["heun"], 16, (0, 1, 2, 4, 6, 8, 10), _deviations)
 
 
 def run_pipeline():
@@ -165,8 +134,8 @@ def run_pipeline():
     steps, gs = 8, 7.5
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 16, 16)))
-    sch = HB.counting(HeunDiscreteScheduler(**HB.SCHED))
-    unet = HB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    sch = counting(HeunDiscreteScheduler(**HB.SCHED))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs = []
     kw = dict(num_inference_steps=steps, guidance_scale=gs)
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, latents=lat0.clone(),
@@ -184,29 +153,15 @@ def run_pipeline():
         o = ops.heun_update(xs[i], unet.outs[i][:2].contiguous(), unet.outs[i][2:].contiguous(), S, D,
                             torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, 0.0)
         replay_off += RB.exact_off(o, xs[i + 1])
-    sch64 = HB.counting(HeunDiscreteScheduler(**HB.SCHED))
-    generic = StableDiffusionDenoiser(HB.Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), fused_update=False, **kw)
+    sch64 = counting(HeunDiscreteScheduler(**HB.SCHED))
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), fused_update=False, **kw)
     E = HB.accumulated(xs[:-1], states, unet.outs, coef64, gs, 0.0, sigma0=sigma0)
     return {"launches": len(unet.outs), "stepped": stepped, "generic_stepped": sch64.step_calls, "replay_off": replay_off,
             "finite": bool(torch.isfinite(fused).all().item()), "elem": _lib.ELEM_NAME, "generic_dtype": str(generic.dtype),
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [(k, (lambda k=k: run_case(k))) for k in HB.CASES] + [("graph", run_graph), ("refusals", run_refusals), ("pipeline", run_pipeline)]
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("HEUN_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("HEUN_JSON", [(k, (lambda k=k: run_case(k))) for k in HB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])

@@ -31,9 +31,10 @@ E_0 = u |x_0| if the start was scaled by init_noise_sigma != 1 (DPM-Solver: 1), 
 import torch
 
 from paddlemix_amd.schedulers import DPMSolverMultistepScheduler
-from tests.guidance_bounds import K_R, RESIDENT, Recording, Replay, _ss, chain   # noqa: F401  (Recording / Replay: re-exported)
-from tests.norm_bounds import fp32, gamma  # noqa: F401
-from tests.rowmap_bounds import U32, check  # noqa: F401
+from tests.guidance_bounds import K_R, RESIDENT, _ss, chain
+from tests.norm_bounds import fp32
+from tests.rowmap_bounds import U32
+from tests.step_pieces import base_inputs
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 
@@ -75,19 +76,12 @@ CASES = {   # name: batch, per_sample and what differs from gs = 7.5, gr = 0.7, 
 def inputs(name):
     """dict(x, eu, et (None: no guidance), m1, coef, gs, gr) of a case: CPU fp32 [batch, n], seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     m1 = 2.0 * torch.randn(shape, generator=g)
     if s.get("nan_history"):
         m1 = torch.full(shape, float("nan"))
     row = FIRST if s.get("row") == "first" else MID
-    return dict(x=x, eu=eu, et=et if s.get("cfg", True) else None, m1=m1, coef=torch.tensor(row, dtype=torch.float32),
+    return dict(x=x, eu=eu, et=et, m1=m1, coef=torch.tensor(row, dtype=torch.float32),
                 gs=s.get("gs", 7.5), gr=s.get("gr", 0.7))
 
 

@@ -8,7 +8,6 @@ rows (D != 0 and D = 0), the refusals, and a 6-step pipeline run. Prints one JSO
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -17,17 +16,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import multistep_bounds as MB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.norm_child import CANARY32, _canary, _counts  # noqa: E402
-from tests.rowmap_child import _flat_in  # noqa: E402
-
-
-def _offset_in(vals):
-    """the values one element into a NaN buffer: a pointer that is not 16-byte aligned"""
-    buf = torch.full((vals.numel() + 65,), float("nan"), device="cuda")
-    buf[1:1 + vals.numel()] = vals.reshape(-1)
-    return buf[1:1 + vals.numel()]
+from tests.step_child import _in, _out, capture, main, refusals, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay  # noqa: E402
 
 
 def _call(lib, x, eu, et, m1, out, m_out, coef, gs, gr, batch, n, st):
@@ -40,27 +31,22 @@ def run_case(name):
     v = MB.inputs(name)
     s = MB.CASES[name]
     batch, n = v["x"].shape
-    eu = _flat_in(v["eu"].reshape(-1).cuda())
-    et = None if v["et"] is None else _flat_in(v["et"].reshape(-1).cuda())
-    cin = _flat_in(v["coef"].cuda())
+    eu, cin = _in(v["eu"]), _in(v["coef"])
+    et = None if v["et"] is None else _in(v["et"])
     res = {"unwritten": 0, "overwritten": 0}
     got = []
     for _ in range(2):
-        (ov, obits, oin), (mv, mbits, min_) = _canary((1, batch * n), batch * n, 32), _canary((1, batch * n), batch * n, 32)
-        out, m_out = ov[0], mv[0]
+        (out, obits, oin), (m_out, mbits, min_) = _out(batch * n), _out(batch * n)
         if s.get("alias"):   # out = x and m_out = m_prev, as a loop with one latent and one history buffer
             out.copy_(v["x"].reshape(-1))
             m_out.copy_(v["m1"].reshape(-1))
             xin, m1 = out, m_out
         else:
-            xin = (_offset_in if s.get("misalign") else _flat_in)(v["x"].reshape(-1).cuda())
-            m1 = _flat_in(v["m1"].reshape(-1).cuda())
+            xin, m1 = _in(v["x"], int(bool(s.get("misalign")))), _in(v["m1"])   # (misalign: x one element past a 16-byte boundary)
         res["rc"] = _call(lib, xin, eu, et, m1, out, m_out, cin, v["gs"], v["gr"], batch, n, st)
         torch.cuda.synchronize()
-        for bits, inside in ((obits, oin), (mbits, min_)):
-            uw, ow = _counts(bits, inside, CANARY32)
-            res["unwritten"] += uw
-            res["overwritten"] += ow
+        tally(res, obits, oin)
+        tally(res, mbits, min_)
         got.append((out.clone(), m_out.clone()))
     dev = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in v.items()}
     r = MB.multistep_update(dev["x"], dev["eu"], dev["et"], dev["m1"], v["coef"], v["gs"], v["gr"])
@@ -80,15 +66,8 @@ def run_graph():
     v = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in MB.inputs("b3 n4093 odd rescale").items()}
     batch, n = v["x"].shape
     cur, out, m_out = torch.zeros(5, device="cuda"), torch.zeros_like(v["x"]), torch.zeros_like(v["x"])
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        rc = _call(lib, v["x"], v["eu"], v["et"], v["m1"], out, m_out, cur, v["gs"], v["gr"], batch, n,
-                   torch.cuda.current_stream().cuda_stream)
-    res = {"rc": rc}
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    res = {}
+    g = capture(res, lambda st: _call(lib, v["x"], v["eu"], v["et"], v["m1"], out, m_out, cur, v["gs"], v["gr"], batch, n, st))
     worst = 0.0
     for row in (MB.MID, MB.FIRST):
         row = torch.tensor(row, dtype=torch.float32)
@@ -101,36 +80,26 @@ def run_graph():
     return res
 
 
-def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((12 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, m1, out, m_out, coef = (p + 4 * n * k for k in (0, 1, 2, 3, 5, 7, 9))
-    ok = (x, eu, et, m1, out, m_out, coef, 7.5, 0.7, 1, n)
+def _deviations(but, n, x, eu, et, m1, out, m_out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out overlaps m_prev": but(out=m1),
+            "out overlaps m_out": but(out=m_out + 4 * (n - 1)),
+            "out is m_out": but(out=m_out),
+            "m_out overlaps x": but(m_out=x),
+            "m_out overlaps m_prev partly": but(m_out=m1 + 4, n=n // 2),
+            "m_out overlaps eps_text": but(m_out=et),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null m_prev": but(m1=None), "null out": but(out=None),
+            "null m_out": but(m_out=None), "null coef": but(coef=None)}
 
-    def but(**kw):
-        names = ("x", "eu", "et", "m1", "out", "m_out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out overlaps m_prev": but(out=m1),
-             "out overlaps m_out": but(out=m_out + 4 * (n - 1)),
-             "out is m_out": but(out=m_out),
-             "m_out overlaps x": but(m_out=x),
-             "m_out overlaps m_prev partly": but(m_out=m1 + 4, n=n // 2),
-             "m_out overlaps eps_text": but(m_out=et),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null m_prev": but(m1=None), "null out": but(out=None),
-             "null m_out": but(m_out=None), "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_multistep_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+
+def run_refusals():
+    return refusals(FORMS["multistep"], 12, (0, 1, 2, 3, 5, 7, 9), _deviations)
 
 
 def run_pipeline():
@@ -145,7 +114,7 @@ def run_pipeline():
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 8, 8)))
     sch = DPMSolverMultistepScheduler(**MB.SCHED)
-    unet = MB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs = []
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr,
                                                latents=lat0.clone(),
@@ -161,7 +130,7 @@ def run_pipeline():
                                     torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, gr)
         replay_off += RB.exact_off(o, xs[i + 1])
         hs.append(m)
-    generic = StableDiffusionDenoiser(MB.Replay(unet.config, unet.outs), sch)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
         pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr, latents=lat0.double(), fused_update=False)
     E = MB.accumulated(xs[:-1], hs[:-1], unet.outs, coef64, gs, gr)
     return {"steps": len(unet.outs), "stepped": stepped, "generic_stepped": sch.step_index, "replay_off": replay_off,
@@ -169,23 +138,7 @@ def run_pipeline():
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [("pipeline", run_pipeline)]
-    if sys.argv[1:] != ["pipeline"]:
-        todo = [(k, (lambda k=k: run_case(k))) for k in MB.CASES] + [("graph", run_graph), ("refusals", run_refusals)] + todo
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("MULTISTEP_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("MULTISTEP_JSON", [(k, (lambda k=k: run_case(k))) for k in MB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])

@@ -44,10 +44,10 @@ are 2^-29 of these and are not counted, as in the sibling modules.
 import torch
 
 from paddlemix_amd.schedulers import PNDMScheduler
-from tests.guidance_bounds import RESIDENT, Recording, Replay  # noqa: F401  (Recording / Replay: re-exported)
-from tests.heun_bounds import counting  # noqa: F401
+from tests.guidance_bounds import RESIDENT
 from tests.multistep_bounds import guided
-from tests.rowmap_bounds import U32, check  # noqa: F401
+from tests.rowmap_bounds import U32, check
+from tests.step_pieces import base_inputs
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", skip_prk_steps=True, steps_offset=1)
 WIDTH = 12   # fp32 values in a row
@@ -105,14 +105,7 @@ def flags(coef):
 def inputs(name):
     """dict(x, eu, et (None: no guidance), P, H [3, batch, n], coef, gs, gr) of a case: CPU fp32, seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    if s.get("kind") == "offset":   # a standard deviation 6400 times below the mean: what cancels in sum v^2 - n m^2
-        eu, et = 64.0 + 1e-2 * torch.randn(shape, generator=g), 64.0 + 1e-2 * torch.randn(shape, generator=g)
-    else:
-        eu = torch.randn(shape, generator=g)
-        et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     # P is NOT near x, and the planes are unrelated: an S from the wrong one, or two planes exchanged, shows
     P, H = 3.0 * torch.randn(shape, generator=g), torch.randn((3,) + shape, generator=g)
     coef = torch.tensor(ROW[s["row"]], dtype=torch.float32)
@@ -124,7 +117,7 @@ def inputs(name):
             P = torch.full(shape, float("nan"))
         else:
             H[(slot - int(k[1])) % 3] = float("nan")
-    return dict(x=x, eu=eu, et=et if s.get("cfg", True) else None, P=P, H=H, coef=coef, gs=s.get("gs", 7.5), gr=s.get("gr", 0.0))
+    return dict(x=x, eu=eu, et=et, P=P, H=H, coef=coef, gs=s.get("gs", 7.5), gr=s.get("gr", 0.0))
 
 
 def plms_update(x, eu, et, P, H, coef, gs, gr, depth=None):

@@ -7,7 +7,6 @@ coefficient buffer, against direct launches; the refusals; and an 8-step (9-laun
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -16,10 +15,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import plms_bounds as PB  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.ancestral_child import _in, _out  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.norm_child import CANARY32, _counts  # noqa: E402
+from tests.step_child import _in, _out, capture, launched, main, refusals, replay_rows, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay, counting  # noqa: E402
 
 
 def _call(lib, x, eu, et, P, H, out, coef, gs, gr, batch, n, st):
@@ -50,13 +48,8 @@ def run_case(name):
             xin = out
         else:
             xin = _in(v["x"], int(mis == "x"))
-        res["rc"] = _call(lib, xin, eu, et, P, H, out, cin, v["gs"], v["gr"], batch, n, st)
-        if res["rc"] == 3:   # MI355X_SD_ERR_HIP: nothing more is launched by this child
-            raise RuntimeError(f"{name}: MI355X_SD_ERR_HIP at launch")
-        torch.cuda.synchronize()
-        uw, ow = _counts(bits, inside, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow
+        res["rc"] = launched(name, _call(lib, xin, eu, et, P, H, out, cin, v["gs"], v["gr"], batch, n, st))
+        tally(res, bits, inside)
         # around the views of P and H nothing changes (inside them: ratios() below, element by element)
         for b, b0, view in ((pbits, before[0], P), (hbits, before[1], H)):
             outside = torch.ones_like(b, dtype=torch.bool)
@@ -100,57 +93,35 @@ def run_graph():
     res = {"rc_direct": rc, "finite": bool(all(torch.isfinite(t).all().item() for d in direct for t in d)),
            "slots": [float(table[i, 8].item()) for i in range(len(GRAPH_ROWS))]}
     x, P, H, cur = v["x"].clone(), nan(), v["H"].clone(), torch.zeros(PB.WIDTH, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        res["rc"] = _call(lib, x, v["eu"], v["et"], P, H, x, cur, gs, gr, batch, n, torch.cuda.current_stream().cuda_stream)
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    g = capture(res, lambda st: _call(lib, x, v["eu"], v["et"], P, H, x, cur, gs, gr, batch, n, st))
     x.copy_(v["x"])   # (the capture launched nothing, but the loop starts from the inputs whatever it did)
     P.copy_(nan())
     H.copy_(v["H"])
-    off = 0
-    for i in range(len(GRAPH_ROWS)):
-        cur.copy_(table[i])
-        g.replay()
-        torch.cuda.synchronize()
-        off += sum(RB.exact_off(a, b) for a, b in zip((x, P, H), direct[i]))
-    res["replay_off"] = off
+    res["replay_off"] = replay_rows(g, cur, table, (x, P, H), direct)
     return res
+
+
+def _deviations(but, n, x, eu, et, P, H, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "park is out": but(P=out), "park overlaps out": but(P=out + 4 * (n - 1)),
+            "park is x": but(P=x), "park overlaps x, no rescale": but(P=x + 4 * (n - 1), gr=0.0),
+            "park overlaps eps_text": but(P=et - 4), "park overlaps coef": but(P=coef - 4 * (n - 1)),
+            "hist is out": but(H=out), "third plane of hist overlaps out": but(H=out - 4 * (3 * n - 1)),
+            "hist is x": but(H=x), "second plane of hist is eps_text": but(H=et - 4 * n),
+            "third plane of hist overlaps coef": but(H=coef - 4 * (3 * n - 1)),
+            "hist is park": but(H=P), "third plane of hist is park": but(P=H + 4 * 2 * n),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0), "batch -1": but(batch=-1),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null park": but(P=None), "null hist": but(H=None),
+            "null out": but(out=None), "null coef": but(coef=None)}
 
 
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((16 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, P, H, out, coef = (p + 4 * n * k for k in (0, 1, 2, 4, 6, 10, 12))   # H: the planes 6, 7, 8
-    ok = (x, eu, et, P, H, out, coef, 7.5, 0.7, 1, n)
-
-    def but(**kw):
-        names = ("x", "eu", "et", "P", "H", "out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "park is out": but(P=out), "park overlaps out": but(P=out + 4 * (n - 1)),
-             "park is x": but(P=x), "park overlaps x, no rescale": but(P=x + 4 * (n - 1), gr=0.0),
-             "park overlaps eps_text": but(P=et - 4), "park overlaps coef": but(P=coef - 4 * (n - 1)),
-             "hist is out": but(H=out), "third plane of hist overlaps out": but(H=out - 4 * (3 * n - 1)),
-             "hist is x": but(H=x), "second plane of hist is eps_text": but(H=et - 4 * n),
-             "third plane of hist overlaps coef": but(H=coef - 4 * (3 * n - 1)),
-             "hist is park": but(H=P), "third plane of hist is park": but(P=H + 4 * 2 * n),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0), "batch -1": but(batch=-1),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null park": but(P=None), "null hist": but(H=None),
-             "null out": but(out=None), "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_plms_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["plms"], 16, (0, 1, 2, 4, 6, 10, 12), _deviations)   # H: the planes 6, 7, 8
 
 
 def run_pipeline():
@@ -165,8 +136,8 @@ def run_pipeline():
     steps, gs = 8, 7.5
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 16, 16)))
-    sch = PB.counting(PNDMScheduler(**PB.SCHED))
-    unet = PB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    sch = counting(PNDMScheduler(**PB.SCHED))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs = []
     kw = dict(num_inference_steps=steps, guidance_scale=gs)
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, latents=lat0.clone(),
@@ -183,29 +154,15 @@ def run_pipeline():
         o = ops.plms_update(xs[i], unet.outs[i][:2].contiguous(), unet.outs[i][2:].contiguous(), P, H,
                             torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, 0.0)
         replay_off += RB.exact_off(o, xs[i + 1])
-    sch64 = PB.counting(PNDMScheduler(**PB.SCHED))
-    generic = StableDiffusionDenoiser(PB.Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), fused_update=False, **kw)
+    sch64 = counting(PNDMScheduler(**PB.SCHED))
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(pe, ne, latents=lat0.double(), fused_update=False, **kw)
     E = PB.accumulated(xs[:-1], states, unet.outs, coef64, gs, 0.0)
     return {"launches": len(unet.outs), "stepped": stepped, "generic_stepped": sch64.step_calls, "replay_off": replay_off,
             "finite": bool(torch.isfinite(fused).all().item()), "elem": _lib.ELEM_NAME, "generic_dtype": str(generic.dtype),
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [(k, (lambda k=k: run_case(k))) for k in PB.CASES] + [("graph", run_graph), ("refusals", run_refusals), ("pipeline", run_pipeline)]
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("PLMS_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("PLMS_JSON", [(k, (lambda k=k: run_case(k))) for k in PB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])

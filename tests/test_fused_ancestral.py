@@ -3,7 +3,7 @@ EulerAncestralDiscreteScheduler on the emulated device (tests/abi_emulator_ances
 mi355x_sd_ancestral_update per step, scheduler.step never called -- and ends where the pipeline's own fused_update=False loop ends
 under the same generator seed when that is run in float64 on the model outputs the fused loop saw, to the bound of
 tests/ancestral_bounds.py accumulated over the steps. (float64 randn draws other numbers than float32 from one seed: the float64 loop's
-step is handed the float32 draw of its generator, widened -- AB.counting.) The pipeline's unmodified float32 generic loop under the
+step is handed the float32 draw of its generator, widened -- counting of tests/step_pieces.py.) The pipeline's unmodified float32 generic loop under the
 same seed is run too: it leaves the generator where the fused loop leaves it."""
 import pytest
 import torch
@@ -16,6 +16,7 @@ from tests.abi_emulator import _flat, on_emulator
 from tests.abi_emulator_ancestral import AncestralEmulator
 from tests.abi_emulator_multistep import MultistepEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay, counting
 
 STEPS, SEED = 8, 7
 
@@ -44,7 +45,7 @@ def _gen():
 
 
 def _scheduler(widen=False, **kw):
-    return AB.counting(EulerAncestralDiscreteScheduler(**AB.SCHED, **kw), widen)
+    return counting(EulerAncestralDiscreteScheduler(**AB.SCHED, **kw), widen)
 
 
 @pytest.mark.parametrize("which", ["no_cfg", "cfg", "cfg_rescale", "v_prediction", "img2img", "inpaint"])
@@ -56,7 +57,7 @@ def test_fused_ancestral_loop_on_the_emulated_device(which):
     sch = _scheduler(**skw)
     emu = _State()
     P = synth_unet_params(TINY, seed=1234)
-    unet = AB.Recording(on_emulator(UNet2DConditionModel, TINY, P, backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, P, backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -98,7 +99,7 @@ def test_fused_ancestral_loop_on_the_emulated_device(which):
     if "latents" in call:
         call = dict(latents=lat0.double())
     g64 = _gen()
-    generic = StableDiffusionDenoiser(AB.Replay(unet.config, unet.outs), sch64)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(
         pe, ne if cfg else None, generator=g64, fused_update=False, **call, **kw)
     assert generic.dtype == torch.float64 and sch64.step_calls == run
     assert torch.equal(torch.randn(5, generator=g64), torch.randn(5, generator=_after(run, which, pipe, sch, lat0, first)))
@@ -109,7 +110,7 @@ def test_fused_ancestral_loop_on_the_emulated_device(which):
     sch32, g32 = _scheduler(**skw), _gen()
     if "latents" in call:
         call = dict(latents=lat0.clone())
-    plain = StableDiffusionDenoiser(AB.Replay(unet.config, unet.outs, dtype=torch.float32), sch32)(
+    plain = StableDiffusionDenoiser(Replay(unet.config, unet.outs, dtype=torch.float32), sch32)(
         pe, ne if cfg else None, generator=g32, fused_update=False, **call, **kw)
     assert sch32.step_calls == run and torch.equal(torch.randn(5, generator=g32), torch.randn(5, generator=_after(run, which, pipe, sch, lat0, first)))
     print(f"{which}: {run} steps, |fused - generic float64| / accumulated bound {ratio:.3f}; bound / |latent| at most "

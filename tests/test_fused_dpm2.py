@@ -14,6 +14,7 @@ from tests.abi_emulator import _flat, on_emulator
 from tests.abi_emulator_dpm2 import Dpm2Emulator
 from tests.abi_emulator_heun import HeunEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay
 
 STEPS, SEED = 8, 7
 BOTH = pytest.mark.parametrize("sampler", ["dpm2", "dpm2a"])
@@ -55,7 +56,7 @@ def test_fused_dpm2_loop_on_the_emulated_device(sampler, which):
     pe, ne, lat0 = _loop_inputs()
     sch = DB.scheduler(sampler, **skw)
     emu = _State()
-    unet = DB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -98,7 +99,7 @@ def test_fused_dpm2_loop_on_the_emulated_device(sampler, which):
     if "latents" in call:
         call = dict(latents=lat0.double())
     g64 = _gen()
-    generic = StableDiffusionDenoiser(DB.Replay(unet.config, unet.outs), sch64)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(
         pe, ne if cfg else None, generator=g64, fused_update=False, **call, **kw)
     assert generic.dtype == torch.float64 and sch64.step_calls == run and torch.equal(g64.get_state(), after)
     xs = [start] + xs
@@ -114,7 +115,7 @@ def test_fused_dpm2_loop_on_the_emulated_device(sampler, which):
     if "latents" in call:
         call = dict(latents=lat0.clone())
     g32 = _gen()
-    plain = StableDiffusionDenoiser(DB.Replay(unet.config, unet.outs, dtype=torch.float32), DB.scheduler(sampler, **skw))(
+    plain = StableDiffusionDenoiser(Replay(unet.config, unet.outs, dtype=torch.float32), DB.scheduler(sampler, **skw))(
         pe, ne if cfg else None, generator=g32, fused_update=False, **call, **kw)
     assert torch.equal(g32.get_state(), after)
     print(f"{sampler} {which}: {run} launches, |fused - generic float64| / accumulated bound {ratio:.3f}; bound / |latent| at most "

@@ -14,6 +14,7 @@ from tests.abi_emulator import _flat, on_emulator
 from tests.abi_emulator_ancestral import AncestralEmulator
 from tests.abi_emulator_heun import HeunEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay, counting
 
 STEPS = 8
 
@@ -39,7 +40,7 @@ def _loop_inputs():
 
 
 def _scheduler(**kw):
-    return HB.counting(HeunDiscreteScheduler(**HB.SCHED, **kw))
+    return counting(HeunDiscreteScheduler(**HB.SCHED, **kw))
 
 
 def _gen():
@@ -55,7 +56,7 @@ def test_fused_heun_loop_on_the_emulated_device(which):
     pe, ne, lat0 = _loop_inputs()
     sch = _scheduler(**skw)
     emu = _State()
-    unet = HB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -85,7 +86,7 @@ def test_fused_heun_loop_on_the_emulated_device(which):
     else:
         start, call = lat0 * sigma0, dict(latents=lat0.double())
     sch64 = _scheduler(**skw)
-    generic = StableDiffusionDenoiser(HB.Replay(unet.config, unet.outs), sch64)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(
         pe, ne if cfg else None, generator=_gen(), fused_update=False, **call, **kw)
     assert generic.dtype == torch.float64 and sch64.step_calls == run
     xs = [start] + xs
@@ -100,7 +101,7 @@ def test_fused_heun_loop_on_the_emulated_device(which):
     # and the unmodified float32 generic loop: reported
     if "latents" in call:
         call = dict(latents=lat0.clone())
-    plain = StableDiffusionDenoiser(HB.Replay(unet.config, unet.outs, dtype=torch.float32), _scheduler(**skw))(
+    plain = StableDiffusionDenoiser(Replay(unet.config, unet.outs, dtype=torch.float32), _scheduler(**skw))(
         pe, ne if cfg else None, generator=_gen(), fused_update=False, **call, **kw)
     print(f"{which}: {run} launches, |fused - generic float64| / accumulated bound {ratio:.3f}; bound / |latent| at most "
           f"{float((E[-1] / generic.abs()).max()):.2e}; |fused - generic float32| / |latent| at most "

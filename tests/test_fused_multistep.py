@@ -12,6 +12,7 @@ from tests import multistep_bounds as MB
 from tests.abi_emulator import Emulator, _flat, on_emulator
 from tests.abi_emulator_multistep import MultistepEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay
 
 STEPS = 6
 
@@ -52,7 +53,7 @@ def test_fused_multistep_loop_on_the_emulated_device(which):
     pe, ne, lat0 = _loop_inputs()
     sch = _scheduler()
     emu = _History()
-    unet = MB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -78,7 +79,7 @@ def test_fused_multistep_loop_on_the_emulated_device(which):
     if which == "img2img":   # (the pipeline's own img2img start is cast to fp32: its lines, driven here in float64)
         generic = MB.generic_loop(sch, ts, start, unet.outs, gs, gr, cfg)
     else:
-        generic = StableDiffusionDenoiser(MB.Replay(unet.config, unet.outs), sch)(
+        generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
             pe, ne if cfg else None, latents=lat0.double(), fused_update=False, **kw)
     assert generic.dtype == torch.float64 and sch.step_calls == run
     hs = [h.reshape(lat0.shape) for h in emu.hs]

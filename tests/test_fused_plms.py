@@ -20,6 +20,7 @@ from tests.abi_emulator import _flat, on_emulator
 from tests.abi_emulator_dpm2 import Dpm2Emulator
 from tests.abi_emulator_plms import PlmsEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay, counting
 
 STEPS = 8
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,7 +47,7 @@ def _loop_inputs():
 
 
 def _scheduler(**kw):
-    return PB.counting(PNDMScheduler(**dict(PB.SCHED, **kw)))
+    return counting(PNDMScheduler(**dict(PB.SCHED, **kw)))
 
 
 def _gen():
@@ -75,7 +76,7 @@ def test_fused_plms_loop_on_the_emulated_device(which):
     pe, ne, lat0 = _loop_inputs()
     sch = _scheduler(**skw)
     emu = _State()
-    unet = PB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -104,7 +105,7 @@ def test_fused_plms_loop_on_the_emulated_device(which):
     else:
         start, call = lat0 * sch.init_noise_sigma, dict(latents=lat0.double())
     sch64 = _scheduler(**skw)
-    generic = StableDiffusionDenoiser(PB.Replay(unet.config, unet.outs), sch64)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch64)(
         pe, ne if cfg else None, generator=_gen(), fused_update=False, **call, **kw)
     assert generic.dtype == torch.float64 and sch64.step_calls == run and sch64.counter == run
     xs = [start] + xs
@@ -115,7 +116,7 @@ def test_fused_plms_loop_on_the_emulated_device(which):
     # and the unmodified float32 generic loop: reported
     if "latents" in call:
         call = dict(latents=lat0.clone())
-    plain = StableDiffusionDenoiser(PB.Replay(unet.config, unet.outs, dtype=torch.float32), _scheduler(**skw))(
+    plain = StableDiffusionDenoiser(Replay(unet.config, unet.outs, dtype=torch.float32), _scheduler(**skw))(
         pe, ne if cfg else None, generator=_gen(), fused_update=False, **call, **kw)
     print(f"{which}: {run} launches, |fused - generic float64| / accumulated bound {ratio:.3f}; bound / |latent| at most "
           f"{float((E[-1] / generic.abs()).max()):.2e}; |fused - generic float32| / |latent| at most "

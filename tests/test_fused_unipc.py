@@ -13,6 +13,8 @@ from tests.abi_emulator import _flat, on_emulator
 from tests.abi_emulator_multistep import MultistepEmulator
 from tests.abi_emulator_unipc import UniPCEmulator
 from tests.configs import TINY
+from tests.multistep_bounds import generic_loop
+from tests.step_pieces import Recording, Replay
 
 STEPS = 8
 
@@ -57,7 +59,7 @@ def test_fused_unipc_loop_on_the_emulated_device(which, order):
     pe, ne, lat0 = _loop_inputs()
     sch = _scheduler(solver_order=order)
     emu = _State()
-    unet = UB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     kw = dict(num_inference_steps=STEPS, guidance_scale=gs, guidance_rescale=gr)
@@ -83,9 +85,9 @@ def test_fused_unipc_loop_on_the_emulated_device(which, order):
     assert coef64[0][11] == 0.0 and all(c[11] == 1.0 for c in coef64[1:])
     assert coef64[0][9] == 0.0 == coef64[-1][9] and all(c[9] != 0.0 for c in coef64[1:-1])
     if which == "img2img":   # (the pipeline's own img2img start is cast to fp32: its lines, driven here in float64)
-        generic = UB.generic_loop(sch, ts, start, unet.outs, gs, gr, cfg)
+        generic = generic_loop(sch, ts, start, unet.outs, gs, gr, cfg)
     else:
-        generic = StableDiffusionDenoiser(UB.Replay(unet.config, unet.outs), sch)(
+        generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
             pe, ne if cfg else None, latents=lat0.double(), fused_update=False, **kw)
     assert generic.dtype == torch.float64 and sch.step_calls == run
     lasts = [v.reshape(lat0.shape) for v in emu.lasts]
@@ -112,7 +114,7 @@ def test_routing_around_the_unipc_entry():
     # the generic one in float64 on the model outputs the fused loop saw, to the accumulated bound (which carries the latents' error
     # through the halving unscaled: an over-estimate)
     sch3, emu3 = _scheduler(), _State()
-    unet3 = UB.Recording(on_emulator(UNet2DConditionModel, TINY, P, backend=emu3))
+    unet3 = Recording(on_emulator(UNet2DConditionModel, TINY, P, backend=emu3))
     xs = [lat0]
 
     def swap(p, i, t, k):
@@ -122,7 +124,7 @@ def test_routing_around_the_unipc_entry():
     assert emu3.calls.count("unipc_update") == 4 and sch3.step_calls == 0
     coef64 = [sch3.unipc_coefficients(t) for t in sch3.timesteps]
     sch3.set_timesteps(4)
-    d = StableDiffusionDenoiser(UB.Replay(unet3.config, unet3.outs), sch3)(
+    d = StableDiffusionDenoiser(Replay(unet3.config, unet3.outs), sch3)(
         pe, ne, latents=lat0.double(), callback_on_step_end=lambda p, i, t, k: {"latents": k["latents"] * 0.5}, fused_update=False, **kw)
     assert d.dtype == torch.float64 and sch3.step_calls == 4
     E = UB.accumulated(xs[:-1], [v.reshape(lat0.shape) for v in emu3.lasts], [v.reshape((2,) + tuple(lat0.shape)) for v in emu3.hists],

@@ -15,6 +15,7 @@ from tests import guidance_bounds as GB
 from tests.abi_emulator import Emulator, on_emulator
 from tests.abi_emulator_guidance import GuidanceEmulator
 from tests.configs import TINY
+from tests.step_pieces import Recording, Replay
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 U64 = 2.0 ** -53
@@ -80,7 +81,7 @@ def test_fused_rescale_loop_on_the_emulated_device(which):
     pe, ne, lat0 = _loop_inputs()
     sch = _schedulers("v_prediction")[which == "euler"][0]
     emu = GuidanceEmulator()
-    unet = GB.Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
+    unet = Recording(on_emulator(UNet2DConditionModel, TINY, synth_unet_params(TINY, seed=1234), backend=emu))
     pipe = StableDiffusionDenoiser(unet, sch)
     xs = []
     fused = pipe(pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr, latents=lat0.clone(),
@@ -96,7 +97,7 @@ def test_fused_rescale_loop_on_the_emulated_device(which):
         coef64.append(sch.step_coefficients(t))
     if which == "euler":
         sch._step_index = None
-    generic = StableDiffusionDenoiser(GB.Replay(unet.config, unet.outs), sch)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
         pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr, latents=lat0.double(), fused_update=False)
     assert generic.dtype == torch.float64
     E = GB.accumulated(xs[:-1], unet.outs, coef64, gs, gr, sigma0)

@@ -16,6 +16,7 @@ from tests import multistep_bounds as MB
 from tests.abi_emulator import on_emulator
 from tests.abi_emulator_multistep import MultistepEmulator, emulate
 from tests.configs import TINY
+from tests.rowmap_bounds import check
 
 OFFSET = "b2 n4092 offset 64"
 U64 = 2.0 ** -53
@@ -24,7 +25,7 @@ U64 = 2.0 ** -53
 def _ratios(v, out, m0):
     r = MB.multistep_update(v["x"], v["eu"], v["et"], v["m1"], v["coef"], v["gs"], v["gr"])
     assert torch.isfinite(r["e_out"]).all() and torch.isfinite(r["e_m0"]).all()
-    return MB.check(out, r["out"], r["e_out"]), MB.check(m0, r["m0"], r["e_m0"])
+    return check(out, r["out"], r["e_out"]), check(m0, r["m0"], r["e_m0"])
 
 
 @pytest.mark.parametrize("name", list(MB.CASES))

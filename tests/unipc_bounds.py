@@ -39,9 +39,10 @@ Terms with a zero coefficient are skipped here as in the kernel (their E may be 
 import torch
 
 from paddlemix_amd.schedulers import UniPCMultistepScheduler
-from tests.multistep_bounds import SCHED, Recording, Replay, check, generic_loop, guided  # noqa: F401  (re-exported)
 from tests.guidance_bounds import RESIDENT
-from tests.rowmap_bounds import U32
+from tests.multistep_bounds import SCHED, guided
+from tests.rowmap_bounds import U32, check
+from tests.step_pieces import base_inputs
 
 NAMES = ("p", "q", "Ac", "Bc", "C2", "C3", "Ct", "Ap", "Bp", "D1", "D2", "corr")
 
@@ -92,18 +93,14 @@ CASES = {   # name: batch, per_sample, hist planes and what differs from gs = 7.
 def inputs(name):
     """dict(x, eu, et (None: no guidance), last, hist [order, batch, n], coef, gs, gr, order) of a case: CPU fp32, seeded by the name"""
     s = CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    shape = (s["batch"], s["n"])
-    x = 3.0 * torch.randn(shape, generator=g)
-    eu = torch.randn(shape, generator=g)
-    et = eu + 0.3 * torch.randn(shape, generator=g)
+    g, shape, x, eu, et = base_inputs(name, s)
     last = 3.0 * torch.randn(shape, generator=g)
     hist = 2.0 * torch.randn((s["order"],) + shape, generator=g)
     if s.get("nan_state"):
         last, hist = torch.full_like(last, float("nan")), torch.full_like(hist, float("nan"))
     if s.get("nan_old"):
         hist[1:] = float("nan")
-    return dict(x=x, eu=eu, et=et if s.get("cfg", True) else None, last=last, hist=hist,
+    return dict(x=x, eu=eu, et=et, last=last, hist=hist,
                 coef=torch.tensor(ROW[s.get("row", "full3")], dtype=torch.float32), gs=s.get("gs", 7.5), gr=s.get("gr", 0.0),
                 order=s["order"])
 

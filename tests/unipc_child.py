@@ -9,7 +9,6 @@ consecutive rows against three direct launches, the refusals, and an 8-step pipe
 """
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -18,11 +17,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
 from tests import unipc_bounds as UB  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.guidance_child import _graph_shape  # noqa: E402
-from tests.multistep_child import _offset_in  # noqa: E402
-from tests.norm_child import CANARY32, _canary, _counts  # noqa: E402
-from tests.rowmap_child import _flat_in  # noqa: E402
+from tests.step_child import _in, _out, capture, main, overwritten, refusals, replay_rows, tally  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
+from tests.step_pieces import Recording, Replay  # noqa: E402
 
 
 def _call(lib, x, eu, et, last, hist, order, out, coef, gs, gr, batch, n, st):
@@ -32,9 +29,9 @@ def _call(lib, x, eu, et, last, hist, order, out, coef, gs, gr, batch, n, st):
 
 def _state_in(vals):
     """the state values in a view of a canary buffer: (view, bits, mask)"""
-    view, bits, inside = _canary((1, vals.numel()), vals.numel(), 32)
-    view[0].copy_(vals.reshape(-1))
-    return view[0], bits, inside
+    view, bits, inside = _out(vals.numel())
+    view.copy_(vals.reshape(-1))
+    return view, bits, inside
 
 
 def run_case(name):
@@ -42,26 +39,23 @@ def run_case(name):
     v = UB.inputs(name)
     s = UB.CASES[name]
     (batch, n), order = v["x"].shape, v["order"]
-    eu = _flat_in(v["eu"].reshape(-1).cuda())
-    et = None if v["et"] is None else _flat_in(v["et"].reshape(-1).cuda())
-    cin = _flat_in(v["coef"].cuda())
+    eu, cin = _in(v["eu"]), _in(v["coef"])
+    et = None if v["et"] is None else _in(v["et"])
     res = {"unwritten": 0, "overwritten": 0}
     got = []
     for _ in range(2):
-        ov, obits, oin = _canary((1, batch * n), batch * n, 32)
-        out = ov[0]
+        out, obits, oin = _out(batch * n)
         last, lbits, lin = _state_in(v["last"].cuda())
         hist, hbits, hin = _state_in(v["hist"].cuda())
         if s.get("alias"):   # out = x, as a loop with one latent buffer
             out.copy_(v["x"].reshape(-1))
             xin = out
         else:
-            xin = (_offset_in if s.get("misalign") else _flat_in)(v["x"].reshape(-1).cuda())
+            xin = _in(v["x"], int(bool(s.get("misalign"))))   # (misalign: one element past a 16-byte boundary)
         res["rc"] = _call(lib, xin, eu, et, last, hist, order, out, cin, v["gs"], v["gr"], batch, n, st)
         torch.cuda.synchronize()
-        uw, ow = _counts(obits, oin, CANARY32)
-        res["unwritten"] += uw
-        res["overwritten"] += ow + _counts(lbits, lin, CANARY32)[1] + _counts(hbits, hin, CANARY32)[1]
+        tally(res, obits, oin)
+        res["overwritten"] += overwritten(lbits, lin) + overwritten(hbits, hin)
         got.append((out.clone(), last.clone(), hist.clone()))
     dev = {k: (t.cuda() if torch.is_tensor(t) else t) for k, t in v.items()}
     dev["coef"] = v["coef"]
@@ -96,60 +90,38 @@ def run_graph():
     res = {"rc_direct": rc, "finite": bool(all(torch.isfinite(t).all() for t in direct[-1]))}
     x, last, hist = fresh()
     cur = torch.zeros(12, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g, stream=s):
-        res["rc"] = _call(lib, x, v["eu"], v["et"], last, hist, order, x, cur, gs, gr, batch, n, torch.cuda.current_stream().cuda_stream)
-    res["nodes"], res["roots"], res["edges"] = _graph_shape(g)
-    g.instantiate()
+    g = capture(res, lambda st: _call(lib, x, v["eu"], v["et"], last, hist, order, x, cur, gs, gr, batch, n, st))
     x.copy_(v["x"])   # (the capture launched nothing, but the loop starts from the inputs whatever it did)
     last.fill_(float("nan"))
     hist.fill_(float("nan"))
-    off = 0
-    for i in range(3):
-        cur.copy_(table[i])
-        g.replay()
-        torch.cuda.synchronize()
-        off += sum(RB.exact_off(a, b) for a, b in zip((x, last, hist), direct[i]))
-    res["replay_off"] = off
+    res["replay_off"] = replay_rows(g, cur, table, (x, last, hist), direct)
     return res
+
+
+def _deviations(but, n, x, eu, et, last, hist, out, coef):
+    return {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
+            "out overlaps eps_uncond": but(out=eu - 4),
+            "out overlaps x partly": but(out=x + 4, n=n // 2),
+            "out is last": but(out=last),
+            "out overlaps the third plane of hist": but(out=hist + 4 * (3 * n - 1)),
+            "out overlaps coef": but(out=coef - 4 * (n - 1)),
+            "last is x": but(last=x),
+            "last overlaps hist": but(last=hist - 4 * (n - 1)),
+            "last overlaps eps_text": but(last=et),
+            "hist is x": but(hist=x),
+            "hist planes reach last": but(hist=last - 4 * 2 * n),
+            "hist overlaps coef": but(hist=coef - 4 * (3 * n - 2)),
+            "order 0": but(order=0), "order 4": but(order=4),
+            "coef not 16-byte aligned": but(coef=coef + 4),
+            "per_sample 0": but(n=0),
+            "per_sample 1 with rescale": but(batch=n, n=1),
+            "batch 0": but(batch=0),
+            "null x": but(x=None), "null eps_uncond": but(eu=None), "null last": but(last=None), "null hist": but(hist=None),
+            "null out": but(out=None), "null coef": but(coef=None)}
 
 
 def run_refusals():
-    lib, st = _lib.load(), ops._stream()
-    n = 4096
-    buf = torch.full((16 * n,), 7.25, device="cuda")
-    p = buf.data_ptr()
-    x, eu, et, last, hist, out, coef = (p + 4 * n * k for k in (0, 1, 2, 3, 5, 9, 11))   # hist: 3 planes, 5 .. 7
-    ok = (x, eu, et, last, hist, 3, out, coef, 7.5, 0.7, 1, n)
-
-    def but(**kw):
-        names = ("x", "eu", "et", "last", "hist", "order", "out", "coef", "gs", "gr", "batch", "n")
-        return tuple(kw.get(k, a) for k, a in zip(names, ok))
-    calls = {"out overlaps eps_text": but(out=et + 4 * (n - 1)),
-             "out overlaps eps_uncond": but(out=eu - 4),
-             "out overlaps x partly": but(out=x + 4, n=n // 2),
-             "out is last": but(out=last),
-             "out overlaps the third plane of hist": but(out=hist + 4 * (3 * n - 1)),
-             "out overlaps coef": but(out=coef - 4 * (n - 1)),
-             "last is x": but(last=x),
-             "last overlaps hist": but(last=hist - 4 * (n - 1)),
-             "last overlaps eps_text": but(last=et),
-             "hist is x": but(hist=x),
-             "hist planes reach last": but(hist=last - 4 * 2 * n),
-             "hist overlaps coef": but(hist=coef - 4 * (3 * n - 2)),
-             "order 0": but(order=0), "order 4": but(order=4),
-             "coef not 16-byte aligned": but(coef=coef + 4),
-             "per_sample 0": but(n=0),
-             "per_sample 1 with rescale": but(batch=n, n=1),
-             "batch 0": but(batch=0),
-             "null x": but(x=None), "null eps_uncond": but(eu=None), "null last": but(last=None), "null hist": but(hist=None),
-             "null out": but(out=None), "null coef": but(coef=None)}
-    res = {k: lib.mi355x_sd_unipc_update(*a, st) for k, a in calls.items()}
-    torch.cuda.synchronize()
-    res["touched"] = int((buf != 7.25).sum().item())
-    return res
+    return refusals(FORMS["unipc"], 16, (0, 1, 2, 3, 5, 9, 11), _deviations)   # hist: 3 planes, 5 .. 7
 
 
 def run_pipeline():
@@ -164,7 +136,7 @@ def run_pipeline():
     g = torch.Generator().manual_seed(0)
     pe, ne, lat0 = (torch.randn(s, generator=g).cuda() for s in ((2, 7, 64), (2, 7, 64), (2, 4, 8, 8)))
     sch = UniPCMultistepScheduler(solver_order=order, **UB.SCHED)
-    unet = UB.Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
+    unet = Recording(UNet2DConditionModel(TINY, synth_unet_params(TINY, seed=1234), device="cuda:0"))
     xs = []
     fused = StableDiffusionDenoiser(unet, sch)(pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr,
                                                latents=lat0.clone(),
@@ -182,7 +154,7 @@ def run_pipeline():
         o = ops.unipc_update(xs[i], unet.outs[i][:2].contiguous(), unet.outs[i][2:].contiguous(), last, hist,
                              torch.tensor(coef64[i], dtype=torch.float32).cuda(), gs, gr)
         replay_off += RB.exact_off(o, xs[i + 1])
-    generic = StableDiffusionDenoiser(UB.Replay(unet.config, unet.outs), sch)(
+    generic = StableDiffusionDenoiser(Replay(unet.config, unet.outs), sch)(
         pe, ne, num_inference_steps=steps, guidance_scale=gs, guidance_rescale=gr, latents=lat0.double(), fused_update=False)
     E = UB.accumulated(xs[:-1], lasts, hists, unet.outs, coef64, gs, gr, order)
     return {"steps": len(unet.outs), "stepped": stepped, "generic_stepped": sch.step_index, "replay_off": replay_off,
@@ -190,23 +162,7 @@ def run_pipeline():
             "ratio": ((fused.double() - generic).abs() / E[-1]).max().item()}
 
 
-def main():
-    t0 = time.time()
-    ops.init(0)
-    res = {}
-    todo = [("pipeline", run_pipeline)]
-    if sys.argv[1:] != ["pipeline"]:
-        todo = [(k, (lambda k=k: run_case(k))) for k in UB.CASES] + [("graph", run_graph), ("refusals", run_refusals)] + todo
-    for name, fn in todo:
-        try:
-            res[name] = fn()
-        except (ValueError, TypeError, IndexError, KeyError, AttributeError, OSError, StopIteration, ZeroDivisionError, AssertionError,
-                _lib.MI355XError) as ex:   # a mistake of the case's own host code: that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    res["seconds"] = round(time.time() - t0, 1)
-    emit("UNIPC_JSON", res)
-
 
 if __name__ == "__main__":
-    main()
+    main("UNIPC_JSON", [(k, (lambda k=k: run_case(k))) for k in UB.CASES] + [("graph", run_graph), ("refusals", run_refusals)],
+         [("pipeline", run_pipeline)])
