@@ -132,7 +132,8 @@ int mi355x_sd_unet_forward_ex(void* handle, void* stream, const float* sample, c
  * time_cond_proj_dim reads them in every forward (unet_2d_condition.py:953-975; embeddings.py:284-285) -- are bound by name, not
  * passed per call: device pointers, read (copied into the plan's static buffers, on the call's stream) by every forward[_ex] call
  * from then on, until replaced; NULL unbinds.
- *   "class_labels"   class_embed_type null + num_class_embeds: int32 [B], the row of the nn.Embedding table per sample;
+ *   "class_labels"   class_embed_type null + num_class_embeds: int32 [B], the row of the nn.Embedding table per sample -- every
+ *                    label must lie in [0, num_class_embeds): the gather reads the table at the index it is given, unchecked;
  *                    "timestep": fp32 [B] (goes through time_proj and a TimestepEmbedding); "projection" / "simple_projection":
  *                    fp32 [B, projection_class_embeddings_input_dim]; "identity": fp32 [B, 4 * block_out_channels[0]].
  *                    A forward call of such a model with nothing bound is MI355X_SD_ERR_INVALID (the reference's ValueError,

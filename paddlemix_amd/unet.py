@@ -28,7 +28,7 @@ from typing import Dict, List, Mapping, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import GEGLU, OUT_F32, SILU
+from ._lib import GEGLU, OUT_F32, SDPA_LOG2, SILU
 from .checkpoint import PretrainedMixin, Table
 from .program import DeviceProgram, PlanBuilder, _Plan, _V
 
@@ -286,8 +286,581 @@ def synth_unet_params(config: Mapping, seed: int = 1234, device="cpu", dtype=tor
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# program builder
+# weights and program: each a small object whose methods are the stages, under the names csrc/unet_weights.hip (Packer) and
+# csrc/unet_plan.hip (Planner) use for the same stages -- a change to one has its counterpart in the stage of that name there
 # ---------------------------------------------------------------------------------------------------------------
+class _UNetWeights:
+    """The reference's parameters (its names, Paddle layouts) repacked once for the kernels into ``model.w``. Stages: ``stem`` (conv_in
+    and the embeddings), ``resnet``, ``transformer`` / ``transformer_block``, ``sampler``, ``batched`` (what the layers contribute to the
+    one-GEMM-per-step matrices), ``head``."""
+
+    def __init__(self, model: "UNet2DConditionModel", params: Mapping[str, Tensor]):
+        self.m, self.cfg, self.W, self.params, self.shapes = model, model.cfg, model.w, params, model._shapes()
+        missing = [k for k in self.shapes if k not in params]
+        if missing:
+            raise KeyError(f"missing parameters: {missing[:5]}{'...' if len(missing) > 5 else ''}")
+        model._kb64 = set()
+        model._log2_blocks = set()   # transformer blocks whose self-attention scores are base-2 exponents (fold_softmax_scale)
+        model._temb_off, model._kv_off = {}, {}   # where a resnet's time_emb_proj / a block's to_k, to_v sit in temb_all / kv_all
+        self.temb_w, self.temb_b = [], []
+        self.kv_w, self.kvip_w = [], []            # every cross-attention to_k / to_v (IPAdapterAttnProcessor: to_k_ip / to_v_ip, same offsets)
+
+    def load(self) -> None:
+        self.stem()
+        for d in self.m._layers:
+            if d[0] == "resnet":
+                self.resnet(d[1], d[2], d[3])
+            elif d[0] == "attn":
+                self.transformer(*d[1:5])
+            elif d[0] in ("down", "up"):
+                self.sampler(d[1])
+        self.batched()
+        self.head()
+
+    def get(self, name):
+        t = self.params[name]
+        if tuple(t.shape) != self.shapes[name]:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != expected {self.shapes[name]} (Paddle layout)")
+        return t.to(device=self.m.device, dtype=torch.float32)
+
+    @staticmethod
+    def bf(t):
+        return t.to(_lib.elem_dtype()).contiguous()
+
+    def lin_w(self, name):  # Paddle [in,out] -> [out,in]
+        return self.get(name + ".weight").t()
+
+    def put_lin(self, key, name, bias=True):
+        self.W[key + ".w"] = self.bf(self.lin_w(name))
+        if bias:
+            self.W[key + ".b"] = self.get(name + ".bias").contiguous()
+
+    def put_conv(self, key, name):  # OIHW -> [O][kh][kw][I]; 3x3 with Cin % 64 == 0 -> [O][I/64][kh][kw][64] (MI355X_SD_CONV_KB64)
+        w = self.get(name + ".weight")
+        O, I, kh, kw = w.shape
+        if kh == 3 and I % 64 == 0:
+            self.W[key + ".w"] = self.bf(w.reshape(O, I // 64, 64, kh, kw).permute(0, 1, 3, 4, 2).reshape(O, -1))
+            self.m._kb64.add(key)
+        else:
+            self.W[key + ".w"] = self.bf(w.permute(0, 2, 3, 1).reshape(O, -1))
+        self.W[key + ".b"] = self.get(name + ".bias").contiguous()
+
+    def put_conv_in(self, key, w, name):  # -> [ky][kx][ci][O], the conv_in kernel's layout
+        self.W[key + ".w"] = self.bf(w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]))
+        self.W[key + ".b"] = self.get(name + ".bias").contiguous()
+
+    def put_norm(self, key, name):
+        self.W[key + ".g"] = self.get(name + ".weight").contiguous()
+        self.W[key + ".b"] = self.get(name + ".bias").contiguous()
+
+    def put_ln_lin(self, key, w, bias, norm):
+        """LayerNorm `norm` folded into the projection w [N, K] (mi355x_sd_linear_ln): W' = W diag(gamma) in bf16,
+        ws = row sums of the bf16 W' (what the MFMAs actually sum), b' = bias + W beta."""
+        wp_ = self.bf(w * self.get(norm + ".weight")[None, :])
+        self.W[key + ".w"] = wp_
+        self.W[key + ".ws"] = wp_.float().sum(1).contiguous()
+        bb = w @ self.get(norm + ".bias")
+        self.W[key + ".b"] = (bb if bias is None else bias + bb).contiguous()
+
+    # ---- stages ----
+    def stem(self):
+        cfg, put_lin = self.cfg, self.put_lin
+        self.put_conv_in("conv_in", self.get("conv_in.weight"), "conv_in")
+        put_lin("time_embedding.linear_1", "time_embedding.linear_1")
+        put_lin("time_embedding.linear_2", "time_embedding.linear_2")
+        if cfg["addition_embed_type"] == "text_time":
+            put_lin("add_embedding.linear_1", "add_embedding.linear_1")
+            put_lin("add_embedding.linear_2", "add_embedding.linear_2")
+        if cfg["time_cond_proj_dim"] is not None:
+            put_lin("time_embedding.cond_proj", "time_embedding.cond_proj", bias=False)
+        if self.m._class_kind == "embedding":
+            self.W["class_embedding.table"] = self.bf(self.get("class_embedding.weight"))
+        elif self.m._class_kind in ("timestep", "projection"):
+            put_lin("class_embedding.linear_1", "class_embedding.linear_1")
+            put_lin("class_embedding.linear_2", "class_embedding.linear_2")
+        elif self.m._class_kind == "simple_projection":
+            put_lin("class_embedding", "class_embedding")
+        if self.m._ip:
+            put_lin("encoder_hid_proj.image_embeds", "encoder_hid_proj.image_embeds")
+            self.put_norm("encoder_hid_proj.norm", "encoder_hid_proj.norm")
+
+    def resnet(self, name, cin, cout):
+        self.put_norm(name + ".norm1", name + ".norm1")
+        self.put_conv(name + ".conv1", name + ".conv1")
+        self.m._temb_off[name] = sum(w.shape[0] for w in self.temb_w)
+        self.temb_w.append(self.lin_w(name + ".time_emb_proj"))
+        self.temb_b.append(self.get(name + ".time_emb_proj.bias"))
+        self.put_norm(name + ".norm2", name + ".norm2")
+        self.put_conv(name + ".conv2", name + ".conv2")
+        if cin != cout:
+            self.put_conv(name + ".conv_shortcut", name + ".conv_shortcut")
+
+    def transformer(self, name, c, heads, layers):
+        self.put_norm(name + ".norm", name + ".norm")
+        put = self.put_lin if self.cfg["use_linear_projection"] else self.put_conv
+        put(name + ".proj_in", name + ".proj_in")
+        put(name + ".proj_out", name + ".proj_out")
+        for l in range(layers):
+            self.transformer_block(f"{name}.transformer_blocks.{l}", c, heads)
+
+    def transformer_block(self, b, c, heads):
+        m, W, lin_w, get = self.m, self.W, self.lin_w, self.get
+        wq = lin_w(b + ".attn1.to_q")
+        if m.fold_scale and c // heads == 64:
+            wq = wq * ((c // heads) ** -0.5 * 1.4426950408889634)
+            m._log2_blocks.add(b)
+        wqkv = torch.cat([wq, lin_w(b + ".attn1.to_k"), lin_w(b + ".attn1.to_v")], 0)
+        if m.fold_ln:
+            self.put_ln_lin(b + ".attn1.qkv", wqkv, None, b + ".norm1")
+            self.put_ln_lin(b + ".attn2.q", lin_w(b + ".attn2.to_q"), None, b + ".norm2")
+        else:
+            for nm in (".norm1", ".norm2", ".norm3"):
+                self.put_norm(b + nm, b + nm)
+            W[b + ".attn1.qkv.w"] = self.bf(wqkv)
+            W[b + ".attn2.q.w"] = self.bf(lin_w(b + ".attn2.to_q"))
+        self.put_lin(b + ".attn1.out", b + ".attn1.to_out.0")
+        if any(x != self.cfg["cross_attention_dim"][0] for x in self.cfg["cross_attention_dim"]):
+            raise NotImplementedError("per-block cross_attention_dim")
+        m._kv_off[b] = sum(w.shape[0] for w in self.kv_w)
+        self.kv_w.append(self.bf(torch.cat([lin_w(b + ".attn2.to_k"), lin_w(b + ".attn2.to_v")], 0)))
+        if m._ip:
+            self.kvip_w.append(self.bf(torch.cat([lin_w(b + ".attn2.processor.to_k_ip"), lin_w(b + ".attn2.processor.to_v_ip")], 0)))
+        self.put_lin(b + ".attn2.out", b + ".attn2.to_out.0")
+        # GEGLU: interleave [16 value rows | 16 gate rows] so a lane holds both halves of a pair
+        w1 = lin_w(b + ".ff.net.0.proj")  # [8c, c]
+        b1 = get(b + ".ff.net.0.proj.bias")
+        half = w1.shape[0] // 2
+        if m.fold_ln:   # norm3 folded in before the row interleave (a row permutation commutes with it)
+            b1 = b1 + w1 @ get(b + ".norm3.bias")
+            w1 = w1 * get(b + ".norm3.weight")[None, :]
+        W[b + ".ff1.w"] = self.bf(torch.stack([w1[:half].reshape(half // 16, 16, -1),
+                                               w1[half:].reshape(half // 16, 16, -1)], 1).reshape(2 * half, -1))
+        W[b + ".ff1.b"] = torch.stack([b1[:half].reshape(half // 16, 16), b1[half:].reshape(half // 16, 16)], 1).reshape(-1).contiguous()
+        if m.fold_ln:
+            W[b + ".ff1.ws"] = W[b + ".ff1.w"].float().sum(1).contiguous()
+        self.put_lin(b + ".ff2", b + ".ff.net.2")
+
+    def sampler(self, name):
+        self.put_conv(name, name)
+
+    def batched(self):
+        W, m = self.W, self.m
+        W["kv_all.w"] = torch.cat(self.kv_w, 0).contiguous()
+        if m._ip:
+            W["kvip_all.w"] = torch.cat(self.kvip_w, 0).contiguous()
+        m._kv_total = W["kv_all.w"].shape[0]
+        W["temb_all.w"] = self.bf(torch.cat(self.temb_w, 0))
+        W["temb_all.b"] = torch.cat(self.temb_b, 0).contiguous()
+        m._temb_total = W["temb_all.w"].shape[0]
+
+    def head(self):
+        self.put_norm("conv_norm_out", "conv_norm_out")
+        w = self.get("conv_out.weight")
+        self.W["conv_out.w"] = self.bf(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
+        self.W["conv_out.b"] = self.get("conv_out.bias").contiguous()
+
+
+class _UNetPlanner:
+    """The launch plan of one input geometry, written stage by stage: ``inputs``, ``time_embedding`` (with ``class_embedding`` around its
+    MLP), ``added_conditions``, ``block_embeddings``, ``context_kv``, ``skip_layout``, ``walk`` (``stem``, then per layer ``resnet`` /
+    ``transformer`` / ``downsample`` / ``upsample``, and ``controlnet_residuals`` where the up path starts) and ``head``. The attributes
+    are what crosses stages: ``emb_t`` / ``emb`` / ``cls_out``, ``temb_all``, ``kv_all``, ``kvip_all``, the masks' biases, the skip layout
+    (``skips``, ``ups``, ``cats``, ``cat_xc``, ``cat_hw``, ``own_skips``) and ``RES``; everything else is a local of one stage."""
+
+    def __init__(self, model: "UNet2DConditionModel", B, H, W, L, masked=False, controlnet=False, self_mask_len=0):
+        self.m, self.cfg, self.lib, self.stream = model, model.cfg, model._lib, model._stream_ptr
+        self.B, self.H, self.W, self.L = B, H, W, L
+        self.masked, self.controlnet, self.self_mask_len = masked, controlnet, self_mask_len
+        self.pb = PlanBuilder(model, B)
+        self.plan = self.pb.plan
+        self.ted = self.cfg["block_out_channels"][0] * 4
+        self.RES = 4 if model.resid_f32 else 2                       # bytes per element of the residual stream
+        self.tmp_i = 0
+
+    def build(self) -> _Plan:
+        self.inputs()
+        self.time_embedding()
+        self.added_conditions()
+        self.block_embeddings()
+        self.context_kv()
+        self.skip_layout()
+        self.head(*self.walk())
+        plan = self.pb.finish()
+        plan.B, plan.H, plan.W, plan.L = self.B, self.H, self.W, self.L
+        plan.scratch_bytes = sum(t.numel() * t.element_size() for t in plan.keep)
+        return plan
+
+    def rows(self, n, C) -> _V:
+        """a persistent buffer of n rows of C 16-bit elements"""
+        return _V(self.pb.persist((n, C), _lib.elem_dtype()).data_ptr(), n, C)
+
+    def sinusoid(self, t: Tensor, t_count, n, out: _V):
+        """Timesteps (flip_sin_to_cos / freq_shift of the config): t [t_count] -> out [n, out.C]"""
+        self.pb.emit(self.lib.mi355x_sd_timestep_embedding,
+                     (t.data_ptr(), t_count, n, out.C, 1, 1 if self.cfg["flip_sin_to_cos"] else 0, float(self.cfg["freq_shift"]), 1.0,
+                      10000.0, out.p, out.ld, self.stream), "misc")
+
+    def cast16(self, x: _V, name: str) -> _V:
+        """16-bit copy of fp32 rows (operand of the down / upsampling convs in the fp32-residual mode)"""
+        if x.es == 2:
+            return x
+        y = _V(self.pb.sc(name, 2 * x.rows * x.C), x.rows, x.C)
+        self.pb.emit(self.lib.mi355x_sd_cast_rows, (x.p, x.ld, y.p, y.ld, x.rows, x.C, self.stream), "misc")
+        return y
+
+    def ln_linear(self, x: _V, nkey: str, ln: Optional[_V], wkey: str, out: _V, bias=True, flags=0):
+        """LayerNorm (eps 1e-5, attention.py:318-331) into the scratch rows ``ln``, then the projection; ``ln`` None (fold_layernorm):
+        the LayerNorm is folded into the projection's weights -- statistics pass + raw-row GEMM"""
+        pb, lib, wp = self.pb, self.lib, self.pb.wp
+        if ln is not None:
+            pb.lnorm(x, nkey, ln)
+            return pb.linear(ln, wkey, out, bias=bias, flags=flags)
+        N, K = self.m.w[wkey + ".w"].shape
+        assert K == x.C, (wkey, K, x.C)
+        st = pb.sc("t_stats", 8 * x.rows)
+        pb.emit(lib.mi355x_sd_row_stats, (x.p, x.rows, x.C, x.ld, 1e-5, st, self.stream), "ln")
+        pb.emit(lib.mi355x_sd_linear_ln, (x.p, x.ld, st, wp(wkey + ".w"), wp(wkey + ".ws"), out.p, out.ld, x.rows, N, K,
+                                          wp(wkey + ".b"), flags, *self.m._gemm_ws, self.stream), "gemm", 2.0 * x.rows * N * K,
+                f"{x.rows}x{N}x{K}" + ("g" if flags & GEGLU else ""))
+
+    def attention(self, q: _V, k: _V, v: _V, out: _V, heads, sq, skv, bias=None, accum: Optional[float] = None, log2=False):
+        sdpa, lib = self.pb.sdpa, self.lib
+        if log2 and bias is not None:
+            # q already carries head_dim^-0.5 * log2(e) (folded into to_q at load) but the masked kernel exponentiates
+            # exp2((q.k + bias / scale) * scale * log2(e)): scale = ln 2 makes that exp2(q.k + bias * log2(e)) -- the same softmax
+            assert accum is None
+            sdpa(q, k, v, out, heads, sq, skv, bias, (skv, 0, 0), math.log(2.0), suffix="m")
+        elif log2:
+            assert accum is None and q.C // heads == 64
+            sdpa(q, k, v, out, heads, sq, skv, scale=1.0, fn=lib.mi355x_sd_sdpa_ex, tail=(SDPA_LOG2,))
+        elif accum is None:
+            # bias: additive encoder mask [B, skv] broadcast over heads and queries (unet_2d_condition.py:921-927)
+            sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0))
+        else:   # out += accum * attention (the image-token half of IPAdapterAttnProcessor)
+            sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0), fn=lib.mi355x_sd_sdpa_accum, tail=(float(accum),),
+                 suffix="+")
+
+    # ---- stages ----
+    def inputs(self):
+        """static buffers, staged by __call__"""
+        plan, persist, cfg, B, L = self.plan, self.pb.persist, self.cfg, self.B, self.L
+        plan.sample = persist((B, cfg["in_channels"], self.H, self.W), torch.float32)
+        plan.t = persist((1,), torch.float32)
+        plan.in_scale = persist((1,), torch.float32)
+        plan.in_scale.fill_(1.0)
+        plan.enc = persist((B * L, cfg["cross_attention_dim"][0]), _lib.elem_dtype())
+        plan.out = persist((B, cfg["out_channels"], self.H, self.W), torch.float32)
+        plan.enc_bias = persist((B, L), torch.float32) if self.masked else None
+        self.enc_bias = plan.enc_bias.data_ptr() if self.masked else None
+        # `attention_mask`: a key mask over the LATENT tokens, added to every self-attention (unet_2d_condition.py:916-923 ->
+        # BasicTransformerBlock.attn1, attention.py:417-423)
+        plan.self_bias = persist((B, self.self_mask_len), torch.float32) if self.self_mask_len else None
+        self.self_bias = plan.self_bias.data_ptr() if self.self_mask_len else None
+
+    def time_embedding(self):
+        """sinusoid, cond_proj, the time MLP (unet_2d_condition.py:933-951), with the class embedding's two halves around the MLP"""
+        plan, cfg, B, ted, linear = self.plan, self.cfg, self.B, self.ted, self.pb.linear
+        t0_t = self.pb.persist((B, cfg["block_out_channels"][0]), _lib.elem_dtype())
+        t0 = _V.of(t0_t)
+        self.sinusoid(plan.t, 1, B, t0)
+        e1 = self.rows(B, ted)
+        ted_b = ted * (2 if cfg["class_embeddings_concat"] else 1)
+        emb_t = self.pb.persist((B, ted_b), _lib.elem_dtype())
+        plan.emb_tensors = dict(t0=t0_t, emb=emb_t)
+        self.emb_t = _V.of(emb_t)
+        self.emb = self.emb_t.cols(0, ted)                 # the time-embedding half (all of it without concat)
+        self.cls_out = self.emb_t.cols(ted, ted) if ted_b > ted else None     # where the class embedding goes when concatenated
+        plan.class_in = None
+        pre_cls = self.class_embedding(before_mlp=True)
+        plan.tcond = None
+        if cfg["time_cond_proj_dim"] is not None:   # t_emb += cond_proj(timestep_cond) (embeddings.py:284-285; zeros when not given)
+            plan.tcond = self.pb.persist((B, cfg["time_cond_proj_dim"]), _lib.elem_dtype())
+            plan.tcond.zero_()
+            linear(_V.of(plan.tcond), "time_embedding.cond_proj", t0, bias=False, R=t0)
+        linear(t0, "time_embedding.linear_1", e1, flags=SILU)
+        linear(e1, "time_embedding.linear_2", self.emb, R=pre_cls)
+        self.class_embedding(before_mlp=False)
+
+    def class_embedding(self, before_mlp: bool) -> Optional[_V]:
+        """class embedding (unet_2d_condition.py:953-975): emb + class_emb, or [emb | class_emb] when class_embeddings_concat. The add
+        is the residual input of a GEMM epilogue, the concat is a GEMM / gather writing the upper columns. ``before_mlp``: a gathered /
+        identity embedding exists before the time MLP and is returned, to be added as the MLP's residual; the computed kinds follow it."""
+        plan, pb, cfg, B, ted, ck, cls_out = self.plan, self.pb, self.cfg, self.B, self.ted, self.m._class_kind, self.cls_out
+        if before_mlp and ck == "embedding":
+            plan.class_in = pb.persist((B,), torch.int32)
+            dst = cls_out or self.rows(B, ted)
+            pb.emit(self.lib.mi355x_sd_embed_tokens, (plan.class_in.data_ptr(), B, 1, pb.wp("class_embedding.table"), None, ted, dst.p,
+                                                      dst.ld, self.stream), "misc")
+            return None if cls_out else dst
+        if before_mlp and ck == "identity":
+            plan.class_in = pb.persist((B, ted), _lib.elem_dtype())
+            src = _V.of(plan.class_in)
+            if not cls_out:
+                return src
+            pb.emit(self.lib.mi355x_sd_copy_rows, (src.p, src.ld, cls_out.p, cls_out.ld, B, ted, self.stream), "misc")
+        if before_mlp or ck not in ("timestep", "projection", "simple_projection"):
+            return None
+        if ck == "timestep":   # class_labels -> sinusoid (time_proj) -> TimestepEmbedding
+            plan.class_in = pb.persist((B,), torch.float32)
+            cin = self.rows(B, cfg["block_out_channels"][0])
+            self.sinusoid(plan.class_in, B, B, cin)
+        else:
+            plan.class_in = pb.persist((B, cfg["projection_class_embeddings_input_dim"]), _lib.elem_dtype())
+            cin = _V.of(plan.class_in)
+        dst, res = (cls_out, None) if cls_out else (self.emb, self.emb)
+        if ck == "simple_projection":
+            pb.linear(cin, "class_embedding", dst, R=res)
+        else:
+            c1 = self.rows(B, ted)
+            pb.linear(cin, "class_embedding.linear_1", c1, flags=SILU)
+            pb.linear(c1, "class_embedding.linear_2", dst, R=res)
+        return None
+
+    def added_conditions(self):
+        """text_time (unet_2d_condition.py:991-1010): emb += MLP([text_embeds | sinusoid(time_ids)]); _finish_add_embedding inserts the
+        sinusoid's launch once the first call shows the widths of text_embeds / time_ids"""
+        plan, pb, cfg, B = self.plan, self.pb, self.cfg, self.B
+        plan.add_in = plan.time_ids = None
+        if cfg["addition_embed_type"] != "text_time":
+            return
+        plan._pdim, plan._atd = cfg["projection_class_embeddings_input_dim"], cfg["addition_time_embed_dim"]
+        plan.add_in = pb.persist((B, plan._pdim), _lib.elem_dtype())
+        plan.text_dim = None
+        a1 = self.rows(B, self.ted)
+        plan._add_emit_index = len(pb.prog)
+        pb.linear(_V.of(plan.add_in), "add_embedding.linear_1", a1, flags=SILU)
+        pb.linear(a1, "add_embedding.linear_2", self.emb, R=self.emb)
+
+    def block_embeddings(self):
+        """SiLU(emb) -> every resnet's time_emb_proj in one GEMM"""
+        pb, B, m, emb_t = self.pb, self.B, self.m, self.emb_t
+        semb = self.rows(B, emb_t.C)
+        pb.emit(self.lib.mi355x_sd_silu, (emb_t.p, semb.p, B * emb_t.C, 0, 0, self.stream), "misc")
+        self.temb_all = pb.persist((B, m._temb_total), torch.float32)
+        pb.linear(semb, "temb_all", _V(self.temb_all.data_ptr(), B, m._temb_total), flags=OUT_F32)
+        self.plan.emb_tensors["temb_all"] = self.temb_all
+
+    def context_kv(self):
+        """every block's cross-attention K/V projection of encoder_hidden_states in one GEMM (attention_processor.py:711-712).
+        IP-Adapter (unet_2d_condition.py:1054-1061): image_embeds -> ImageProjection (Linear, view [B*T, Dx], LayerNorm) -> the image
+        tokens' K/V for every cross-attention in one GEMM. The reference appends the tokens to encoder_hidden_states and each
+        IPAdapterAttnProcessor splits them off again; here they never join the text rows."""
+        plan, pb, cfg, B, m = self.plan, self.pb, self.cfg, self.B, self.m
+        self.kv_all = self.rows(B * self.L, m._kv_total)
+        pb.linear(_V.of(plan.enc), "kv_all", self.kv_all, bias=False)
+        plan.image_embeds = self.kvip_all = None
+        if not m._ip:
+            return
+        dx, T = cfg["cross_attention_dim"][0], cfg["ip_adapter_num_tokens"]
+        plan.image_embeds = pb.persist((B, cfg["encoder_hid_dim"]), _lib.elem_dtype())
+        raw = self.rows(B, T * dx)
+        pb.linear(_V.of(plan.image_embeds), "encoder_hid_proj.image_embeds", raw)
+        tok = self.rows(B * T, dx)
+        pb.lnorm(_V(raw.p, B * T, dx), "encoder_hid_proj.norm", tok)
+        self.kvip_all = self.rows(B * T, m._kv_total)
+        pb.linear(tok, "kvip_all", self.kvip_all, bias=False)
+
+    def skip_layout(self):
+        """the pre-walk: every skip connection is produced inside the buffer its up-block consumer reads (concat by construction); a
+        layer list without an up path (ControlNetModel) gets buffers of the skips' own"""
+        B, RES, S = self.B, self.RES, self.m._layers
+        self.skips: List[Tuple[int, int, int]] = []  # (C, h, w) in production order
+        h, w_, c_cur = self.H, self.W, self.cfg["block_out_channels"][0]
+        for d in S:
+            if d[0] == "resnet":
+                c_cur = d[3]
+            elif d[0] == "down":
+                h, w_ = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+            elif d[0] == "skip":
+                self.skips.append((c_cur, h, w_))
+            elif d[0] == "cat":
+                break
+        self.ups = [d for d in S if d[0] == "resnet" and d[1].startswith("up_blocks.")]
+        assert not self.ups or len(self.ups) == len(self.skips)
+        self.own_skips = None if self.ups else [self.rows(B * hs * ws_, cs) for cs, hs, ws_ in self.skips]
+        self.cats: List[_V] = []
+        self.cat_xc: List[int] = []
+        self.cat_hw: List[Tuple[int, int]] = []
+        for u, d in enumerate(self.ups):  # up resnet u consumes skip n-1-u
+            cs, hs, ws_ = self.skips[len(self.skips) - 1 - u]
+            t = self.pb.persist((B * hs * ws_, d[2]), torch.float32 if RES == 4 else _lib.elem_dtype())
+            self.cats.append(_V(t.data_ptr(), B * hs * ws_, d[2], es=RES))
+            self.cat_xc.append(d[2] - cs)
+            self.cat_hw.append((hs, ws_))
+
+    def skip_slot(self, k: int) -> _V:  # where skip k is produced
+        if self.own_skips is not None:
+            return self.own_skips[k]
+        u = len(self.skips) - 1 - k
+        return self.cats[u].cols(self.cat_xc[u], self.cats[u].C - self.cat_xc[u])
+
+    def x_slot(self, u: int) -> _V:
+        return self.cats[u].cols(0, self.cat_xc[u])
+
+    def tmp(self, rows, c) -> _V:
+        self.tmp_i ^= 1
+        return _V(self.pb.sc(f"x{self.tmp_i}", self.RES * rows * c), rows, c, es=self.RES)
+
+    def resnet(self, name, x: _V, h, w_, cout, scale, out: _V):
+        pb, m, RES, sc, eps = self.pb, self.m, self.RES, self.pb.sc, float(self.cfg["norm_eps"])
+        hw = h * w_
+        rows = self.B * hw
+        need_short = x.C != cout
+        x16 = _V(sc("x16", 2 * rows * x.C), rows, x.C) if (need_short and x.es == 4) else None
+        g1 = pb.gnorm(x, hw, name + ".norm1", eps, True, raw16=x16)
+        h1 = _V(sc("h1", RES * rows * cout), rows, cout, es=RES)   # fp32 mode: GroupNorm 2 reads the unrounded conv1 output
+        rb = self.temb_all.data_ptr() + 4 * m._temb_off[name]
+        pb.conv3(g1, h, w_, name + ".conv1", h1, rowbias=rb, ld_rb=m._temb_total)
+        g2 = pb.gnorm(h1, hw, name + ".norm2", eps, True)
+        if need_short:
+            short = _V(sc("short", RES * rows * cout), rows, cout, es=RES)
+            pb.linear(x16 if x16 is not None else x, name + ".conv_shortcut", short)
+        else:
+            short = x
+        pb.conv3(g2, h, w_, name + ".conv2", out, R=short, out_scale=1.0 / scale)
+
+    def transformer(self, name, x: _V, h, w_, heads, layers, out: _V):
+        pb, m, RES, sc, linear, ln_linear = self.pb, self.m, self.RES, self.pb.sc, self.pb.linear, self.ln_linear
+        hw = h * w_
+        rows = self.B * hw
+        c = x.C
+        g = pb.gnorm(x, hw, name + ".norm", 1e-6, False)
+        hid = _V(sc("t_h", RES * rows * c), rows, c, es=RES)
+        hid16 = _V(sc("t_h16", 2 * rows * c), rows, c) if RES == 4 else hid   # proj_out's operand: the last FF2 writes it
+        linear(g, name + ".proj_in", hid)
+        ln = None if m.fold_ln else _V(sc("t_ln", 2 * rows * c), rows, c)
+        qkv = _V(sc("t_qkv", 2 * rows * 3 * c), rows, 3 * c)
+        ao = _V(sc("t_ao", 2 * rows * c), rows, c)
+        ff = _V(sc("t_ff", 2 * rows * 4 * c), rows, 4 * c)
+        for l in range(layers):
+            b = f"{name}.transformer_blocks.{l}"
+            q2 = _V(qkv.p, rows, c)
+            ln_linear(hid, b + ".norm1", ln, b + ".attn1.qkv", qkv, bias=False)
+            if self.self_bias is not None and hw != self.self_mask_len:
+                # the reference pads a mask of the wrong length by target_length zeros (Attention.prepare_attention_mask,
+                # attention_processor.py:616-622) and the add onto the [.., hw, hw] scores then fails on the shapes
+                raise ValueError(f"attention_mask has {self.self_mask_len} key tokens but {b}.attn1 attends over {hw} latent tokens "
+                                 "(the mask must match the token count of every attention level)")
+            self.attention(qkv.cols(0, c), qkv.cols(c, c), qkv.cols(2 * c, c), ao, heads, hw, hw, bias=self.self_bias,
+                           log2=b in m._log2_blocks)
+            linear(ao, b + ".attn1.out", hid, R=hid)
+            ln_linear(hid, b + ".norm2", ln, b + ".attn2.q", q2, bias=False)
+            ko = m._kv_off[b]
+            self.attention(q2, self.kv_all.cols(ko, c), self.kv_all.cols(ko + c, c), ao, heads, hw, self.L, bias=self.enc_bias)
+            if self.kvip_all is not None and m.ip_adapter_scale != 0.0:
+                self.attention(q2, self.kvip_all.cols(ko, c), self.kvip_all.cols(ko + c, c), ao, heads, hw,
+                               self.cfg["ip_adapter_num_tokens"], accum=m.ip_adapter_scale)
+            linear(ao, b + ".attn2.out", hid, R=hid)
+            ln_linear(hid, b + ".norm3", ln, b + ".ff1", ff, flags=GEGLU)
+            linear(ff, b + ".ff2", hid16 if l == layers - 1 else hid, R=hid)
+        linear(hid16, name + ".proj_out", out, R=x)
+
+    def downsample(self, name, x: _V, h, w_, out: _V):
+        self.pb.conv3(self.cast16(x, "xc16"), h, w_, name, out, stride=2)
+
+    def upsample(self, name, x: _V, h, w_, ht, wt, out: _V):
+        """to (ht, wt), the size of the skip the next resnet concatenates with"""
+        pb, B = self.pb, self.B
+        src = self.cast16(x, "xc16")
+        if (ht, wt) == (2 * h, 2 * w_):
+            return pb.conv3(src, h, w_, name, out, up=1)     # nearest x2 folded into the conv's gather
+        # `forward_upsample_size` (unet_2d_condition.py:900-906, :1165-1169; Upsample2D interpolates to the skip's size):
+        # latents that are not multiples of 2^(levels - 1) leave a skip of odd size 2h - 1, and nearest interpolation
+        # from h to 2h - 1 reads source row y >> 1 like the x2 form, cropped. The crop moves the zero padding of the
+        # conv, so the upsampled tensor is materialised here (strided row copies: one per source row and parity --
+        # many small launches, on this rare path only) and a plain 3x3 conv follows.
+        assert ht in (2 * h - 1, 2 * h) and wt in (2 * w_ - 1, 2 * w_), (h, w_, ht, wt)
+        C_ = src.C
+        upb = _V(pb.sc("upx", 2 * B * ht * wt * C_), B * ht * wt, C_)
+        for b in range(B):
+            for i_ in range(h):
+                for y in (2 * i_, 2 * i_ + 1)[:ht - 2 * i_]:   # (a skip of odd height 2h - 1 has no row 2h - 1)
+                    for dx in (0, 1):
+                        pb.emit(self.lib.mi355x_sd_copy_rows, (src.p + 2 * ((b * h + i_) * w_) * src.ld, src.ld,
+                                                               upb.p + 2 * ((b * ht + y) * wt + dx) * C_, 2 * C_, (wt - dx + 1) // 2, C_,
+                                                               self.stream), "misc")
+        pb.conv3(upb, ht, wt, name, out)
+
+    def controlnet_residuals(self, mid: _V, h, w_):
+        """ControlNet residuals (unet_2d_condition.py:1121-1132, 1151-1155): every skip tensor and the mid output get their residual
+        once the down path and the mid block have consumed the originals"""
+        if not self.controlnet:
+            return
+        plan, pb, B = self.plan, self.pb, self.B
+
+        def add(dst: _V, c, hs, ws_) -> Tensor:
+            r = pb.persist((B, c, hs, ws_), torch.float32)
+            if dst.es == 2:
+                pb.emit(self.lib.mi355x_sd_add_nchw, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, self.stream), "misc")
+            else:
+                pb.emit(self.lib.mi355x_sd_add_nchw_ex, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, 1, self.stream), "misc")
+            return r
+
+        plan.ctrl_down = [add(self.skip_slot(k), *s) for k, s in enumerate(self.skips)]
+        plan.ctrl_mid = add(mid, mid.C, h, w_)
+
+    def stem(self) -> _V:
+        """conv_in writes skip 0"""
+        plan, pb, cfg = self.plan, self.pb, self.cfg
+        cur = self.skip_slot(0)
+        args = (plan.sample.data_ptr(), plan.in_scale.data_ptr(), pb.wp("conv_in.w"), pb.wp("conv_in.b"), cur.p, self.B,
+                cfg["in_channels"], self.H, self.W, cfg["block_out_channels"][0], cur.ld)
+        if cur.es == 2:
+            pb.emit(self.lib.mi355x_sd_conv_in3x3, args + (self.stream,), "misc")
+        else:
+            pb.emit(self.lib.mi355x_sd_conv_in3x3_ex, args + (1, self.stream), "misc")
+        return cur
+
+    def walk(self):
+        """the loop over the layer list that picks each layer's destination; returns the last output and its size"""
+        S, B = self.m._layers, self.B
+        h, w_ = self.H, self.W
+        k, u = 1, 0          # next skip index to produce (S[0] is the conv_in skip), next up resnet index
+        cur = self.stem()
+        for i in range(1, len(S)):
+            d = S[i]
+            nxt = S[i + 1][0] if i + 1 < len(S) else "end"
+            if d[0] in ("resnet", "attn"):
+                cout = d[3] if d[0] == "resnet" else d[2]
+                if nxt == "skip":
+                    dst = self.skip_slot(k)
+                elif nxt == "cat":
+                    dst = self.x_slot(u)
+                else:  # followed by a transformer / the mid resnet / an upsampler / the head
+                    dst = self.tmp(B * h * w_, cout)
+                if d[0] == "resnet":
+                    self.resnet(d[1], cur, h, w_, cout, d[4], dst)
+                else:
+                    self.transformer(d[1], cur, h, w_, d[3], d[4], dst)
+                cur = dst
+            elif d[0] == "skip":
+                k += 1
+            elif d[0] == "down":
+                dst = self.skip_slot(k)
+                self.downsample(d[1], cur, h, w_, dst)
+                h, w_ = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+                cur = dst
+            elif d[0] == "cat":
+                if u == 0:
+                    self.controlnet_residuals(cur, h, w_)
+                cur = self.cats[u]
+                u += 1
+            elif d[0] == "up":
+                dst = self.x_slot(u)
+                self.upsample(d[1], cur, h, w_, *self.cat_hw[u], dst)
+                h, w_ = self.cat_hw[u]
+                cur = dst
+        assert k == len(self.skips) and u == len(self.ups) and (not self.ups or (h, w_) == (self.H, self.W))
+        return cur, h, w_
+
+    def head(self, x: _V, h, w_):
+        """conv_norm_out + conv_out (unet_2d_condition.py:1193-1196)"""
+        pb, cfg = self.pb, self.cfg
+        g = pb.gnorm(x, h * w_, "conv_norm_out", float(cfg["norm_eps"]), True)
+        pb.emit(self.lib.mi355x_sd_conv_out3x3, (g.p, g.ld, pb.wp("conv_out.w"), pb.wp("conv_out.b"), self.plan.out.data_ptr(), self.B,
+                                                 g.C, h, w_, cfg["out_channels"], self.stream), "misc")
+
+
 class UNet2DConditionOutput(SimpleNamespace):
     """``.sample`` holder, mirroring unet_2d_condition.py:61-72."""
 
@@ -333,547 +906,18 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
             # `unet.add_embedding.linear_1.in_features`: the one sub-layer attribute a pipeline reads off the UNet
             pdim = self.cfg["projection_class_embeddings_input_dim"]
             self.add_embedding = SimpleNamespace(linear_1=SimpleNamespace(in_features=pdim, out_features=self.cfg["block_out_channels"][0] * 4))
-        self._load_weights(params)
+        ct = self.cfg["class_embed_type"]
+        self._class_kind = "embedding" if (ct is None and self.cfg["num_class_embeds"] is not None) else ct
+        self._ip = self.cfg["encoder_hid_dim_type"] == "ip_image_proj"
+        self.ip_adapter_scale = 1.0
+        self._layers = _structure(self.cfg, self._encoder_only)
+        self._Weights(self, params).load()
 
-    _encoder_only = False   # ControlNetModel: stop after the mid block
+    _encoder_only = False   # ControlNetModel: the layer list stops after the mid block
+    _Weights, _Planner = _UNetWeights, _UNetPlanner   # ControlNetModel overrides stages of both
 
     def _shapes(self) -> Dict[str, tuple]:
         return unet_param_shapes(self.cfg)
-
-    # ------------------------------------------------------------------ weights
-    def _load_weights(self, params: Mapping[str, Tensor]) -> None:
-        cfg, dev = self.cfg, self.device
-        shapes = self._shapes()
-        missing = [k for k in shapes if k not in params]
-        if missing:
-            raise KeyError(f"missing parameters: {missing[:5]}{'...' if len(missing) > 5 else ''}")
-
-        def get(name):
-            t = params[name]
-            if tuple(t.shape) != shapes[name]:
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != expected {shapes[name]} (Paddle layout)")
-            return t.to(device=dev, dtype=torch.float32)
-
-        bf = lambda t: t.to(_lib.elem_dtype()).contiguous()  # noqa: E731
-        W = self.w
-
-        def lin_w(name):  # Paddle [in,out] -> [out,in]
-            return get(name + ".weight").t()
-
-        def put_lin(key, name, bias=True):
-            W[key + ".w"] = bf(lin_w(name))
-            if bias:
-                W[key + ".b"] = get(name + ".bias").contiguous()
-
-        self._kb64 = set()
-        self._log2_blocks = set()   # transformer blocks whose self-attention scores are base-2 exponents (fold_softmax_scale)
-
-        def put_conv(key, name):  # OIHW -> [O][kh][kw][I]; 3x3 with Cin % 64 == 0 -> [O][I/64][kh][kw][64] (MI355X_SD_CONV_KB64)
-            w = get(name + ".weight")
-            O, I, kh, kw = w.shape
-            if kh == 3 and I % 64 == 0:
-                W[key + ".w"] = bf(w.reshape(O, I // 64, 64, kh, kw).permute(0, 1, 3, 4, 2).reshape(O, -1))
-                self._kb64.add(key)
-            else:
-                W[key + ".w"] = bf(w.permute(0, 2, 3, 1).reshape(O, -1))
-            W[key + ".b"] = get(name + ".bias").contiguous()
-
-        def put_norm(key, name):
-            W[key + ".g"] = get(name + ".weight").contiguous()
-            W[key + ".b"] = get(name + ".bias").contiguous()
-
-        def put_ln_lin(key, w, bias, norm):
-            """LayerNorm `norm` folded into the projection w [N, K] (mi355x_sd_linear_ln): W' = W diag(gamma) in bf16,
-            ws = row sums of the bf16 W' (what the MFMAs actually sum), b' = bias + W beta."""
-            wp_ = bf(w * get(norm + ".weight")[None, :])
-            W[key + ".w"] = wp_
-            W[key + ".ws"] = wp_.float().sum(1).contiguous()
-            bb = w @ get(norm + ".bias")
-            W[key + ".b"] = (bb if bias is None else bias + bb).contiguous()
-
-        w = get("conv_in.weight")  # -> [ky][kx][ci][O]
-        W["conv_in.w"] = bf(w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]))
-        W["conv_in.b"] = get("conv_in.bias").contiguous()
-        put_lin("time_embedding.linear_1", "time_embedding.linear_1")
-        put_lin("time_embedding.linear_2", "time_embedding.linear_2")
-        if cfg["addition_embed_type"] == "text_time":
-            put_lin("add_embedding.linear_1", "add_embedding.linear_1")
-            put_lin("add_embedding.linear_2", "add_embedding.linear_2")
-        if cfg["time_cond_proj_dim"] is not None:
-            put_lin("time_embedding.cond_proj", "time_embedding.cond_proj", bias=False)
-        ct = cfg["class_embed_type"]
-        self._class_kind = ("embedding" if (ct is None and cfg["num_class_embeds"] is not None) else ct)
-        if self._class_kind == "embedding":
-            W["class_embedding.table"] = bf(get("class_embedding.weight"))
-        elif ct in ("timestep", "projection"):
-            put_lin("class_embedding.linear_1", "class_embedding.linear_1")
-            put_lin("class_embedding.linear_2", "class_embedding.linear_2")
-        elif ct == "simple_projection":
-            put_lin("class_embedding", "class_embedding")
-        temb_w, temb_b = [], []
-        self._temb_off: Dict[str, int] = {}
-        off = 0
-        self._ip = cfg["encoder_hid_dim_type"] == "ip_image_proj"
-        self.ip_adapter_scale = 1.0
-        if self._ip:
-            put_lin("encoder_hid_proj.image_embeds", "encoder_hid_proj.image_embeds")
-            put_norm("encoder_hid_proj.norm", "encoder_hid_proj.norm")
-        kvip_w: List[Tensor] = []          # ... and every IPAdapterAttnProcessor's to_k_ip / to_v_ip, same column offsets
-        kv_w: List[Tensor] = []            # every cross-attention to_k / to_v, batched into one GEMM per step
-        self._kv_off: Dict[str, int] = {}
-        kv_off = 0
-        for d in _structure(cfg, self._encoder_only):
-            if d[0] == "resnet":
-                _, name, cin, cout, _ = d
-                put_norm(name + ".norm1", name + ".norm1")
-                put_conv(name + ".conv1", name + ".conv1")
-                temb_w.append(lin_w(name + ".time_emb_proj"))
-                temb_b.append(get(name + ".time_emb_proj.bias"))
-                self._temb_off[name] = off
-                off += cout
-                put_norm(name + ".norm2", name + ".norm2")
-                put_conv(name + ".conv2", name + ".conv2")
-                if cin != cout:
-                    put_conv(name + ".conv_shortcut", name + ".conv_shortcut")
-            elif d[0] == "attn":
-                _, name, c, heads, layers, cross = d
-                put_norm(name + ".norm", name + ".norm")
-                if cfg["use_linear_projection"]:
-                    put_lin(name + ".proj_in", name + ".proj_in")
-                    put_lin(name + ".proj_out", name + ".proj_out")
-                else:
-                    put_conv(name + ".proj_in", name + ".proj_in")
-                    put_conv(name + ".proj_out", name + ".proj_out")
-                for l in range(layers):
-                    b = f"{name}.transformer_blocks.{l}"
-                    wq = lin_w(b + ".attn1.to_q")
-                    if self.fold_scale and c // heads == 64:
-                        wq = wq * ((c // heads) ** -0.5 * 1.4426950408889634)
-                        self._log2_blocks.add(b)
-                    wqkv = torch.cat([wq, lin_w(b + ".attn1.to_k"), lin_w(b + ".attn1.to_v")], 0)
-                    if self.fold_ln:
-                        put_ln_lin(b + ".attn1.qkv", wqkv, None, b + ".norm1")
-                        put_ln_lin(b + ".attn2.q", lin_w(b + ".attn2.to_q"), None, b + ".norm2")
-                    else:
-                        for nm in (".norm1", ".norm2", ".norm3"):
-                            put_norm(b + nm, b + nm)
-                        W[b + ".attn1.qkv.w"] = bf(wqkv)
-                        W[b + ".attn2.q.w"] = bf(lin_w(b + ".attn2.to_q"))
-                    put_lin(b + ".attn1.out", b + ".attn1.to_out.0")
-                    if any(x != cfg["cross_attention_dim"][0] for x in cfg["cross_attention_dim"]):
-                        raise NotImplementedError("per-block cross_attention_dim")
-                    kv_w.append(bf(torch.cat([lin_w(b + ".attn2.to_k"), lin_w(b + ".attn2.to_v")], 0)))
-                    if self._ip:
-                        kvip_w.append(bf(torch.cat([lin_w(b + ".attn2.processor.to_k_ip"),
-                                                    lin_w(b + ".attn2.processor.to_v_ip")], 0)))
-                    self._kv_off[b] = kv_off
-                    kv_off += 2 * c
-                    put_lin(b + ".attn2.out", b + ".attn2.to_out.0")
-                    # GEGLU: interleave [16 value rows | 16 gate rows] so a lane holds both halves of a pair
-                    w1 = lin_w(b + ".ff.net.0.proj")  # [8c, c]
-                    b1 = get(b + ".ff.net.0.proj.bias")
-                    half = w1.shape[0] // 2
-                    if self.fold_ln:   # norm3 folded in before the row interleave (a row permutation commutes with it)
-                        b1 = b1 + w1 @ get(b + ".norm3.bias")
-                        w1 = w1 * get(b + ".norm3.weight")[None, :]
-                    W[b + ".ff1.w"] = bf(torch.stack([w1[:half].reshape(half // 16, 16, -1),
-                                                      w1[half:].reshape(half // 16, 16, -1)], 1).reshape(2 * half, -1))
-                    W[b + ".ff1.b"] = torch.stack([b1[:half].reshape(half // 16, 16), b1[half:].reshape(half // 16, 16)],
-                                                  1).reshape(-1).contiguous()
-                    if self.fold_ln:
-                        W[b + ".ff1.ws"] = W[b + ".ff1.w"].float().sum(1).contiguous()
-                    put_lin(b + ".ff2", b + ".ff.net.2")
-            elif d[0] in ("down", "up"):
-                put_conv(d[1], d[1])
-        W["kv_all.w"] = torch.cat(kv_w, 0).contiguous()
-        if self._ip:
-            W["kvip_all.w"] = torch.cat(kvip_w, 0).contiguous()
-        del kv_w, kvip_w
-        self._kv_total = kv_off
-        W["temb_all.w"] = bf(torch.cat(temb_w, 0))
-        W["temb_all.b"] = torch.cat(temb_b, 0).contiguous()
-        self._temb_total = off
-        if self._encoder_only:
-            self._load_extra(get, bf, put_conv)
-            return
-        put_norm("conv_norm_out", "conv_norm_out")
-        w = get("conv_out.weight")
-        W["conv_out.w"] = bf(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
-        W["conv_out.b"] = get("conv_out.bias").contiguous()
-
-    # ------------------------------------------------------------------ plan
-    def _build_plan(self, B: int, H: int, Wd: int, L: int, masked: bool = False, controlnet: bool = False,
-                    self_mask_len: int = 0) -> _Plan:
-        cfg, lib = self.cfg, self._lib
-        stream = self._stream_ptr
-        boc = cfg["block_out_channels"]
-        eps = float(cfg["norm_eps"])
-        ted = boc[0] * 4
-        pb = PlanBuilder(self, B)
-        plan, sc, persist, emit, wp = pb.plan, pb.sc, pb.persist, pb.emit, pb.wp
-        linear, conv3, gnorm, lnorm = pb.linear, pb.conv3, pb.gnorm, pb.lnorm
-
-        def cast16(x: _V, name: str) -> _V:
-            """16-bit copy of fp32 rows (operand of the down / upsampling convs in the fp32-residual mode)"""
-            if x.es == 2:
-                return x
-            y = _V(sc(name, 2 * x.rows * x.C), x.rows, x.C)
-            emit(lib.mi355x_sd_cast_rows, (x.p, x.ld, y.p, y.ld, x.rows, x.C, stream), "misc")
-            return y
-
-        def ln_linear(x: _V, wkey: str, out: _V, flags=0):
-            """LayerNorm(eps 1e-5, attention.py:318-331) folded into the projection: statistics pass + raw-row GEMM"""
-            N, K = self.w[wkey + ".w"].shape
-            assert K == x.C, (wkey, K, x.C)
-            st = sc("t_stats", 8 * x.rows)
-            emit(lib.mi355x_sd_row_stats, (x.p, x.rows, x.C, x.ld, 1e-5, st, stream), "ln")
-            emit(lib.mi355x_sd_linear_ln, (x.p, x.ld, st, wp(wkey + ".w"), wp(wkey + ".ws"), out.p, out.ld, x.rows, N, K,
-                                           wp(wkey + ".b"), flags, *self._gemm_ws, stream), "gemm", 2.0 * x.rows * N * K,
-                 f"{x.rows}x{N}x{K}" + ("g" if flags & GEGLU else ""))
-
-        def attention(q: _V, k: _V, v: _V, out: _V, heads, sq, skv, bias=None, accum: Optional[float] = None, log2=False):
-            if log2 and bias is not None:
-                # q already carries head_dim^-0.5 * log2(e) (folded into to_q at load) but the masked kernel exponentiates
-                # exp2((q.k + bias / scale) * scale * log2(e)): scale = ln 2 makes that exp2(q.k + bias * log2(e)) -- the same softmax
-                assert accum is None
-                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv, 0, 0), math.log(2.0), suffix="m")
-            elif log2:
-                assert accum is None and q.C // heads == 64
-                pb.sdpa(q, k, v, out, heads, sq, skv, scale=1.0, fn=lib.mi355x_sd_sdpa_ex, tail=(_lib.SDPA_LOG2,))
-            elif accum is None:
-                # bias: additive encoder mask [B, skv] broadcast over heads and queries (unet_2d_condition.py:921-927)
-                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0))
-            else:   # out += accum * attention (the image-token half of IPAdapterAttnProcessor)
-                pb.sdpa(q, k, v, out, heads, sq, skv, bias, (skv if bias else 0, 0, 0), fn=lib.mi355x_sd_sdpa_accum,
-                        tail=(float(accum),), suffix="+")
-
-        # ---- inputs (static buffers; staged by __call__) ----
-        plan.sample = persist((B, cfg["in_channels"], H, Wd), torch.float32)
-        plan.t = persist((1,), torch.float32)
-        plan.in_scale = persist((1,), torch.float32)
-        plan.in_scale.fill_(1.0)
-        dx = cfg["cross_attention_dim"][0]
-        plan.enc = persist((B * L, dx), _lib.elem_dtype())
-        enc = _V(plan.enc.data_ptr(), B * L, dx)
-        plan.out = persist((B, cfg["out_channels"], H, Wd), torch.float32)
-        plan.enc_bias = persist((B, L), torch.float32) if masked else None
-        enc_bias = plan.enc_bias.data_ptr() if masked else None
-        # `attention_mask`: a key mask over the LATENT tokens, added to every self-attention (unet_2d_condition.py:916-923 ->
-        # BasicTransformerBlock.attn1, attention.py:417-423)
-        plan.self_bias = persist((B, self_mask_len), torch.float32) if self_mask_len else None
-        self_bias = plan.self_bias.data_ptr() if self_mask_len else None
-
-        # ---- time / added-condition embedding (unet_2d_condition.py:933-1030) ----
-        t0 = persist((B, boc[0]), _lib.elem_dtype())
-        emit(lib.mi355x_sd_timestep_embedding, (plan.t.data_ptr(), 1, B, boc[0], 1, 1 if cfg["flip_sin_to_cos"] else 0,
-                                                float(cfg["freq_shift"]), 1.0, 10000.0, t0.data_ptr(), boc[0], stream),
-             "misc")
-        # class embedding (unet_2d_condition.py:953-975): emb + class_emb, or [emb | class_emb] when class_embeddings_concat.
-        # The add is the residual input of a GEMM epilogue, the concat is a GEMM / gather writing the upper columns.
-        ck = self._class_kind
-        concat = bool(cfg["class_embeddings_concat"])
-        ted_b = ted * (2 if concat else 1)
-        e1 = persist((B, ted), _lib.elem_dtype())
-        emb_t = persist((B, ted_b), _lib.elem_dtype())
-        emb = _V(emb_t.data_ptr(), B, ted, ted_b)          # the time-embedding half (all of it without concat)
-        cls_out = emb.cols(ted, ted) if concat else None     # where the class embedding goes when concatenated
-        plan.class_in = None
-        pre_cls = None   # class embedding available BEFORE the time MLP (gather / identity): added as its residual
-        if ck == "embedding":
-            plan.class_in = persist((B,), torch.int32)
-            dst = cls_out if concat else _V(persist((B, ted), _lib.elem_dtype()).data_ptr(), B, ted)
-            emit(lib.mi355x_sd_embed_tokens, (plan.class_in.data_ptr(), B, 1, wp("class_embedding.table"), None, ted, dst.p,
-                                              dst.ld, stream), "misc")
-            pre_cls = None if concat else dst
-        elif ck == "identity":
-            plan.class_in = persist((B, ted), _lib.elem_dtype())
-            src = _V(plan.class_in.data_ptr(), B, ted)
-            if concat:
-                emit(lib.mi355x_sd_copy_rows, (src.p, src.ld, cls_out.p, cls_out.ld, B, ted, stream), "misc")
-            else:
-                pre_cls = src
-        plan.tcond = None
-        if cfg["time_cond_proj_dim"] is not None:   # t_emb += cond_proj(timestep_cond) (embeddings.py:284-285; zeros when not given)
-            plan.tcond = persist((B, cfg["time_cond_proj_dim"]), _lib.elem_dtype())
-            plan.tcond.zero_()
-            tv = _V(t0.data_ptr(), B, boc[0])
-            linear(_V(plan.tcond.data_ptr(), B, cfg["time_cond_proj_dim"]), "time_embedding.cond_proj", tv, bias=False, R=tv)
-        linear(_V(t0.data_ptr(), B, boc[0]), "time_embedding.linear_1", _V(e1.data_ptr(), B, ted), flags=SILU)
-        linear(_V(e1.data_ptr(), B, ted), "time_embedding.linear_2", emb, R=pre_cls)
-        if ck in ("timestep", "projection", "simple_projection"):
-            if ck == "timestep":   # class_labels -> sinusoid (time_proj) -> TimestepEmbedding
-                plan.class_in = persist((B,), torch.float32)
-                cin = _V(persist((B, boc[0]), _lib.elem_dtype()).data_ptr(), B, boc[0])
-                emit(lib.mi355x_sd_timestep_embedding, (plan.class_in.data_ptr(), B, B, boc[0], 1,
-                                                        1 if cfg["flip_sin_to_cos"] else 0, float(cfg["freq_shift"]), 1.0,
-                                                        10000.0, cin.p, cin.ld, stream), "misc")
-            else:
-                pdim = cfg["projection_class_embeddings_input_dim"]
-                plan.class_in = persist((B, pdim), _lib.elem_dtype())
-                cin = _V(plan.class_in.data_ptr(), B, pdim)
-            dst, res = (cls_out, None) if concat else (emb, emb)
-            if ck == "simple_projection":
-                linear(cin, "class_embedding", dst, R=res)
-            else:
-                c1 = _V(persist((B, ted), _lib.elem_dtype()).data_ptr(), B, ted)
-                linear(cin, "class_embedding.linear_1", c1, flags=SILU)
-                linear(c1, "class_embedding.linear_2", dst, R=res)
-        plan.add_in = plan.time_ids = None
-        if cfg["addition_embed_type"] == "text_time":
-            pdim = cfg["projection_class_embeddings_input_dim"]
-            atd = cfg["addition_time_embed_dim"]
-            plan.add_in = persist((B, pdim), _lib.elem_dtype())
-            plan.text_dim = None  # widths of text_embeds / time_ids are only known at the first call
-            plan._pdim, plan._atd = pdim, atd
-            a1 = persist((B, ted), _lib.elem_dtype())
-            plan._add_emit_index = len(pb.prog)  # the time_ids embedding op is inserted here once widths are known
-            linear(_V(plan.add_in.data_ptr(), B, pdim), "add_embedding.linear_1", _V(a1.data_ptr(), B, ted),
-                   flags=SILU)
-            linear(_V(a1.data_ptr(), B, ted), "add_embedding.linear_2", emb, R=emb)
-        semb = persist((B, ted_b), _lib.elem_dtype())
-        emit(lib.mi355x_sd_silu, (emb_t.data_ptr(), semb.data_ptr(), B * ted_b, 0, 0, stream), "misc")
-        temb_all = persist((B, self._temb_total), torch.float32)
-        linear(_V(semb.data_ptr(), B, ted_b), "temb_all", _V(temb_all.data_ptr(), B, self._temb_total), flags=OUT_F32)
-        # every block's cross-attention K/V projection of encoder_hidden_states in one GEMM (attention_processor.py:711-712)
-        kv_all_t = persist((B * L, self._kv_total), _lib.elem_dtype())
-        kv_all = _V(kv_all_t.data_ptr(), B * L, self._kv_total)
-        linear(enc, "kv_all", kv_all, bias=False)
-        # IP-Adapter (unet_2d_condition.py:1054-1061): image_embeds -> ImageProjection (Linear, view [B*T, Dx], LayerNorm) -> the
-        # image tokens' K/V for every cross-attention in one GEMM. The reference appends the tokens to encoder_hidden_states
-        # and each IPAdapterAttnProcessor splits them off again; here they never join the text rows.
-        plan.image_embeds = None
-        kvip_all, T = None, cfg["ip_adapter_num_tokens"]
-        if self._ip:
-            E = cfg["encoder_hid_dim"]
-            plan.image_embeds = persist((B, E), _lib.elem_dtype())
-            raw = _V(persist((B, T * dx), _lib.elem_dtype()).data_ptr(), B, T * dx)
-            linear(_V(plan.image_embeds.data_ptr(), B, E), "encoder_hid_proj.image_embeds", raw)
-            tok = _V(persist((B * T, dx), _lib.elem_dtype()).data_ptr(), B * T, dx)
-            lnorm(_V(raw.p, B * T, dx), "encoder_hid_proj.norm", tok)
-            kvip_all = _V(persist((B * T, self._kv_total), _lib.elem_dtype()).data_ptr(), B * T, self._kv_total)
-            linear(tok, "kvip_all", kvip_all, bias=False)
-
-        # ---- skip / concat buffers: pre-walk ----
-        S = _structure(cfg, self._encoder_only)
-        skips: List[Tuple[int, int, int]] = []  # (C, h, w) in production order
-        h, w_ = H, Wd
-        c_cur = boc[0]
-        for d in S:
-            if d[0] == "resnet":
-                c_cur = d[3]
-            elif d[0] == "down":
-                h, w_ = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
-            elif d[0] == "skip":
-                skips.append((c_cur, h, w_))
-            elif d[0] == "cat":
-                break
-        ups = [d for d in S if d[0] == "resnet" and d[1].startswith("up_blocks.")]
-        assert len(ups) == len(skips) or self._encoder_only
-        RES = 4 if self.resid_f32 else 2                       # bytes per element of the residual stream
-        res_dt = torch.float32 if self.resid_f32 else _lib.elem_dtype()
-        own_skips = [_V(persist((B * hs * ws_, cs), _lib.elem_dtype()).data_ptr(), B * hs * ws_, cs)
-                     for cs, hs, ws_ in skips] if self._encoder_only else None   # no up path to host them
-        cats: List[_V] = []
-        cat_xc: List[int] = []
-        cat_hw: List[Tuple[int, int]] = []
-        for u, d in enumerate(ups):  # up resnet u consumes skip n-1-u
-            cs, hs, ws_ = skips[len(skips) - 1 - u]
-            cx = d[2] - cs
-            t = persist((B * hs * ws_, cx + cs), res_dt)
-            cats.append(_V(t.data_ptr(), B * hs * ws_, cx + cs, es=RES))
-            cat_xc.append(cx)
-            cat_hw.append((hs, ws_))
-
-        def skip_slot(k: int) -> _V:  # where skip k is produced
-            if own_skips is not None:
-                return own_skips[k]
-            u = len(skips) - 1 - k
-            return cats[u].cols(cat_xc[u], cats[u].C - cat_xc[u])
-
-        def x_slot(u: int) -> _V:
-            return cats[u].cols(0, cat_xc[u])
-
-        def add_nchw(dst: _V, r: Tensor, c, hw):
-            if dst.es == 2:
-                return lib.mi355x_sd_add_nchw, (dst.p, dst.ld, r.data_ptr(), B, c, hw, stream)
-            return lib.mi355x_sd_add_nchw_ex, (dst.p, dst.ld, r.data_ptr(), B, c, hw, 1, stream)
-
-        # ---- layer emitters ----
-        def resnet(name, x: _V, h, w_, cout, scale, out: _V):
-            hw = h * w_
-            rows = B * hw
-            need_short = x.C != cout
-            x16 = _V(sc("x16", 2 * rows * x.C), rows, x.C) if (need_short and x.es == 4) else None
-            g1 = gnorm(x, hw, name + ".norm1", eps, True, raw16=x16)
-            h1 = _V(sc("h1", RES * rows * cout), rows, cout, es=RES)   # fp32 mode: GroupNorm 2 reads the unrounded conv1 output
-            rb = temb_all.data_ptr() + 4 * self._temb_off[name]
-            conv3(g1, h, w_, name + ".conv1", h1, rowbias=rb, ld_rb=self._temb_total)
-            g2 = gnorm(h1, hw, name + ".norm2", eps, True)
-            if need_short:
-                short = _V(sc("short", RES * rows * cout), rows, cout, es=RES)
-                linear(x16 if x16 is not None else x, name + ".conv_shortcut", short)
-            else:
-                short = x
-            conv3(g2, h, w_, name + ".conv2", out, R=short, out_scale=1.0 / scale)
-
-        def transformer(name, x: _V, h, w_, heads, layers, out: _V):
-            hw = h * w_
-            rows = B * hw
-            c = x.C
-            g = gnorm(x, hw, name + ".norm", 1e-6, False)
-            hid = _V(sc("t_h", RES * rows * c), rows, c, es=RES)
-            hid16 = _V(sc("t_h16", 2 * rows * c), rows, c) if RES == 4 else hid   # proj_out's operand: the last FF2 writes it
-            linear(g, name + ".proj_in", hid)
-            ln = None if self.fold_ln else _V(sc("t_ln", 2 * rows * c), rows, c)
-            qkv = _V(sc("t_qkv", 2 * rows * 3 * c), rows, 3 * c)
-            ao = _V(sc("t_ao", 2 * rows * c), rows, c)
-            ff = _V(sc("t_ff", 2 * rows * 4 * c), rows, 4 * c)
-            for l in range(layers):
-                b = f"{name}.transformer_blocks.{l}"
-                q2 = _V(qkv.p, rows, c)
-                if self.fold_ln:
-                    ln_linear(hid, b + ".attn1.qkv", qkv)
-                else:
-                    lnorm(hid, b + ".norm1", ln)
-                    linear(ln, b + ".attn1.qkv", qkv, bias=False)
-                if self_bias is not None and hw != self_mask_len:
-                    # the reference pads a mask of the wrong length by target_length zeros (Attention.prepare_attention_mask,
-                    # attention_processor.py:616-622) and the add onto the [.., hw, hw] scores then fails on the shapes
-                    raise ValueError(f"attention_mask has {self_mask_len} key tokens but {b}.attn1 attends over {hw} latent tokens "
-                                     "(the mask must match the token count of every attention level)")
-                attention(qkv.cols(0, c), qkv.cols(c, c), qkv.cols(2 * c, c), ao, heads, hw, hw, bias=self_bias,
-                          log2=b in self._log2_blocks)
-                linear(ao, b + ".attn1.out", hid, R=hid)
-                if self.fold_ln:
-                    ln_linear(hid, b + ".attn2.q", q2)
-                else:
-                    lnorm(hid, b + ".norm2", ln)
-                    linear(ln, b + ".attn2.q", q2, bias=False)
-                ko = self._kv_off[b]
-                attention(q2, kv_all.cols(ko, c), kv_all.cols(ko + c, c), ao, heads, hw, L, bias=enc_bias)
-                if kvip_all is not None and self.ip_adapter_scale != 0.0:
-                    attention(q2, kvip_all.cols(ko, c), kvip_all.cols(ko + c, c), ao, heads, hw, T,
-                              accum=self.ip_adapter_scale)
-                linear(ao, b + ".attn2.out", hid, R=hid)
-                if self.fold_ln:
-                    ln_linear(hid, b + ".ff1", ff, flags=GEGLU)
-                else:
-                    lnorm(hid, b + ".norm3", ln)
-                    linear(ln, b + ".ff1", ff, flags=GEGLU)
-                linear(ff, b + ".ff2", hid16 if l == layers - 1 else hid, R=hid)
-            linear(hid16, name + ".proj_out", out, R=x)
-
-        # ---- body ----
-        h, w_ = H, Wd
-        k = 0            # next skip index to produce
-        u = 0            # next up resnet index
-        cur = skip_slot(0)
-        if cur.es == 2:
-            emit(lib.mi355x_sd_conv_in3x3, (plan.sample.data_ptr(), plan.in_scale.data_ptr(), wp("conv_in.w"),
-                                            wp("conv_in.b"), cur.p, B, cfg["in_channels"], H, Wd, boc[0], cur.ld, stream),
-                 "misc")
-        else:
-            emit(lib.mi355x_sd_conv_in3x3_ex, (plan.sample.data_ptr(), plan.in_scale.data_ptr(), wp("conv_in.w"),
-                                               wp("conv_in.b"), cur.p, B, cfg["in_channels"], H, Wd, boc[0], cur.ld, 1,
-                                               stream), "misc")
-        if self._encoder_only:
-            self._emit_pre(pb, cur, H, Wd)
-        k = 1
-        tmp_i = 0
-
-        def tmp(rows, c) -> _V:
-            nonlocal tmp_i
-            tmp_i ^= 1
-            return _V(sc(f"x{tmp_i}", RES * rows * c), rows, c, es=RES)
-
-        i = 1  # S[0] is the conv_in skip
-        n_layers = len(S)
-        while i < n_layers:
-            d = S[i]
-            nxt = S[i + 1] if i + 1 < n_layers else ("end",)
-            rows = B * h * w_
-            if d[0] == "resnet" or d[0] == "attn":
-                cout = d[3] if d[0] == "resnet" else d[2]
-                # destination of this layer's output
-                if nxt[0] == "attn":
-                    dst = tmp(rows, cout)
-                elif nxt[0] == "skip":
-                    dst = skip_slot(k)
-                elif nxt[0] == "cat":
-                    dst = x_slot(u)
-                else:  # followed by mid resnet / upsampler / end
-                    dst = tmp(rows, cout)
-                if d[0] == "resnet":
-                    resnet(d[1], cur, h, w_, cout, d[4], dst)
-                else:
-                    transformer(d[1], cur, h, w_, d[3], d[4], dst)
-                cur = dst
-            elif d[0] == "skip":
-                k += 1
-            elif d[0] == "down":
-                ho, wo = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
-                dst = skip_slot(k)
-                conv3(cast16(cur, "xc16"), h, w_, d[1], dst, stride=2)
-                h, w_ = ho, wo
-                cur = dst
-            elif d[0] == "cat":
-                if u == 0 and controlnet:
-                    # ControlNet residuals (unet_2d_condition.py:1121-1132, 1151-1155): every skip tensor and the mid
-                    # output get their residual once the down path and the mid block have consumed the originals
-                    plan.ctrl_down = []
-                    for kk, (cs, hs, ws_) in enumerate(skips):
-                        rt = persist((B, cs, hs, ws_), torch.float32)
-                        plan.ctrl_down.append(rt)
-                        sl = skip_slot(kk)
-                        emit(*add_nchw(sl, rt, cs, hs * ws_), "misc")
-                    plan.ctrl_mid = persist((B, cur.C, h, w_), torch.float32)
-                    emit(*add_nchw(cur, plan.ctrl_mid, cur.C, h * w_), "misc")
-                cur = cats[u]
-                u += 1
-            elif d[0] == "up":
-                dst = x_slot(u)
-                ht, wt = cat_hw[u]                 # the size of the skip the next resnet concatenates with
-                src = cast16(cur, "xc16")
-                if (ht, wt) == (2 * h, 2 * w_):
-                    conv3(src, h, w_, d[1], dst, up=1)     # nearest x2 folded into the conv's gather
-                else:
-                    # `forward_upsample_size` (unet_2d_condition.py:900-906, :1165-1169; Upsample2D interpolates to the skip's size):
-                    # latents that are not multiples of 2^(levels - 1) leave a skip of odd size 2h - 1, and nearest interpolation
-                    # from h to 2h - 1 reads source row y >> 1 like the x2 form, cropped. The crop moves the zero padding of the
-                    # conv, so the upsampled tensor is materialised here (strided row copies: one per source row and parity --
-                    # many small launches, on this rare path only) and a plain 3x3 conv follows.
-                    assert ht in (2 * h - 1, 2 * h) and wt in (2 * w_ - 1, 2 * w_), (h, w_, ht, wt)
-                    C_ = src.C
-                    upb = _V(sc("upx", 2 * B * ht * wt * C_), B * ht * wt, C_)
-                    for b in range(B):
-                        for i_ in range(h):
-                            for dy in (0, 1):
-                                y = 2 * i_ + dy
-                                if y >= ht:
-                                    continue
-                                for dx in (0, 1):
-                                    n = (wt - dx + 1) // 2
-                                    emit(lib.mi355x_sd_copy_rows, (src.p + 2 * ((b * h + i_) * w_) * src.ld, src.ld,
-                                                                    upb.p + 2 * ((b * ht + y) * wt + dx) * C_, 2 * C_, n, C_, stream), "misc")
-                    conv3(upb, ht, wt, d[1], dst)
-                h, w_ = ht, wt
-                cur = dst
-            i += 1
-        assert k == len(skips) and u == len(ups) and ((h, w_) == (H, Wd) or self._encoder_only)
-
-        if self._encoder_only:
-            self._emit_post(pb, [skip_slot(kk) for kk in range(len(skips))], skips, cur, h, w_)
-        else:
-            # ---- post (unet_2d_condition.py:1193-1196) ----
-            g = gnorm(cur, H * Wd, "conv_norm_out", eps, True)
-            emit(lib.mi355x_sd_conv_out3x3, (g.p, g.ld, wp("conv_out.w"), wp("conv_out.b"), plan.out.data_ptr(), B, g.C, H,
-                                             Wd, cfg["out_channels"], stream), "misc")
-
-        pb.finish()
-        plan.B, plan.H, plan.W, plan.L = B, H, Wd, L
-        plan.scratch_bytes = sum(t.numel() * t.element_size() for t in plan.keep)
-        plan.emb_tensors = dict(t0=t0, emb=emb_t, temb_all=temb_all)
-        return plan
 
     # ------------------------------------------------------------------ execution
     def _finish_add_embedding(self, plan: _Plan, text_dim: int, n_ids: int) -> None:
@@ -904,7 +948,7 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
         if masked and self._ip:
             raise NotImplementedError("encoder_attention_mask together with IP-Adapter image tokens")
         return self.plan_for((B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len),
-                             lambda: self._build_plan(B, H, W, L, masked, controlnet, self_mask_len))
+                             lambda: self._Planner(self, B, H, W, L, masked, controlnet, self_mask_len).build())
 
     def stage_inputs(self, plan: _Plan, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
                      in_scale: Optional[float] = None, encoder_attention_mask=None,
@@ -1100,6 +1144,71 @@ class ControlNetOutput(SimpleNamespace):
     """``down_block_res_samples`` (tuple) and ``mid_block_res_sample`` (controlnet.py:46-68)"""
 
 
+class _ControlNetWeights(_UNetWeights):
+    def head(self):
+        """in place of conv_norm_out / conv_out: the conditioning embedding and the zero convolutions"""
+        ch = self.m._extra["conditioning_embedding_out_channels"]
+        w = self.get("controlnet_cond_embedding.conv_in.weight")
+        if self.m._extra["controlnet_conditioning_channel_order"] == "bgr":
+            w = torch.flip(w, dims=[1])                               # flipping the input channels = flipping the weight's
+        self.put_conv_in("cn.conv_in", w, "controlnet_cond_embedding.conv_in")
+        for j in range(2 * (len(ch) - 1)):
+            self.put_conv(f"cn.blocks.{j}", f"controlnet_cond_embedding.blocks.{j}")
+        self.put_conv("cn.conv_out", "controlnet_cond_embedding.conv_out")
+        k = 0
+        while f"controlnet_down_blocks.{k}.weight" in self.shapes:
+            self.put_conv(f"cn.down.{k}", f"controlnet_down_blocks.{k}")
+            k += 1
+        self.m._n_down = k
+        self.put_conv("cn.mid", "controlnet_mid_block")
+
+
+class _ControlNetPlanner(_UNetPlanner):
+    def stem(self) -> _V:
+        """ControlNetConditioningEmbedding.forward (controlnet.py:103-113) + ``sample = conv_in(sample) + cond`` (:807-810)"""
+        x0 = super().stem()
+        lib, stream, plan, pb, B, extra = self.lib, self.stream, self.plan, self.pb, self.B, self.m._extra
+        ch = extra["conditioning_embedding_out_channels"]
+        f = 1 << (len(ch) - 1)
+        hc, wc = self.H * f, self.W * f
+        plan.cond = pb.persist((B, extra["conditioning_channels"], hc, wc), torch.float32)
+        bufs = [pb.persist((B * hc * wc * ch[0],), _lib.elem_dtype()), pb.persist((B * hc * wc * ch[0],), _lib.elem_dtype())]
+        e = _V(bufs[0].data_ptr(), B * hc * wc, ch[0])
+        pb.emit(lib.mi355x_sd_conv_in3x3, (plan.cond.data_ptr(), None, pb.wp("cn.conv_in.w"), pb.wp("cn.conv_in.b"), e.p, B,
+                                           extra["conditioning_channels"], hc, wc, ch[0], e.ld, stream), "misc")
+        pb.emit(lib.mi355x_sd_silu, (e.p, e.p, B * hc * wc * ch[0], 0, 0, stream), "misc")
+        which = 0
+        for i in range(len(ch) - 1):
+            for j, (cout, stride) in enumerate(((ch[i], 1), (ch[i + 1], 2))):
+                ho, wo = (hc + 2 - 3) // stride + 1, (wc + 2 - 3) // stride + 1
+                which ^= 1
+                out = _V(bufs[which].data_ptr(), B * ho * wo, cout)
+                pb.conv3(e, hc, wc, f"cn.blocks.{2 * i + j}", out, stride=stride, flags=SILU)
+                e, hc, wc = out, ho, wo
+        assert (hc, wc) == (self.H, self.W)
+        pb.conv3(e, hc, wc, "cn.conv_out", x0, R=x0)
+        return x0
+
+    def head(self, mid: _V, hm, wm):
+        """zero convolutions + scaling (controlnet.py:842-869) -> fp32 NCHW residuals"""
+        pb, B = self.pb, self.B
+        scale, guess = self.m._cn_key
+        n = len(self.skips)
+        if n != self.m._n_down:
+            raise ValueError(f"checkpoint has {self.m._n_down} controlnet_down_blocks, the configuration produces {n} skips")
+        scales = [scale] * (n + 1)
+        if guess:   # paddle.logspace(-1, 0, n + 1) * conditioning_scale (:855-859)
+            scales = [float(v) * scale for v in torch.logspace(-1, 0, n + 1)]
+        self.plan.ctrl_out = []
+        for k, (cs, hs, ws_) in enumerate(self.skips + [(mid.C, hm, wm)]):
+            sl = self.skip_slot(k) if k < n else mid
+            rows = _V(pb.sc("cn_rows", 2 * sl.rows * cs), sl.rows, cs)
+            pb.linear(sl, f"cn.down.{k}" if k < n else "cn.mid", rows, out_scale=scales[k])
+            out = pb.persist((B, cs, hs, ws_), torch.float32)
+            pb.emit(self.lib.mi355x_sd_unpatchify, (rows.p, rows.ld, B, cs, hs, ws_, 1, out.data_ptr(), self.stream), "misc")
+            self.plan.ctrl_out.append(out)
+
+
 class ControlNetModel(UNet2DConditionModel):
     """ControlNetModel.forward (PPD/models/controlnet.py:671-877) on the UNet's program: conv_in + conditioning embedding
     (3x3 convs with SiLU epilogues, the last one adding onto conv_in's output in place), the down blocks and the mid block
@@ -1107,6 +1216,7 @@ class ControlNetModel(UNet2DConditionModel):
     returned as the fp32 NCHW tensors ``UNet2DConditionModel.forward`` takes as ``down_block_additional_residuals`` /
     ``mid_block_additional_residual``."""
     _encoder_only = True
+    _Weights, _Planner = _ControlNetWeights, _ControlNetPlanner
     _param_shapes = staticmethod(controlnet_param_shapes)
 
     def __init__(self, config: Mapping, params: Mapping[str, Tensor], **kw):
@@ -1120,68 +1230,8 @@ class ControlNetModel(UNet2DConditionModel):
     def _shapes(self) -> Dict[str, tuple]:
         return controlnet_param_shapes(self._full_config)
 
-    def _load_extra(self, get, bf, put_conv) -> None:
-        W, ch = self.w, self._extra["conditioning_embedding_out_channels"]
-        w = get("controlnet_cond_embedding.conv_in.weight")           # -> [ky][kx][ci][O], the conv_in kernel's layout
-        if self._extra["controlnet_conditioning_channel_order"] == "bgr":
-            w = torch.flip(w, dims=[1])                               # flipping the input channels = flipping the weight's
-        W["cn.conv_in.w"] = bf(w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]))
-        W["cn.conv_in.b"] = get("controlnet_cond_embedding.conv_in.bias").contiguous()
-        for j in range(2 * (len(ch) - 1)):
-            put_conv(f"cn.blocks.{j}", f"controlnet_cond_embedding.blocks.{j}")
-        put_conv("cn.conv_out", "controlnet_cond_embedding.conv_out")
-        k = 0
-        while f"controlnet_down_blocks.{k}.weight" in self._shapes():
-            put_conv(f"cn.down.{k}", f"controlnet_down_blocks.{k}")
-            k += 1
-        self._n_down = k
-        put_conv("cn.mid", "controlnet_mid_block")
-
-    def _emit_pre(self, pb: PlanBuilder, x0: _V, H, Wd) -> None:
-        """ControlNetConditioningEmbedding.forward (controlnet.py:103-113) + ``sample = conv_in(sample) + cond`` (:807-810)"""
-        lib, stream = self._lib, self._stream_ptr
-        plan, B, persist, emit, wp, conv3 = pb.plan, pb.B, pb.persist, pb.emit, pb.wp, pb.conv3
-        ch = self._extra["conditioning_embedding_out_channels"]
-        f = 1 << (len(ch) - 1)
-        hc, wc = H * f, Wd * f
-        plan.cond = persist((B, self._extra["conditioning_channels"], hc, wc), torch.float32)
-        bufs = [persist((B * hc * wc * ch[0],), _lib.elem_dtype()), persist((B * hc * wc * ch[0],), _lib.elem_dtype())]
-        e = _V(bufs[0].data_ptr(), B * hc * wc, ch[0])
-        emit(lib.mi355x_sd_conv_in3x3, (plan.cond.data_ptr(), None, wp("cn.conv_in.w"), wp("cn.conv_in.b"), e.p, B,
-                                        self._extra["conditioning_channels"], hc, wc, ch[0], e.ld, stream), "misc")
-        emit(lib.mi355x_sd_silu, (e.p, e.p, B * hc * wc * ch[0], 0, 0, stream), "misc")
-        which = 0
-        for i in range(len(ch) - 1):
-            for j, (cout, stride) in enumerate(((ch[i], 1), (ch[i + 1], 2))):
-                ho, wo = (hc + 2 - 3) // stride + 1, (wc + 2 - 3) // stride + 1
-                which ^= 1
-                out = _V(bufs[which].data_ptr(), B * ho * wo, cout)
-                conv3(e, hc, wc, f"cn.blocks.{2 * i + j}", out, stride=stride, flags=SILU)
-                e, hc, wc = out, ho, wo
-        assert (hc, wc) == (H, Wd)
-        conv3(e, hc, wc, "cn.conv_out", x0, R=x0)
-
-    def _emit_post(self, pb: PlanBuilder, slots, skips, mid: _V, hm, wm) -> None:
-        """zero convolutions + scaling (controlnet.py:842-869) -> fp32 NCHW residuals"""
-        lib, stream, plan, B = self._lib, self._stream_ptr, pb.plan, pb.B
-        scale, guess = self._cn_key
-        n = len(slots)
-        if n != self._n_down:
-            raise ValueError(f"checkpoint has {self._n_down} controlnet_down_blocks, the configuration produces {n} skips")
-        scales = [scale] * (n + 1)
-        if guess:   # paddle.logspace(-1, 0, n + 1) * conditioning_scale (:855-859)
-            scales = [float(v) * scale for v in torch.logspace(-1, 0, n + 1)]
-        plan.ctrl_out = []
-        for k, (sl, (cs, hs, ws_)) in enumerate(list(zip(slots, skips)) + [(mid, (mid.C, hm, wm))]):
-            key = f"cn.down.{k}" if k < n else "cn.mid"
-            rows = _V(pb.sc("cn_rows", 2 * sl.rows * cs), sl.rows, cs)
-            pb.linear(sl, key, rows, out_scale=scales[k])
-            out = pb.persist((B, cs, hs, ws_), torch.float32)
-            pb.emit(lib.mi355x_sd_unpatchify, (rows.p, rows.ld, B, cs, hs, ws_, 1, out.data_ptr(), stream), "misc")
-            plan.ctrl_out.append(out)
-
     def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False) -> _Plan:
-        return self.plan_for((B, H, W, L, masked) + self._cn_key, lambda: self._build_plan(B, H, W, L, masked, False))
+        return self.plan_for((B, H, W, L, masked) + self._cn_key, lambda: self._Planner(self, B, H, W, L, masked).build())
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale: float = 1.0,
                 class_labels=None, timestep_cond=None, attention_mask=None, added_cond_kwargs=None,
