@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 20
+#define MI355X_SD_ABI_VERSION 21
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -649,6 +649,43 @@ int mi355x_sd_dpm2_update(const float* x, const float* eps_uncond, const float* 
 int mi355x_sd_plms_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream);
+
+/* One model evaluation of DPM-Solver singlestep sampling (DPMSolverSinglestepScheduler: dpmsolver++ / dpmsolver, orders 1-3, midpoint /
+ * heun) in one launch: guidance combine, guidance rescale, convert_model_output, the update, the parked sample and the group's
+ * converted outputs. An order-k evaluation steps from the sample parked k - 1 evaluations earlier, not from the current latents.
+ * `park` (S) is one caller-owned plane of batch * per_sample fp32 values; `hist` is two such planes, batch * per_sample values apart:
+ * plane 0 holds the first converted output of the current group (an order-1 evaluation and the order-2 and order-3 ones that follow
+ * it), plane 1 its second. With e the guided (and rescaled) model output as in mi355x_sd_multistep_update, per element:
+ *   m0  = p*x + q*e
+ *   order 1:  out = A*x + B*m0                          then S <- x (bit copy), plane 0 <- m0; S and hist are NOT read
+ *   order 2:  out = A*S + B*b + E1*(m0 - b)             b = plane 0; plane 1 <- m0 only if keep != 0; S and plane 0 are NOT written
+ *   order 3:  out = A*S + B*b + E1*(m0 - b)             b = plane 0
+ *                   [+ E2*(m1 - b)]                     m1 = plane 1, only if E2 != 0 (heun); otherwise plane 1 is NOT read
+ *                                                       nothing but out is written
+ * Rules:
+ *  - coef is 8 fp32 values (p, q, A, B, E1, E2, order, keep) in device memory, read by the kernel
+ *    (DPMSolverSinglestepScheduler.singlestep_coefficients): a captured graph of one node replays a whole loop, every order, with only
+ *    the row changing and park / hist at fixed addresses. keep != 0 on an order-2 row says that an order-3 evaluation follows.
+ *  - order is 1, 2 or 3; any other device value is taken as the nearest of them (NaN: 1). An order-k row (k > 1) must directly follow
+ *    the order-(k - 1) row of its group: each plane has one writer per group, nothing is shifted and the launch copies no plane.
+ *  - eps_text == NULL: no guidance, e = eps_uncond; guidance_scale and guidance_rescale are ignored.
+ *  - order, keep and E2 == 0 are wave-uniform branches on the device values. State an evaluation does not need is not dereferenced:
+ *    park and hist need no initialising before a loop's first launch (an order-1 row), and stale or NaN contents of S or of a plane
+ *    cannot reach out where the row does not use them. x is read by every row.
+ *  - operation order: as written above, every difference formed before it is multiplied (E1 and E2 carry the reciprocals of the step
+ *    ratios: the regrouped form would cancel), the terms summed left to right; which product contracts into which sum is the
+ *    compiler's choice, as in mi355x_sd_multistep_update.
+ *  - two launches on equal inputs give equal bits (no atomics; the rescale's sums are the fixed trees of mi355x_sd_cfg_rescale_axpby).
+ *  - two forms: guidance_rescale > 0 with eps_text runs one 1024-thread block per sample (the statistics passes of
+ *    mi355x_sd_cfg_rescale_axpby; a sample of <= 32768 elements stays in registers, larger ones are re-read); otherwise a grid-stride
+ *    elementwise kernel with 16-byte vectors when x, park, hist, out and the eps planes are 16-byte aligned and batch * per_sample is
+ *    a multiple of 4 (both planes of hist aligned), and a scalar tail. No scratch memory.
+ *  - aliasing: out may be x itself. Any other overlap of out, park or the two planes of hist with each other, x, eps_uncond,
+ *    eps_text or coef is MI355X_SD_ERR_INVALID before any launch, as are a null x, eps_uncond, park, hist, out or coef, batch <= 0,
+ *    per_sample < 1, and per_sample < 2 with guidance_rescale > 0. */
+int mi355x_sd_singlestep_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
+                                const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                                void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

@@ -24,7 +24,7 @@ if os.environ.get("MI355X_SD_LIB") == "dbg":
         raise ValueError("MI355X_SD_LIB=dbg: the debug-switch build exists for bf16 elements only")
     LIB_PATH = os.path.join(_HERE, "libmi355x_sd_dbg.so")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 GEGLU, OUT_F32, SILU, GELU_TANH, PAD_BR, R_F32, CONV_KB64 = 1, 2, 4, 8, 16, 32, 64
 UNET_ENC_MASK, UNET_SELF_MASK, UNET_CONTROLNET = 1, 2, 4   # mi355x_sd_unet_plan_ex flags
 SDPA_LOG2 = 1
@@ -157,6 +157,10 @@ SIGNATURES = {
     # ring of three model outputs and the parked sample (csrc/step_tail.hip, ABI 20)
     "mi355x_sd_plms_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
                                       c_int64, c_void_p]),
+    # one evaluation of DPM-Solver singlestep sampling (DPMSolverSinglestepScheduler): guidance, rescale, convert_model_output, the
+    # update, the parked sample and the group's two converted outputs (csrc/step_tail.hip, ABI 21)
+    "mi355x_sd_singlestep_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                            c_int, c_int64, c_void_p]),
     # seam B1: the whole UNet behind a handle (csrc/unet_exec.hip)
     "mi355x_sd_unet_create": (c_int, [c_char_p, POINTER(c_void_p)]),
     "mi355x_sd_unet_destroy": (c_int, [c_void_p]),

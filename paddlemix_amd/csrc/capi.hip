@@ -730,6 +730,22 @@ int mi355x_sd_plms_update(const float* x, const float* eps_uncond, const float* 
                                    batch, (long)per_sample, S(stream)), who);
 }
 
+int mi355x_sd_singlestep_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
+                                const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
+                                void* stream) {
+  const char* who = "mi355x_sd_singlestep_update";
+  if (!x || !eps_uncond || !park || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  const bool rescale = eps_text && guidance_rescale > 0.0f;
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 2, STEP_RANGE_RULE, {{out, bytes}, {park, bytes}, {hist, bytes * 2}},
+                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 8 * sizeof(float)}}, {{0, 0}},
+                               "%s: out may be x itself; out, park and the two planes of hist must not overlap each other, the "
+                               "inputs or coef in any other way"))
+    return rc;
+  return finish(launch_singlestep_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale,
+                                         rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

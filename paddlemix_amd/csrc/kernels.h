@@ -173,6 +173,8 @@ int launch_dpm2_update(const float* x, const float* eu, const float* et, const f
                        const float* coef, float gs, float gr, int batch, long per_sample, hipStream_t stream);
 int launch_plms_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
                        float gs, float gr, int batch, long per_sample, hipStream_t stream);
+int launch_singlestep_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
+                             float gs, float gr, int batch, long per_sample, hipStream_t stream);
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 

@@ -1,9 +1,10 @@
 // The fused step tails (gfx950): the guidance combine, the guidance rescale and one scheduler step in one launch over the fp32 latents.
 //
-// One skeleton, seven step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
+// One skeleton, eight step forms. A STEP FORM is a small struct -- LinearStep (DDIM at eta = 0, Euler), MultistepStep (DPM-Solver
 // multistep), UniPCStep, AncestralStep (Euler a), HeunStep (Heun: two stages), MidpointStep (DPM2 and DPM2 a: two stages, the second
-// with noise), PlmsStep (PNDM's PLMS: a ring of three model outputs and a parked sample) -- that holds the operand pointers of its
-// step and states its arithmetic once:
+// with noise), PlmsStep (PNDM's PLMS: a ring of three model outputs and a parked sample), SinglestepStep (DPM-Solver singlestep: a
+// parked sample and the group's first two converted outputs) -- that holds the operand pointers of its step and states its
+// arithmetic once:
 //   operands            the leading members, filled by the public launcher (aggregate initialisation; the rest is set on the device)
 //   FLAT                whether the form has an elementwise kernel here (LinearStep: no, see there)
 //   vector_ok()         host: the operands allow the 16-byte vector loop (alignment, and whatever else the form needs)
@@ -23,7 +24,8 @@
 //   the steps                            schedulers/scheduling_euler_discrete.py, scheduling_ddim.py, scheduling_dpmsolver_multistep.py,
 //                                        scheduling_unipc_multistep.py, scheduling_euler_ancestral_discrete.py,
 //                                        scheduling_heun_discrete.py, scheduling_k_dpm_2_discrete.py,
-//                                        scheduling_k_dpm_2_ancestral_discrete.py, scheduling_pndm.py (step_plms)
+//                                        scheduling_k_dpm_2_ancestral_discrete.py, scheduling_pndm.py (step_plms),
+//                                        scheduling_dpmsolver_singlestep.py
 #include "common.h"
 #include "kernels.h"
 
@@ -690,6 +692,109 @@ struct PlmsStep {
 int launch_plms_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
                        float gs, float gr, int batch, long per_sample, hipStream_t stream) {
   return launch_step(PlmsStep{x, park, hist, (long)batch * per_sample, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
+}
+
+// One model evaluation of DPM-Solver SINGLESTEP sampling (DPMSolverSinglestepScheduler: dpmsolver++ / dpmsolver, orders 1-3, midpoint /
+// heun; an order-k evaluation does not step from the current latents but from the sample parked k - 1 evaluations earlier, with the
+// converted outputs of its group as differences against the group's first) in one launch: the guidance combine, the guidance
+// rescale, convert_model_output, the update, the parked sample and the group's outputs. The state lives in caller-owned planes: S
+// (`park`, the sample the group started from) and TWO planes of `hist`, batch * per_sample elements apart: plane 0 the group's first
+// converted output, plane 1 its second. A group is an order-1 evaluation followed by an order-2 and then an order-3 one, as far as it
+// goes, so each plane has one writer per group and a fixed meaning: nothing is shifted and no plane is copied. With coef =
+// (p, q, A, B, E1, E2, order, keep) in device memory (8 fp32: 32 bytes), per element and IN THIS ORDER (tests/singlestep_bounds.py
+// derives its bound from it; which product fuses with which sum is the compiler's choice, as in multistep_elem):
+//   e   = the guided (and rescaled) model output, as in the ancestral step
+//   m0  = p * x + q * e
+//   order 1:  out = A * x + B * m0                        S <- x (bit copy), plane 0 <- m0; S and hist are NOT read
+//   order 2:  b   = plane 0
+//             out = A * S + B * b + E1 * (m0 - b)         plane 1 <- m0 only if keep != 0 (an order-3 evaluation follows); S and
+//                                                         plane 0 are NOT written
+//   order 3:  b   = plane 0, m1 = plane 1
+//             out = A * S + B * b + E1 * (m0 - b)
+//             out = out + E2 * (m1 - b)                   only if E2 != 0 (heun); E2 == 0 (midpoint): plane 1 is NOT read
+//                                                         nothing but out is written
+// Every difference is taken against b and formed before it is multiplied: E1 and E2 carry 1 / r0, 1 / r1 and 1 / (r0 - r1), and the
+// regrouped (B - E1 - E2) * b + E1 * m0 + E2 * m1 would cancel, as in multistep_elem. order, keep and E2 != 0 are uniform branches on
+// the device values, set once in load(): one captured node replays every evaluation of a loop with only the row changing and every
+// pointer fixed. order is 1, 2 or 3; any other device value is taken as the nearest of them (NaN: 1), so that a wrong row cannot do
+// anything the three branches don't. State an evaluation does not need never enters the arithmetic -- a fresh loop's S and hist are
+// uninitialised, and 0 * NaN would poison the latents. x is read by every row (for m0) and out written by the same lane in the last
+// pass only: out may be x. S and hist are touched by that same lane at the same element; they overlap nothing else.
+struct SsCoef {
+  float p, q, A, B, E1, E2, order, keep;
+};
+
+__device__ __forceinline__ void singlestep_elem(const SsCoef& k, int order, bool heun, float x, float e, float S, float b, float m1,
+                                                float& o, float& m0) {
+  m0 = k.p * x + k.q * e;
+  if (order == 1) {
+    o = k.A * x + k.B * m0;
+  } else {
+    o = k.A * S + k.B * b + k.E1 * (m0 - b);
+    if (heun) o += k.E2 * (m1 - b);
+  }
+}
+
+struct SinglestepStep {
+  static constexpr bool FLAT = true;
+  const float* x;
+  float *park, *hist;
+  long plane;   // the planes of hist are batch * per_sample elements apart, for every sample
+  float* out;
+  SsCoef k;
+  int order;
+  bool keep, heun;   // order 2 writes plane 1; order 3 adds E2 (m1 - b)
+
+  bool vector_ok() const { return !((ptr_bits(x) | ptr_bits(park) | ptr_bits(hist) | ptr_bits(out)) & 15) && !(plane & 3); }
+  __device__ __forceinline__ void load(const float* __restrict__ c) {
+    k = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]};
+    order = k.order >= 2.5f ? 3 : k.order >= 1.5f ? 2 : 1;
+    keep = order == 2 && k.keep != 0.0f;
+    heun = order == 3 && k.E2 != 0.0f;
+  }
+  __device__ __forceinline__ void to_sample(long base) { x += base, park += base, hist += base, out += base; }
+  __device__ __forceinline__ void elem(long i, float e) const {
+    const float xv = x[i];
+    const float S = order > 1 ? park[i] : 0.f, b = order > 1 ? hist[i] : 0.f, m1 = heun ? hist[plane + i] : 0.f;
+    float o, m0;
+    singlestep_elem(k, order, heun, xv, e, S, b, m1, o, m0);
+    out[i] = o;
+    if (order == 1) {
+      park[i] = xv;
+      hist[i] = m0;
+    } else if (keep) {
+      hist[plane + i] = m0;
+    }
+  }
+  template <class E>
+  __device__ __forceinline__ void vec(long i, E&& guided) const {
+    f32x4 *s4 = reinterpret_cast<f32x4*>(park), *p0 = reinterpret_cast<f32x4*>(hist), *p1 = reinterpret_cast<f32x4*>(hist + plane);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f}, xv = reinterpret_cast<const f32x4*>(x)[i], ev = guided();
+    f32x4 Sv = zero, bv = zero, m1 = zero, ov, mv;
+    if (order > 1) {
+      Sv = s4[i];
+      bv = p0[i];
+    }
+    if (heun) m1 = p1[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float o, m0;
+      singlestep_elem(k, order, heun, xv[j], ev[j], Sv[j], bv[j], m1[j], o, m0);
+      ov[j] = o, mv[j] = m0;
+    }
+    reinterpret_cast<f32x4*>(out)[i] = ov;
+    if (order == 1) {
+      s4[i] = xv;
+      p0[i] = mv;
+    } else if (keep) {
+      p1[i] = mv;
+    }
+  }
+};
+
+int launch_singlestep_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
+                             float gs, float gr, int batch, long per_sample, hipStream_t stream) {
+  return launch_step(SinglestepStep{x, park, hist, (long)batch * per_sample, out}, eu, et, coef, gs, gr, batch, per_sample, stream);
 }
 
 }  // namespace sd

@@ -466,6 +466,29 @@ def plms_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park:
     return out
 
 
+def singlestep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park: Tensor, hist: Tensor, coef: Tensor,
+                      guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """One model evaluation of DPM-Solver singlestep sampling (``DPMSolverSinglestepScheduler``) in one launch -> out; ``park`` (the
+    sample S the group of evaluations started from) and ``hist`` (the group's first and second converted model output) are updated IN
+    PLACE. x, eps_uncond, eps_text (None: no guidance), park: contiguous fp32 [B, ...] of one shape; hist: contiguous fp32 [2, B, ...];
+    coef: fp32 GPU (p, q, A, B, E1, E2, order, keep) of ``DPMSolverSinglestepScheduler.singlestep_coefficients``. With e the guided
+    (and, with guidance_rescale > 0, rescaled) model output, m0 = p x + q e and b = hist[0]: order 1: out = A x + B m0, then S = x and
+    hist[0] = m0; order 2: out = A S + B b + E1 (m0 - b), then hist[1] = m0 if keep; order 3: the same plus E2 (hist[1] - b) where
+    E2 != 0. State a row does not use is not read. out may be x."""
+    lib = _lib.load()
+    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (park, "park", False), (out, "out", True)),
+               coef, 8, "coef: expected a contiguous fp32 GPU tensor of the 8 values of a singlestep row",
+               eps_text is not None and guidance_rescale > 0.0)
+    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] != 2 or hist.shape[1:] != x.shape:
+        raise ValueError(f"hist: expected [2, {', '.join(map(str, x.shape))}]")
+    _flat_f32(hist, "hist")
+    out = torch.empty_like(x) if out is None else out
+    check(lib.mi355x_sd_singlestep_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), park.data_ptr(), hist.data_ptr(),
+                                          out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
+                                          x.numel() // x.shape[0], _stream()))
+    return out
+
+
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
                  guidance_scale: float, guidance_rescale: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
     """One UniPC step in one launch -> out; ``last`` and ``hist`` are updated IN PLACE. x, eps_uncond, eps_text (None: no guidance),

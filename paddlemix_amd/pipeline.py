@@ -226,8 +226,25 @@ class _PlmsTail(_FusedTail):
                                               lat.numel() // lat.shape[0], stream)
 
 
+class _SinglestepTail(_FusedTail):
+    """``singlestep_coefficients`` (DPM-Solver singlestep): one launch per model evaluation; (p, q, A, B, E1, E2, order, keep) = row
+    i - first of a table [evaluations, 8] over the timesteps the loop RUNS (an img2img loop starts inside the schedule, where the
+    listed order may not be possible yet). The tail owns the parked sample and the two planes of the group's converted outputs; the
+    first row has order 1 and reads neither, every later one reads only what an earlier launch of its group wrote, so fresh ones are
+    not initialised, no plane is ever copied and their pointers stay fixed for the whole loop"""
+
+    walk, entry = "singlestep_coefficients", "mi355x_sd_singlestep_update"
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.history is None:
+            self.history, self.park, self.first = lat.new_empty((2,) + tuple(lat.shape)), torch.empty_like(lat), i
+        return self.lib.mi355x_sd_singlestep_update(lat.data_ptr(), eps, eps_text, self.park.data_ptr(), self.history.data_ptr(),
+                                                    out.data_ptr(), self.coef.data_ptr() + 32 * (i - self.first), gs, gr,
+                                                    lat.shape[0], lat.numel() // lat.shape[0], stream)
+
+
 # in priority order: the first whose walk the scheduler has
-_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _Dpm2Tail, _PlmsTail, _LinearTail)
+_TAILS = (_UniPCTail, _MultistepTail, _AncestralTail, _HeunTail, _Dpm2Tail, _PlmsTail, _SinglestepTail, _LinearTail)
 
 
 class _VaeSwitches:

@@ -13,6 +13,7 @@ Mirrors the reference classes' public contract -- ``set_timesteps`` / ``scale_mo
   HeunDiscreteScheduler              scheduling_heun_discrete.py:71 (set_timesteps :213-277, step :349-455) -- "Heun", order 2
   KDPM2DiscreteScheduler             scheduling_k_dpm_2_discrete.py:71 (set_timesteps :209-286, step :365-462) -- "DPM2", order 2
   KDPM2AncestralDiscreteScheduler    scheduling_k_dpm_2_ancestral_discrete.py:72 (set_timesteps :210-296, step :373-478) -- "DPM2 a"
+  DPMSolverSinglestepScheduler       scheduling_dpmsolver_singlestep.py:75 (order list :201-233, updates :482-734, step :815-878), orders 1-3
 Schedule tables are float32 numpy like the reference's float32 tensors; ``step`` works on torch tensors of any device.
 
 For deterministic sampling every ``step`` is a linear map  prev = a*sample + b*model_output ; ``step_coefficients``
@@ -32,6 +33,9 @@ The DPM2 step is a midpoint method of the same two-stage shape that parks the sa
 the second stage: ``dpm2_coefficients`` of both classes returns (p, q, h, c, second) for the library's ``mi355x_sd_dpm2_update``.
 The PLMS step (PNDM with ``skip_prk_steps``) is linear in the sample, the model output, up to three stored model outputs and one parked
 sample: ``PNDMScheduler.plms_coefficients`` returns its row of 12 for the library's ``mi355x_sd_plms_update``.
+The singlestep DPM-Solver evaluation is linear in the sample, the model output, the sample parked at the start of its group and the
+group's first two converted outputs: ``DPMSolverSinglestepScheduler.singlestep_coefficients`` returns (p, q, A, B, E1, E2, order, keep)
+for the library's ``mi355x_sd_singlestep_update``.
 
 The schedule pieces. Every class below is put together from module-level functions that are each written once, and from one base
 plus one mixin:
@@ -1377,6 +1381,227 @@ class UniPCMultistepScheduler(_Schedule):
         while alpha_t.dim() < original_samples.dim():
             alpha_t, sigma_t = alpha_t.unsqueeze(-1), sigma_t.unsqueeze(-1)
         return alpha_t * original_samples + sigma_t * noise
+
+
+class DPMSolverSinglestepScheduler(_Schedule):
+    """The singlestep DPM-Solver(++) of orders 1-3 (scheduling_dpmsolver_singlestep.py:75-920; what diffusers-style front ends pick
+    for their "DPM++ 2S"-type presets): the evaluations run in groups of ``solver_order``, an order-k evaluation stepping from the
+    sample parked k - 1 evaluations earlier with the group's converted outputs as differences against its first. Implemented:
+    ``solver_order`` 1-3, "dpmsolver++" / "dpmsolver" ("deis" becomes "dpmsolver++"), "midpoint" / "heun" ("logrho" / "bh1" / "bh2"
+    become "midpoint"), epsilon / sample / v_prediction, ``lower_order_final`` (switched on by ``set_timesteps`` when the step count is
+    no multiple of the order), Karras sigmas, the img2img order reduction of ``step``. linspace spacing only, as the reference.
+    Not implemented (NotImplementedError): thresholding, ``trained_betas``, a finite ``lambda_min_clipped``, ``variance_type``.
+
+    The step's scalars are float32 TENSOR expressions, as the reference's 0-dim tensors give them, not numpy's as in
+    ``DPMSolverMultistepScheduler._update_scalars``: numpy's float32 log and exp round differently from the tensor library's on one
+    argument in eight, this update divides differences of logs by each other, and the recorded loops
+    (tests/golden/singlestep) are reproduced bit for bit only with the tensor ones. The training table is the "tensor" one for the
+    same reason. Every evaluation is linear in the tensors: ``singlestep_coefficients`` returns it as one row for the library's
+    ``mi355x_sd_singlestep_update``."""
+
+    _train_arithmetic = "tensor"
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", trained_betas=None, solver_order: int = 2, prediction_type: str = "epsilon",
+                 thresholding: bool = False, dynamic_thresholding_ratio: float = 0.995, sample_max_value: float = 1.0,
+                 algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint", lower_order_final: bool = True,
+                 use_karras_sigmas: Optional[bool] = False, lambda_min_clipped: float = -float("inf"),
+                 variance_type: Optional[str] = None):
+        if algorithm_type not in ("dpmsolver", "dpmsolver++"):
+            if algorithm_type != "deis":
+                raise NotImplementedError(f"{algorithm_type} does is not implemented for {self.__class__}")
+            algorithm_type = "dpmsolver++"
+        if solver_type not in ("midpoint", "heun"):
+            if solver_type not in ("logrho", "bh1", "bh2"):
+                raise NotImplementedError(f"{solver_type} does is not implemented for {self.__class__}")
+            solver_type = "midpoint"
+        self._capture(locals())
+        if solver_order not in (1, 2, 3) or thresholding or lambda_min_clipped != -float("inf") or variance_type:
+            raise NotImplementedError("DPMSolverSinglestepScheduler(mi355x): solver_order outside 1-3, thresholding, "
+                                      "lambda_min_clipped and learned variance are not implemented")
+        self._build()
+        self.order_list = self.get_order_list(num_train_timesteps)
+
+    def _reset(self):
+        self.model_outputs = [None] * self.config.solver_order
+        self.sample = None
+        self._last_order = 0   # the effective order of the evaluation before this one (0: none yet)
+        self._step_index = None
+
+    coefficient_walk = _coefficient_walk("_step_index", "model_outputs", "sample", "_last_order")   # (singlestep_coefficients)
+
+    def get_order_list(self, num_inference_steps: int):
+        """the solver order listed for each step (:201-233)"""
+        steps, order = num_inference_steps, self.config.solver_order
+        if order == 1:
+            return [1] * steps
+        if not self.config.lower_order_final:
+            return list(range(1, order + 1)) * (steps // order)
+        if order == 2:
+            return [1, 2] * (steps // 2) + [1] * (steps % 2)
+        if steps % 3 == 0:
+            return [1, 2, 3] * (steps // 3 - 1) + [1, 2] + [1]
+        return [1, 2, 3] * (steps // 3) + ([1] if steps % 3 == 1 else [1, 2])
+
+    def set_timesteps(self, num_inference_steps: int):
+        c = self.config
+        spaced = SimpleNamespace(timestep_spacing="linspace", steps_offset=0, num_train_timesteps=c.num_train_timesteps,
+                                 use_karras_sigmas=c.use_karras_sigmas)   # (the reference has this one spacing and no offset)
+        self.sigmas, self.timesteps = _multistep_schedule(self.alphas_cumprod, spaced, num_inference_steps, karras_ends_as_float=True)
+        self.num_inference_steps = num_inference_steps
+        if not c.lower_order_final and num_inference_steps % c.solver_order != 0:
+            c.lower_order_final = True   # (:287-291: an uneven step count is finished at lower order, from now on)
+        self.order_list = self.get_order_list(num_inference_steps)
+        self._reset()
+
+    _init_step_index = _init_multistep_index
+    _sigma_to_alpha_sigma_t = staticmethod(_sigma_to_alpha_sigma_t)
+    add_noise = UniPCMultistepScheduler.add_noise   # (:896-917: the CURRENT schedule's sigmas, as UniPC's)
+
+    def _alpha_sigma(self) -> Tuple[float, float]:
+        _check_alpha_prediction_type(self.config.prediction_type, "DPMSolverSinglestepScheduler")
+        return _alpha_sigma_floats(torch.from_numpy(self.sigmas)[self._step_index])
+
+    def convert_model_output(self, model_output, *args, sample=None, **kwargs):
+        """model output -> x0 prediction (dpmsolver++) or epsilon prediction (dpmsolver), :393-480"""
+        if sample is None:
+            if len(args) < 2:
+                raise ValueError("missing `sample` as a required keyward argument")
+            sample = args[1]
+        c = self.config
+        return _alpha_convert(c.prediction_type, c.algorithm_type == "dpmsolver++", *self._alpha_sigma(), sample, model_output)
+
+    def _effective_order(self, have) -> int:
+        """the order listed for this step, lowered until the group has that many outputs (:859-864: an img2img loop may start where
+        the list says 2 or 3). `have`: the converted outputs held, this step's included, oldest first; None = not there"""
+        order = self.order_list[self._step_index]
+        while have[-order] is None:
+            order -= 1
+        return order
+
+    def _update_scalars(self, order: int):
+        """The scalars of an order-`order` update that ends at sigma index ``_step_index + 1`` and starts `order` - 1 indices before
+        ``_step_index`` -> (A, b, terms), each a float of a float32 tensor expression:
+            order 1 (:526-536)   prev = A x - b m0                                             terms = ()
+            order 2 (:583-630)   D1 = ri0 (m0 - m1);  prev = A S - b m1 -/+ c D1                terms = (ri0, c, plus)
+            order 3, midpoint    D1_1 = ri0 (m0 - m2);  prev = A S - b m2 -/+ c D1_1            terms = (ri0, c, plus)
+            order 3, heun        D1_0 = ri1 (m1 - m2), D1 = (r0 D1_0 - r1 D1_1) / (r0 - r1), D2 = 2 (D1_1 - D1_0) / (r0 - r1);
+                                 prev = A S - b m2 -/+ c D1 - d D2                              terms = (ri0, c, plus, ri1, r0, r1, r01, d)
+        ri0 = 1 / r0, ri1 = 1 / r1, r01 = r0 - r1. ``step`` and ``singlestep_coefficients`` both read this and nothing else of the
+        schedule. c and d come with the sign the reference's expressions give them and `plus` apart, as in the multistep class."""
+        cfg, i, f = self.config, self._step_index, float
+        sig = torch.from_numpy(self.sigmas)
+        lam = lambda a, s: torch.log(a) - torch.log(s)   # noqa: E731
+        at, st = _sigma_to_alpha_sigma_t(sig[i + 1])
+        a0, s0 = _sigma_to_alpha_sigma_t(sig[i])
+        ab, sb = _sigma_to_alpha_sigma_t(sig[i - (order - 1)])   # where the group started: s0 (order 1), s1, s2
+        lt, l0, lb = lam(at, st), lam(a0, s0), lam(ab, sb)
+        h = lt - lb
+        pp = cfg.algorithm_type == "dpmsolver++"
+        A, b = (f(st / sb), f(at * (torch.exp(-h) - 1.0))) if pp else (f(at / ab), f(st * (torch.exp(h) - 1.0)))
+        if order == 1:
+            return A, b, ()
+        r0 = (l0 - lb) / h
+        heun = cfg.solver_type == "heun"
+        first = at * ((torch.exp(-h) - 1.0) / h + 1.0) if pp else st * ((torch.exp(h) - 1.0) / h - 1.0)
+        if order == 2 and not heun:
+            return A, b, (f(1.0 / r0), f(0.5 * (at * (torch.exp(-h) - 1.0))) if pp else f(0.5 * (st * (torch.exp(h) - 1.0))), False)
+        if order == 2 or not heun:
+            return A, b, (f(1.0 / r0), f(first), pp)
+        a1, s1 = _sigma_to_alpha_sigma_t(sig[i - 1])
+        r1 = (lam(a1, s1) - lb) / h
+        d = at * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5) if pp else st * ((torch.exp(h) - 1.0 - h) / h ** 2 - 0.5)
+        return A, b, (f(1.0 / r0), f(first), pp, f(1.0 / r1), f(r0), f(r1), f(r0 - r1), f(d))
+
+    def step(self, model_output, timestep, sample, return_dict: bool = True):
+        self._require_steps()
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        m0 = self.convert_model_output(model_output, sample=sample)
+        self.model_outputs = self.model_outputs[1:] + [m0]
+        order = self._effective_order(self.model_outputs)
+        if order == 1:   # "for single-step solvers, we use the initial value at each time with order = 1"
+            self.sample = sample
+        A, b, terms = self._update_scalars(order)
+        base = self.model_outputs[-order]
+        prev = A * self.sample - b * base
+        if len(terms) == 3:
+            ri0, c, plus = terms
+            d1 = ri0 * (m0 - base)
+            prev = prev + c * d1 if plus else prev - c * d1
+        elif terms:
+            ri0, c, plus, ri1, r0, r1, r01, d = terms
+            d1_0, d1_1 = ri1 * (self.model_outputs[-2] - base), ri0 * (m0 - base)
+            d1 = (r0 * d1_0 - r1 * d1_1) / r01
+            d2 = 2.0 * (d1_1 - d1_0) / r01
+            prev = (prev + c * d1 if plus else prev - c * d1) - d * d2
+        self._last_order = order
+        self._step_index += 1
+        return _out(prev, return_dict)
+
+    def singlestep_coefficients(self, timestep) -> Tuple[float, ...]:
+        """This model evaluation as a linear map of the sample x the loop holds, the model output e, the parked sample S and the
+        converted outputs of the evaluation's group, ``base`` its first and m1 its second -> (p, q, A, B, E1, E2, order, keep):
+            m0   = p x + q e                                      (``convert_model_output``)
+            prev = A x + B m0                                     order 1; afterwards S = x and base = m0
+            prev = A S + B base + E1 (m0 - base)                  order 2; afterwards m1 = m0 where keep = 1.0 (order 3 follows)
+            prev = A S + B base + E1 (m0 - base) + E2 (m1 - base) order 3; E2 = 0.0 for "midpoint"
+        ``order`` is the EFFECTIVE order, after the reduction of ``step``. Advances ``_step_index``, ``model_outputs`` (placeholders
+        for the tensors) and ``sample`` as ``step`` does. The schedule values are ``_update_scalars``' and the alpha_t, sigma_t of
+        ``convert_model_output``, the very numbers ``step`` reads; the row is composed from them in float64.
+        An effective order k > 1 directly follows effective order k - 1: every order list is made of runs 1, 2, .. and the reduction
+        lowers an order to the number of outputs held, which is one more than it was an evaluation earlier. The device planes rely
+        on it (the parked sample and ``base`` are what the order-1 evaluation of the group left, m1 what its order-2 one left), so it
+        is checked here. NotImplementedError: that invariant broken, a history that holds tensors (``step`` has run on this
+        scheduler: the planes never saw them), thresholding switched on, a coefficient that is not finite; the step state is then
+        what it was before the call."""
+        self._require_steps()
+        fresh = self._step_index is None
+        if fresh:
+            self._init_step_index(timestep)
+        try:
+            return self._walk_row()
+        except NotImplementedError:
+            if fresh:
+                self._step_index = None
+            raise
+
+    def _walk_row(self):
+        cfg = self.config
+        if cfg.thresholding or cfg.prediction_type not in ("epsilon", "sample", "v_prediction"):
+            raise NotImplementedError("the fused form has no thresholding, and is for epsilon, sample or v prediction")
+        if any(m is not None and m is not _WALKED for m in self.model_outputs):
+            raise NotImplementedError("the history of this scheduler was not built by a coefficient walk")
+        have = self.model_outputs[1:] + [_WALKED]
+        order = self._effective_order(have)
+        if order > 1 and self._last_order != order - 1:
+            raise NotImplementedError(f"an order-{order} evaluation that does not follow an order-{order - 1} one")
+        p, q = _alpha_convert_pq(cfg.prediction_type, cfg.algorithm_type == "dpmsolver++", *self._alpha_sigma())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            A, b, terms = self._update_scalars(order)
+            E1 = E2 = 0.0
+            try:
+                if len(terms) == 3:
+                    ri0, c, plus = terms
+                    E1 = (c if plus else -c) * ri0
+                elif terms:
+                    ri0, c, plus, ri1, r0, r1, r01, d = terms
+                    sc = c if plus else -c
+                    E1 = (sc * (-r1 * ri0) - d * 2.0 * ri0) / r01
+                    E2 = (sc * (r0 * ri1) + d * 2.0 * ri1) / r01
+            except ZeroDivisionError:
+                E1 = float("nan")
+        nxt = self._step_index + 1
+        keep = float(order == 2 and nxt < len(self.order_list) and self.order_list[nxt] == 3)
+        row = (p, q, A, -b, E1, E2, float(order), keep)
+        if not all(map(isfinite, row)):
+            raise NotImplementedError("a singlestep coefficient of this evaluation is not finite")
+        self.model_outputs = have
+        if order == 1:
+            self.sample = _WALKED
+        self._last_order = order
+        self._step_index += 1
+        return row
 
 
 class FlowMatchEulerDiscreteScheduler:
