@@ -5,6 +5,8 @@ import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p, POINTER
 
+from . import step_forms
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # The library comes in two builds of the same sources (include/mi355x_sd.h, mi355x_sd_elem_dtype): bfloat16 elements
@@ -134,33 +136,7 @@ SIGNATURES = {
     "mi355x_sd_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355x_sd_mask_to_bias": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355x_sd_cfg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
-    # guidance rescale folded into the update (csrc/step_tail.hip, ABI 14)
-    "mi355x_sd_cfg_rescale_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int64,
-                                            c_void_p]),
-    # one DPM-Solver multistep step: guidance, rescale, convert_model_output, update and history (csrc/step_tail.hip, ABI 15)
-    "mi355x_sd_multistep_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                           c_int, c_int64, c_void_p]),
-    # one UniPC step: guidance, rescale, convert_model_output, corrector, predictor, last_sample and history (csrc/step_tail.hip, ABI 16)
-    "mi355x_sd_unipc_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float,
-                                       c_int, c_int64, c_void_p]),
-    # one ancestral step: guidance, rescale and prev = a x + b e + c noise (csrc/step_tail.hip, ABI 17)
-    "mi355x_sd_ancestral_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int64,
-                                           c_void_p]),
-    # one evaluation of a two-stage Heun step: guidance, rescale, the derivative, the update and the parked state (csrc/step_tail.hip, ABI 18)
-    "mi355x_sd_heun_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
-                                      c_int64, c_void_p]),
-    # one evaluation of a two-stage midpoint step (DPM2, DPM2 a): guidance, rescale, the derivative, the update [+ c noise] and the
-    # parked sample (csrc/step_tail.hip, ABI 19)
-    "mi355x_sd_dpm2_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
-                                      c_int64, c_void_p]),
-    # one evaluation of PLMS sampling (PNDMScheduler, skip_prk_steps): guidance, rescale, the history combination, the update, the
-    # ring of three model outputs and the parked sample (csrc/step_tail.hip, ABI 20)
-    "mi355x_sd_plms_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
-                                      c_int64, c_void_p]),
-    # one evaluation of DPM-Solver singlestep sampling (DPMSolverSinglestepScheduler): guidance, rescale, convert_model_output, the
-    # update, the parked sample and the group's two converted outputs (csrc/step_tail.hip, ABI 21)
-    "mi355x_sd_singlestep_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                            c_int, c_int64, c_void_p]),
+    # (the fused step tails of csrc/step_tail.hip, ABI 14 - 21: generated below from step_forms.FORMS)
     # seam B1: the whole UNet behind a handle (csrc/unet_exec.hip)
     "mi355x_sd_unet_create": (c_int, [c_char_p, POINTER(c_void_p)]),
     "mi355x_sd_unet_destroy": (c_int, [c_void_p]),
@@ -198,6 +174,7 @@ SIGNATURES = {
     "mi355x_sd_comm_all_gather": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "mi355x_sd_comm_destroy": (c_int, [c_void_p]),
 }
+SIGNATURES.update(("mi355x_sd_" + form.entry, step_forms.signature(form)) for form in step_forms.FORMS.values())
 
 _lib = None
 

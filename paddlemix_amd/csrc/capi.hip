@@ -90,6 +90,72 @@ static int check_ws(const void* ws, size_t bytes, const char* who) {
   return SD_OK;
 }
 
+// The argument rule of the step-tail entries (step_tail.hip), stated once: step_entry() checks a call against its operands and
+// launches. An entry names its operands in the header's order -- paddlemix_amd/step_forms.py holds the same row for the Python side,
+// tests/test_step_forms.py generates every refusal from it. Blocks write their part of the written spans while other blocks still read
+// the inputs, so a written span must not overlap another one, nor anything read -- except the read operand named by `same`, when the
+// two are one pointer: the same lane reads and then writes each element of such a pair. A null span (no guidance, no noise) overlaps
+// nothing. The range: batch > 0, per_sample >= 1 (>= 2 under the rescale), and batch * per_sample * planes * 4 bytes fit an int64_t
+// for the operand of the most planes; a span's length is meaningful only once the range has passed, and only then is it used.
+struct StepOperand {
+  const char* name;
+  const void* p;
+  int planes;      // the span is planes * batch * per_sample floats
+  bool written;
+  bool optional;   // may be null
+  int same;        // written: the index of the read operand it may be itself, or -1
+};
+static StepOperand reads(const char* name, const void* p, bool optional = false) { return {name, p, 1, false, optional, -1}; }
+static StepOperand writes(const char* name, const void* p, int planes = 1, int same = -1) { return {name, p, planes, true, false, same}; }
+struct StepCoef {
+  const float* p;
+  int floats, align;   // the row and the alignment its loads need, in bytes
+  bool overlaps;       // takes part in the overlap rule
+};
+
+// always_rescale (cfg_rescale_axpby): the rescale runs whatever guidance_rescale is, which goes to the launch as it came; otherwise
+// the launch gets 0 unless there is an eps_text to rescale by. launch(guidance_rescale) -> the launcher's status
+template <class Launch>
+static int step_entry(const char* who, std::initializer_list<StepOperand> operands, StepCoef coef, const float* eps_text,
+                      float guidance_rescale, bool always_rescale, int batch, int64_t per_sample, Launch launch) {
+  auto refuse = [who](const char* rule, const char* a = "", const char* b = "") {
+    snprintf(g_err, sizeof(g_err), rule, who, a, b);
+    return (int)SD_ERR_INVALID;
+  };
+  int planes = 1;
+  for (const StepOperand& o : operands) {
+    if (!o.p && !o.optional) return refuse("%s: null pointer (%s)", o.name);
+    planes = o.planes > planes ? o.planes : planes;
+  }
+  if (!coef.p) return refuse("%s: null pointer (%s)", "coef");
+  if ((uintptr_t)coef.p % (uintptr_t)coef.align) {
+    snprintf(g_err, sizeof(g_err), "%s: coef must be %d-byte aligned", who, coef.align);
+    return SD_ERR_INVALID;
+  }
+  const bool rescale = always_rescale || (eps_text && guidance_rescale > 0.0f);
+  if (batch <= 0 || per_sample < (rescale ? 2 : 1) || per_sample > INT64_MAX / 4 / planes / batch)
+    return refuse(always_rescale ? "%s: needs batch > 0 and per_sample >= 2 (the estimator divides by per_sample - 1)"
+                                 : "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by "
+                                   "per_sample - 1)");
+  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
+  auto overlap = [](const void* a, uintptr_t la, const void* b, uintptr_t lb) {
+    return a && b && (uintptr_t)a < (uintptr_t)b + lb && (uintptr_t)b < (uintptr_t)a + la;
+  };
+  for (const StepOperand* w = operands.begin(); w != operands.end(); ++w) {
+    if (!w->written) continue;
+    for (const StepOperand* v = operands.begin(); v != operands.end(); ++v) {
+      if (v == w || (v->written && v < w)) continue;   // (two written spans: seen from the earlier one)
+      const bool partner = w->same == v - operands.begin();
+      if (!(partner && w->p == v->p) && overlap(w->p, bytes * w->planes, v->p, bytes * v->planes))
+        return refuse(partner ? "%s: %s may be %s itself, but must not overlap it in any other way" : "%s: %s must not overlap %s",
+                      w->name, v->name);
+    }
+    if (coef.overlaps && overlap(w->p, bytes * w->planes, coef.p, coef.floats * sizeof(float)))
+      return refuse("%s: %s must not overlap %s", w->name, "coef");
+  }
+  return finish(launch(rescale ? guidance_rescale : 0.0f), who);
+}
+
 extern "C" {
 
 int mi355x_sd_abi_version(void) { return MI355X_SD_ABI_VERSION; }
@@ -584,166 +650,93 @@ int mi355x_sd_cfg_axpby(const float* x, const float* eps_uncond, const float* ep
   return finish(launch_cfg_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, (long)n, S(stream)), "mi355x_sd_cfg_axpby");
 }
 
-// The argument rule of the step-tail entries (step_tail.hip). Blocks write their part of the `written` spans while other blocks still
-// read the inputs, so a written span must not overlap another one, nor anything read -- except a pair named in `same`, when the two
-// are one pointer: the same lane reads and then writes each element of such a pair. A null span (no guidance, no noise) overlaps
-// nothing. The range: batch > 0, per_sample >= min_per_sample, and batch * per_sample * planes * 4 bytes fit an int64_t (planes:
-// UniPC's history). `bytes` of the callers is meaningful only once the range has passed, and only then is it used.
-struct Span {
-  const void* p;
-  uintptr_t len;
-};
-struct SamePair {   // written[w] may be read[r] itself
-  int w, r;
-};
-static int check_step_args(const char* who, int batch, int64_t per_sample, int min_per_sample, int planes, const char* range_rule,
-                           std::initializer_list<Span> written, std::initializer_list<Span> read,
-                           std::initializer_list<SamePair> same, const char* overlap_rule) {
-  if (batch <= 0 || per_sample < min_per_sample || per_sample > INT64_MAX / 4 / planes / batch) return fail(SD_ERR_INVALID, range_rule, who);
-  auto overlaps = [](const Span& a, const Span& b) {
-    return a.p && b.p && (uintptr_t)a.p < (uintptr_t)b.p + b.len && (uintptr_t)b.p < (uintptr_t)a.p + a.len;
-  };
-  bool bad = false;
-  for (const Span* w = written.begin(); w != written.end(); ++w) {
-    for (const Span* v = w + 1; v != written.end(); ++v) bad = bad || overlaps(*w, *v);
-    for (const Span* r = read.begin(); r != read.end(); ++r) {
-      bool allowed = false;
-      for (const SamePair& s : same) allowed = allowed || (s.w == w - written.begin() && s.r == r - read.begin() && w->p == r->p);
-      bad = bad || (!allowed && overlaps(*w, *r));
-    }
-  }
-  return bad ? fail(SD_ERR_INVALID, overlap_rule, who) : SD_OK;
-}
-static const char* const STEP_RANGE_RULE =
-    "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by per_sample - 1)";
-
+// ---- the step-tail entries (step_tail.hip): each is one call of step_entry(), defined before the extern "C" block ----
 int mi355x_sd_cfg_rescale_axpby(const float* x, const float* eps_uncond, const float* eps_text, float* out, const float* coef,
                                 float guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream) {
-  const char* who = "mi355x_sd_cfg_rescale_axpby";
-  if (!x || !eps_uncond || !eps_text || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, 2, 1, "%s: needs batch > 0 and per_sample >= 2 (the estimator divides by per_sample - 1)",
-                               {{out, bytes}}, {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}}, {{0, 0}},
-                               "%s: out may be x itself, but must not overlap x in any other way, nor eps_uncond / eps_text"))
-    return rc;
-  return finish(launch_cfg_rescale_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, guidance_rescale, batch, (long)per_sample,
-                                         S(stream)), who);
+  return step_entry("mi355x_sd_cfg_rescale_axpby", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text),
+                                                    writes("out", out, 1, 0)},
+                    {coef, 2, 1, false}, eps_text, guidance_rescale, true, batch, per_sample, [&](float gr) {
+                      return launch_cfg_rescale_axpby(x, eps_uncond, eps_text, out, coef, guidance_scale, gr, batch, (long)per_sample,
+                                                      S(stream));
+                    });
 }
 
 int mi355x_sd_multistep_update(const float* x, const float* eps_uncond, const float* eps_text, const float* m_prev, float* out,
                                float* m_out, const float* coef, float guidance_scale, float guidance_rescale, int batch,
                                int64_t per_sample, void* stream) {
-  const char* who = "mi355x_sd_multistep_update";
-  if (!x || !eps_uncond || !m_prev || !out || !m_out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {m_out, bytes}},
-                               {{x, bytes}, {m_prev, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 5 * sizeof(float)}},
-                               {{0, 0}, {1, 1}},
-                               "%s: out may be x itself and m_out may be m_prev itself; out and m_out must not overlap each other, "
-                               "the inputs or coef in any other way"))
-    return rc;
-  return finish(launch_multistep_update(x, eps_uncond, eps_text, m_prev, out, m_out, coef, guidance_scale,
-                                        rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_multistep_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                                   reads("m_prev", m_prev), writes("out", out, 1, 0), writes("m_out", m_out, 1, 3)},
+                    {coef, 5, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_multistep_update(x, eps_uncond, eps_text, m_prev, out, m_out, coef, guidance_scale, gr, batch,
+                                                     (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_unipc_update(const float* x, const float* eps_uncond, const float* eps_text, float* last, float* hist, int order,
                            float* out, const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                            void* stream) {
-  const char* who = "mi355x_sd_unipc_update";
-  if (!x || !eps_uncond || !last || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  if (order < 1 || order > 3) return fail(SD_ERR_INVALID, "%s: order must be 1, 2 or 3 (the planes of hist)", who);
-  if ((uintptr_t)coef & 15) return fail(SD_ERR_INVALID, "%s: coef must be 16-byte aligned", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, order, STEP_RANGE_RULE,
-                               {{out, bytes}, {last, bytes}, {hist, bytes * (uintptr_t)order}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 12 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; out, last and hist must not overlap each other, the inputs or coef in any "
-                               "other way"))
-    return rc;
-  return finish(launch_unipc_update(x, eps_uncond, eps_text, last, hist, order, out, coef, guidance_scale,
-                                    rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+  if (order < 1 || order > 3) return fail(SD_ERR_INVALID, "%s: order must be 1, 2 or 3 (the planes of hist)", "mi355x_sd_unipc_update");
+  return step_entry("mi355x_sd_unipc_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                               writes("last", last), writes("hist", hist, order), writes("out", out, 1, 0)},
+                    {coef, 12, 16, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_unipc_update(x, eps_uncond, eps_text, last, hist, order, out, coef, guidance_scale, gr, batch,
+                                                 (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_ancestral_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* out,
                                const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                                void* stream) {
-  const char* who = "mi355x_sd_ancestral_update";
-  if (!x || !eps_uncond || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);   // (noise: see the header)
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {noise, bytes}, {coef, 3 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; it must not overlap x in any other way, nor eps_uncond, eps_text, noise or "
-                               "coef"))
-    return rc;
-  return finish(launch_ancestral_update(x, eps_uncond, eps_text, noise, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
-                                        batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_ancestral_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                                   reads("noise", noise, true), writes("out", out, 1, 0)},   // (noise: see the header)
+                    {coef, 3, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_ancestral_update(x, eps_uncond, eps_text, noise, out, coef, guidance_scale, gr, batch,
+                                                     (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_heun_update(const float* x, const float* eps_uncond, const float* eps_text, float* sample, float* deriv, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream) {
-  const char* who = "mi355x_sd_heun_update";
-  if (!x || !eps_uncond || !sample || !deriv || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {sample, bytes}, {deriv, bytes}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 5 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; out, sample and deriv must not overlap each other, the inputs or coef in any "
-                               "other way"))
-    return rc;
-  return finish(launch_heun_update(x, eps_uncond, eps_text, sample, deriv, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
-                                   batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_heun_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                              writes("sample", sample), writes("deriv", deriv), writes("out", out, 1, 0)},
+                    {coef, 5, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_heun_update(x, eps_uncond, eps_text, sample, deriv, out, coef, guidance_scale, gr, batch,
+                                                (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_dpm2_update(const float* x, const float* eps_uncond, const float* eps_text, const float* noise, float* sample, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream) {
-  const char* who = "mi355x_sd_dpm2_update";
-  if (!x || !eps_uncond || !sample || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);   // (noise: see the header)
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 1, STEP_RANGE_RULE, {{out, bytes}, {sample, bytes}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {noise, bytes}, {coef, 5 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; out and sample must not overlap each other, the inputs, noise or coef in any "
-                               "other way"))
-    return rc;
-  return finish(launch_dpm2_update(x, eps_uncond, eps_text, noise, sample, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
-                                   batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_dpm2_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                              reads("noise", noise, true), writes("sample", sample), writes("out", out, 1, 0)},
+                    {coef, 5, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {   // (noise: see the header)
+                      return launch_dpm2_update(x, eps_uncond, eps_text, noise, sample, out, coef, guidance_scale, gr, batch,
+                                                (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_plms_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
                           const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                           void* stream) {
-  const char* who = "mi355x_sd_plms_update";
-  if (!x || !eps_uncond || !park || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 3, STEP_RANGE_RULE, {{out, bytes}, {park, bytes}, {hist, bytes * 3}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 12 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; out, park and the three planes of hist must not overlap each other, the "
-                               "inputs or coef in any other way"))
-    return rc;
-  return finish(launch_plms_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale, rescale ? guidance_rescale : 0.0f,
-                                   batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_plms_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                              writes("park", park), writes("hist", hist, 3), writes("out", out, 1, 0)},
+                    {coef, 12, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_plms_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale, gr, batch,
+                                                (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_singlestep_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
                                 const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                                 void* stream) {
-  const char* who = "mi355x_sd_singlestep_update";
-  if (!x || !eps_uncond || !park || !hist || !out || !coef) return fail(SD_ERR_INVALID, "%s: null pointer", who);
-  const bool rescale = eps_text && guidance_rescale > 0.0f;
-  const uintptr_t bytes = (uintptr_t)batch * (uintptr_t)per_sample * 4;
-  if (int rc = check_step_args(who, batch, per_sample, rescale ? 2 : 1, 2, STEP_RANGE_RULE, {{out, bytes}, {park, bytes}, {hist, bytes * 2}},
-                               {{x, bytes}, {eps_uncond, bytes}, {eps_text, bytes}, {coef, 8 * sizeof(float)}}, {{0, 0}},
-                               "%s: out may be x itself; out, park and the two planes of hist must not overlap each other, the "
-                               "inputs or coef in any other way"))
-    return rc;
-  return finish(launch_singlestep_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale,
-                                         rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream)), who);
+  return step_entry("mi355x_sd_singlestep_update", {reads("x", x), reads("eps_uncond", eps_uncond), reads("eps_text", eps_text, true),
+                                                    writes("park", park), writes("hist", hist, 2), writes("out", out, 1, 0)},
+                    {coef, 8, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
+                      return launch_singlestep_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale, gr, batch,
+                                                      (long)per_sample, S(stream));
+                    });
 }
 
 int mi355x_sd_graph_begin(void* stream) {

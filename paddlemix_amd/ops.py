@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import GEGLU, GELU_TANH, OUT_F32, SILU, check
+from .step_forms import FORMS
 
 Tensor = torch.Tensor
 
@@ -330,28 +331,46 @@ def axpby(x: Tensor, y: Tensor, coef: Tensor, out: Optional[Tensor] = None) -> T
     return out
 
 
-def _step_args(x: Tensor, same_shape, coef: Tensor, width: int, coef_error: str, rescale: bool, always_rescale: bool = False,
-               coef_align: int = 1) -> None:
-    """The checks the step-tail wrappers share. x: contiguous fp32 GPU [B, ...], non-empty, with at least 2 elements per sample under
-    the guidance rescale; same_shape: (tensor, name, may_be_none) triples, each like x; coef: contiguous fp32 GPU with at least
-    `width` values at a multiple of coef_align bytes (coef_error: the form's own text)"""
+def _step(form, a, coef_error: str, required=()):
+    """One fused step-tail entry, `form` its row of step_forms.FORMS, `a` its wrapper's ``locals()``: the tensors by the row's operand
+    names, guidance_scale and guidance_rescale. The checks the wrappers share -- x: contiguous fp32 GPU [B, ...], non-empty, with at
+    least 2 elements per sample under the guidance rescale; every other one-plane operand like x (None: a null pointer where the row
+    allows one and `required` does not name it; a new plane for a written one that is not the caller's state); coef: contiguous fp32
+    GPU with the row's width at the row's alignment (coef_error: the form's own text); an operand of several planes: [planes, B, ...]
+    (``order`` = its planes where the row leaves them open) -- then the launch -> the written planes that are not the caller's state"""
+    lib = _lib.load()
+    x, coef, gr = a["x"], a["coef"], a["guidance_rescale"]
     _flat_f32(x, "x")
-    if always_rescale:
+    if form.always_rescale:
         if x.dim() < 2 or x.shape[0] < 1 or x.numel() // x.shape[0] < 2:
             raise ValueError(f"x: expected [B, ...] with at least 2 elements per sample, got {tuple(x.shape)}")
     elif x.dim() < 2 or x.shape[0] < 1 or x.numel() < 1:
         raise ValueError(f"x: expected a non-empty [B, ...], got {tuple(x.shape)}")
-    elif rescale and x.numel() // x.shape[0] < 2:
+    elif a["eps_text"] is not None and gr > 0.0 and x.numel() // x.shape[0] < 2:
         raise ValueError(f"x: guidance_rescale needs at least 2 elements per sample, got {tuple(x.shape)}")
-    for t, name, may_be_none in same_shape:
-        if t is None and may_be_none:
+    many = {k: planes for k, planes in form.written.items() if planes != 1}
+    results = [k for k in form.written if k not in form.state]
+    for k in form.operands:
+        t = a.get(k)
+        if k in ("x", "coef", "order") or k in many or (t is None and (k in results or (k in form.optional and k not in required))):
             continue
-        _flat_f32(t, name, x.numel())
-        if t.shape != x.shape:
-            raise ValueError(f"{name}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
-    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < width or \
-            not coef.is_contiguous() or coef.data_ptr() % coef_align:
+        _flat_f32(t, k, x.numel())
+        if t.shape != x.shape and not (form.always_rescale and k in results):   # (the guidance form takes any `out` of x's size)
+            raise ValueError(f"{k}: expected shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if not isinstance(coef, torch.Tensor) or not coef.is_cuda or coef.dtype != torch.float32 or coef.numel() < form.width or \
+            not coef.is_contiguous() or coef.data_ptr() % form.align:
         raise ValueError(coef_error)
+    a = dict(a)
+    for k, planes in many.items():
+        t, want = a[k], (1, 2, 3) if planes is None else (planes,)
+        if not isinstance(t, torch.Tensor) or t.dim() != x.dim() + 1 or t.shape[0] not in want or t.shape[1:] != x.shape:
+            raise ValueError(f"{k}: expected [{planes or 'order'}, {', '.join(map(str, x.shape))}]" + ("" if planes else " with order 1-3"))
+        _flat_f32(t, k)
+        a["order"] = t.shape[0]
+    a.update((k, torch.empty_like(x)) for k in results if a[k] is None)
+    check(getattr(lib, "mi355x_sd_" + form.entry)(*(a[k] if k == "order" else _p(a[k]) for k in form.operands), float(a["guidance_scale"]),
+                                                  float(gr), x.shape[0], x.numel() // x.shape[0], _stream()))
+    return a[results[0]] if len(results) == 1 else tuple(a[k] for k in results)
 
 
 def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Tensor, guidance_scale: float,
@@ -360,17 +379,7 @@ def cfg_rescale_axpby(x: Tensor, eps_uncond: Tensor, eps_text: Tensor, coef: Ten
     eps_text: contiguous fp32 [B, ...] of one shape with at least 2 elements per sample; with c = eps_uncond + guidance_scale *
     (eps_text - eps_uncond) and r[s] = std(eps_text[s]) / std(c[s]) over everything but the batch axis,
     out = coef[0] * x + coef[1] * c * (guidance_rescale * r[s] + 1 - guidance_rescale). out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", False)), coef, 2,
-               "coef: expected a contiguous fp32 GPU tensor (a, b)", True, always_rescale=True)
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _flat_f32(out, "out", x.numel())
-    check(lib.mi355x_sd_cfg_rescale_axpby(x.data_ptr(), eps_uncond.data_ptr(), eps_text.data_ptr(), out.data_ptr(), coef.data_ptr(),
-                                          float(guidance_scale), float(guidance_rescale), x.shape[0], x.numel() // x.shape[0],
-                                          _stream()))
-    return out
+    return _step(FORMS["guidance"], locals(), "coef: expected a contiguous fp32 GPU tensor (a, b)")
 
 
 def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], m_prev: Tensor, coef: Tensor, guidance_scale: float,
@@ -379,16 +388,7 @@ def multistep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     fp32 [B, ...] of one shape; coef: fp32 GPU (p, q, A, B, D) of ``DPMSolverMultistepScheduler.multistep_coefficients``. With e
     the guided (and, with guidance_rescale > 0, rescaled) model output: m_out = p x + q e, out = A x + B m_out + D (m_out - m_prev);
     D == 0 does not read m_prev. out may be x and m_out may be m_prev."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (m_prev, "m_prev", False), (out, "out", True),
-                   (m_out, "m_out", True)), coef, 5, "coef: expected a contiguous fp32 GPU tensor (p, q, A, B, D)",
-               eps_text is not None and guidance_rescale > 0.0)
-    out = torch.empty_like(x) if out is None else out
-    m_out = torch.empty_like(x) if m_out is None else m_out
-    check(lib.mi355x_sd_multistep_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), m_prev.data_ptr(), out.data_ptr(),
-                                         m_out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale),
-                                         x.shape[0], x.numel() // x.shape[0], _stream()))
-    return out, m_out
+    return _step(FORMS["multistep"], locals(), "coef: expected a contiguous fp32 GPU tensor (p, q, A, B, D)")
 
 
 def ancestral_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise: Tensor, coef: Tensor, guidance_scale: float,
@@ -397,14 +397,7 @@ def ancestral_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], 
     [B, ...] of one shape; coef: fp32 GPU (a, b, c) of ``EulerAncestralDiscreteScheduler.ancestral_coefficients``. With e the guided
     (and, with guidance_rescale > 0, rescaled) model output: out = a x + b e + c noise; c == 0 does not read noise (the C entry takes a
     null plane for such a row; this wrapper always wants a real one). out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (noise, "noise", False), (out, "out", True)),
-               coef, 3, "coef: expected a contiguous fp32 GPU tensor (a, b, c)", eps_text is not None and guidance_rescale > 0.0)
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_ancestral_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), noise.data_ptr(), out.data_ptr(),
-                                         coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
-                                         x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["ancestral"], locals(), "coef: expected a contiguous fp32 GPU tensor (a, b, c)", required=("noise",))
 
 
 def heun_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], sample: Tensor, deriv: Tensor, coef: Tensor,
@@ -414,15 +407,7 @@ def heun_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], sampl
     [B, ...] of one shape; coef: fp32 GPU (p, q, h, g, second) of ``HeunDiscreteScheduler.heun_coefficients``. With e the guided
     (and, with guidance_rescale > 0, rescaled) model output and d = p x + q e: second == 0: out = x + h d, S = x, D = d (neither is
     read); second != 0: out = S + h (g D + d) (g == 0 does not read D; neither is written). out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (sample, "sample", False),
-                   (deriv, "deriv", False), (out, "out", True)), coef, 5,
-               "coef: expected a contiguous fp32 GPU tensor (p, q, h, g, second)", eps_text is not None and guidance_rescale > 0.0)
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_heun_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), sample.data_ptr(), deriv.data_ptr(),
-                                    out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
-                                    x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["heun"], locals(), "coef: expected a contiguous fp32 GPU tensor (p, q, h, g, second)")
 
 
 def dpm2_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise: Optional[Tensor], sample: Tensor, coef: Tensor,
@@ -432,15 +417,7 @@ def dpm2_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], noise
     sample: contiguous fp32 [B, ...] of one shape; coef: fp32 GPU (p, q, h, c, second) of ``dpm2_coefficients``. With e the guided
     (and, with guidance_rescale > 0, rescaled) model output and d = p x + q e: second == 0: out = x + h d, S = x (neither S nor noise
     is read); second != 0: out = S + h d + c noise (c == 0 does not read noise; S is not written). out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (noise, "noise", True), (sample, "sample", False),
-                   (out, "out", True)), coef, 5,
-               "coef: expected a contiguous fp32 GPU tensor (p, q, h, c, second)", eps_text is not None and guidance_rescale > 0.0)
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_dpm2_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), _p(noise), sample.data_ptr(), out.data_ptr(),
-                                    coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
-                                    x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["dpm2"], locals(), "coef: expected a contiguous fp32 GPU tensor (p, q, h, c, second)")
 
 
 def plms_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park: Tensor, hist: Tensor, coef: Tensor,
@@ -452,18 +429,7 @@ def plms_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park:
     output and h_k = hist[(slot - k) % 3]: m = w0 e + w1 h1 + w2 h2 + w3 h3, S = P if from_park else x, m = p S + q m if p != 0,
     out = a S + b m; then hist[slot] = e unless from_park, and P = x if park. A term with a zero weight does not read its plane, and
     only one of x and P is read. out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (park, "park", False), (out, "out", True)),
-               coef, 12, "coef: expected a contiguous fp32 GPU tensor of the 12 values of a PLMS row",
-               eps_text is not None and guidance_rescale > 0.0)
-    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] != 3 or hist.shape[1:] != x.shape:
-        raise ValueError(f"hist: expected [3, {', '.join(map(str, x.shape))}]")
-    _flat_f32(hist, "hist")
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_plms_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), park.data_ptr(), hist.data_ptr(),
-                                    out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
-                                    x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["plms"], locals(), "coef: expected a contiguous fp32 GPU tensor of the 12 values of a PLMS row")
 
 
 def singlestep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], park: Tensor, hist: Tensor, coef: Tensor,
@@ -475,18 +441,7 @@ def singlestep_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor],
     (and, with guidance_rescale > 0, rescaled) model output, m0 = p x + q e and b = hist[0]: order 1: out = A x + B m0, then S = x and
     hist[0] = m0; order 2: out = A S + B b + E1 (m0 - b), then hist[1] = m0 if keep; order 3: the same plus E2 (hist[1] - b) where
     E2 != 0. State a row does not use is not read. out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (park, "park", False), (out, "out", True)),
-               coef, 8, "coef: expected a contiguous fp32 GPU tensor of the 8 values of a singlestep row",
-               eps_text is not None and guidance_rescale > 0.0)
-    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] != 2 or hist.shape[1:] != x.shape:
-        raise ValueError(f"hist: expected [2, {', '.join(map(str, x.shape))}]")
-    _flat_f32(hist, "hist")
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_singlestep_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), park.data_ptr(), hist.data_ptr(),
-                                          out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale), x.shape[0],
-                                          x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["singlestep"], locals(), "coef: expected a contiguous fp32 GPU tensor of the 8 values of a singlestep row")
 
 
 def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last: Tensor, hist: Tensor, coef: Tensor,
@@ -498,18 +453,7 @@ def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last
     m_t = p x + q e, x_c = Ac L + Bc h1 + C2 (h2 - h1) + C3 (h3 - h1) + Ct (m_t - h1) (corr == 0: x_c = x),
     out = Ap x_c + Bp m_t + D1 (h1 - m_t) + D2 (h2 - m_t); then last = x_c and hist = [m_t, h1, h2][:order]. A term with a zero
     coefficient does not read its operand. out may be x."""
-    lib = _lib.load()
-    _step_args(x, ((eps_uncond, "eps_uncond", False), (eps_text, "eps_text", True), (last, "last", False), (out, "out", True)),
-               coef, 12, "coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients",
-               eps_text is not None and guidance_rescale > 0.0, coef_align=16)
-    if not isinstance(hist, torch.Tensor) or hist.dim() != x.dim() + 1 or hist.shape[0] not in (1, 2, 3) or hist.shape[1:] != x.shape:
-        raise ValueError(f"hist: expected [order, {', '.join(map(str, x.shape))}] with order 1-3")
-    _flat_f32(hist, "hist")
-    out = torch.empty_like(x) if out is None else out
-    check(lib.mi355x_sd_unipc_update(x.data_ptr(), eps_uncond.data_ptr(), _p(eps_text), last.data_ptr(), hist.data_ptr(),
-                                     hist.shape[0], out.data_ptr(), coef.data_ptr(), float(guidance_scale), float(guidance_rescale),
-                                     x.shape[0], x.numel() // x.shape[0], _stream()))
-    return out
+    return _step(FORMS["unipc"], locals(), "coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients")
 
 
 def probe_layouts(device="cuda") -> Tensor:

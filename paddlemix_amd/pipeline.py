@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, program
+from .step_forms import FORMS
 
 
 def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
@@ -51,25 +52,43 @@ class _GenericTail:
 class _FusedTail:
     """Guidance combine (+ rescale) and scheduler update as ONE device pass over the latents on the caller's stream, coefficients in a
     device table. Not through paddlemix_amd.ops: its wrappers refuse the emulator's host tensors and validate every call.
-    A subclass is one row of _TAILS: it names the scheduler method whose rows it runs and the library entry it needs."""
+    A subclass is one row of _TAILS and names its ``form``, a row of step_forms.FORMS: the scheduler method whose rows it runs, the
+    library entry it needs with its operands, the state it owns and the noise it draws."""
 
+    form = None              # the row; the four below are read from it
     walk = None              # the scheduler method that gives a step's coefficient row
     whole_schedule = False   # a row depends on the steps before it: the walk covers the timesteps the loop RUNS. True: a stateless
     #                          row, walked over the scheduler's WHOLE schedule together with its model_input_scale
     entry = None             # the library entry every step needs (a test backend from before it keeps the generic path)
     rescale_entry = None     # ... and the one it needs instead under the guidance rescale
 
-    def __init__(self, lib, emulated, coef, scales=None):
-        self.lib, self.emulated, self.coef, self.scales, self.history = lib, emulated, coef, scales, None
+    def __init_subclass__(cls):
+        """what the row alone decides, once per class: the attributes above and where each operand sits in the call"""
+        form, at = cls.form, {k: n for n, k in enumerate(cls.form.operands)}
+        cls.symbol = "mi355x_sd_" + form.entry
+        cls.walk, cls.whole_schedule = form.walk, form.whole_schedule
+        cls.entry, cls.rescale_entry = (None, cls.symbol) if form.always_rescale else (cls.symbol, None)
+        cls.stride = 4 * form.width   # bytes of a row
+        cls.at_out, cls.at_coef, cls.at_noise, cls.at_order = at["out"], at["coef"], at.get("noise"), at.get("order")
+        cls.owned = [(k, at[k], planes) for k, planes in form.state.items()]
+        # a written operand the tail owns through the read one it may be itself (multistep: m_out is m_prev's plane)
+        cls.shared = [(at[w], at[r]) for w, r in form.same if r in form.state]
+        cls.blank = [None] * (len(at) + 5)   # the operands, then guidance_scale, guidance_rescale, batch, per_sample, stream
 
-    @classmethod
-    def build(cls, lib, emulated, coef, scales, scheduler, generator):
-        return cls(lib, emulated, coef, scales)
+    def __init__(self, lib, emulated, coef, scales, scheduler, generator):
+        self.lib, self.emulated, self.coef, self.scales, self.generator = lib, emulated, coef, scales, generator
+        self.order = None if self.at_order is None else scheduler.config.solver_order
+        self.noisy = self.form.noise == "fresh" or \
+            (self.form.noise == "reused" and "generator" in inspect.signature(scheduler.step).parameters)
+        self.noise = self.args = None
 
     def scale(self, x, i, t):
         return x if self.scales is None else x * self.scales[i]
 
     def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
+        if self.noisy:   # the ``torch.randn`` call of the scheduler's ``step``, from the call's generator: one seed, the same noise
+            self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32,
+                                     out=self.noise if self.form.noise == "reused" else None)
         lat = latents.contiguous()
         out = torch.empty_like(lat)
         eps = noise_pred.data_ptr()
@@ -77,15 +96,42 @@ class _FusedTail:
                                float(guidance_rescale), program.caller_stream(self.coef.device, self.emulated)))
         return out
 
+    def _first(self, lat, i):
+        """What no step changes, on the first one: the entry, the state the tail owns (never initialised: the first row reads none of
+        it), the address of row 0 and the call's arguments in the row's operand order with the state's pointers, ``order``, batch and
+        per_sample in place -- a step fills in the rest"""
+        a, self.state = list(self.blank), {}
+        for k, at, planes in self.owned:
+            t = self.state[k] = torch.empty_like(lat) if planes == 1 else lat.new_empty((planes or self.order,) + tuple(lat.shape))
+            a[at] = t.data_ptr()
+        for w, r in self.shared:
+            a[w] = a[r]
+        if self.order:
+            a[self.at_order] = self.order
+        a[-3], a[-2] = lat.shape[0], lat.numel() // lat.shape[0]
+        self.row0 = self.coef.data_ptr() - (0 if self.whole_schedule else self.stride * i)
+        self.fn, self.args = getattr(self.lib, self.symbol), a
+
+    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
+        if self.args is None:
+            self._first(lat, i)
+        a = self.args
+        a[0], a[1], a[2] = lat.data_ptr(), eps, eps_text   # (every form starts with x, eps_uncond, eps_text)
+        a[self.at_out], a[self.at_coef] = out.data_ptr(), self.row0 + self.stride * i
+        if self.noisy:
+            a[self.at_noise] = self.noise.data_ptr()
+        a[-5], a[-4], a[-1] = gs, gr, stream
+        return self.fn(*a)
+
 
 class _LinearTail(_FusedTail):
     """``step_coefficients`` (DDIM at eta = 0, Euler; epsilon and v prediction): prev = a * x + b * model_output, (a, b) = row i of a
     table [steps, 2] over the scheduler's WHOLE schedule; ``scales``: that schedule's model-input scales"""
 
-    walk, whole_schedule, rescale_entry = "step_coefficients", True, "mi355x_sd_cfg_rescale_axpby"
+    form = FORMS["guidance"]
 
     def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        n, cp = lat.numel(), self.coef.data_ptr() + 8 * i
+        n, cp = lat.numel(), self.coef.data_ptr() + self.stride * i
         if gr > 0.0:
             return self.lib.mi355x_sd_cfg_rescale_axpby(lat.data_ptr(), eps, eps_text, out.data_ptr(), cp, gs, gr, lat.shape[0],
                                                         n // lat.shape[0], stream)
@@ -98,15 +144,7 @@ class _MultistepTail(_FusedTail):
     """``multistep_coefficients`` (DPM-Solver multistep): convert_model_output and the history shuffle ride in the same launch;
     (p, q, A, B, D) = row i - first of a table [steps, 5] over the steps the loop RUNS (img2img starts inside the schedule)"""
 
-    walk, entry = "multistep_coefficients", "mi355x_sd_multistep_update"
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:   # the previous step's converted model output, fp32; row 0 has D = 0: a fresh one is not read
-            self.history, self.first = torch.empty_like(lat), i
-        h = self.history.data_ptr()
-        return self.lib.mi355x_sd_multistep_update(lat.data_ptr(), eps, eps_text, h, out.data_ptr(), h,
-                                                   self.coef.data_ptr() + 20 * (i - self.first), gs, gr, lat.shape[0],
-                                                   lat.numel() // lat.shape[0], stream)
+    form = FORMS["multistep"]
 
 
 class _UniPCTail(_FusedTail):
@@ -114,22 +152,7 @@ class _UniPCTail(_FusedTail):
     the same launch; the 12 coefficients = row i - first of a table [steps, 12] over the steps the loop RUNS. The tail owns ``last``
     and the ``order`` planes of ``hist``; the first row forms no term that reads them, so fresh ones are not initialised"""
 
-    walk, entry = "unipc_coefficients", "mi355x_sd_unipc_update"
-
-    def __init__(self, lib, emulated, coef, order):
-        super().__init__(lib, emulated, coef)
-        self.order, self.last = order, None
-
-    @classmethod
-    def build(cls, lib, emulated, coef, scales, scheduler, generator):
-        return cls(lib, emulated, coef, scheduler.config.solver_order)
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:
-            self.history, self.last, self.first = lat.new_empty((self.order,) + tuple(lat.shape)), torch.empty_like(lat), i
-        return self.lib.mi355x_sd_unipc_update(lat.data_ptr(), eps, eps_text, self.last.data_ptr(), self.history.data_ptr(), self.order,
-                                               out.data_ptr(), self.coef.data_ptr() + 48 * (i - self.first), gs, gr, lat.shape[0],
-                                               lat.numel() // lat.shape[0], stream)
+    form = FORMS["unipc"]
 
 
 class _AncestralTail(_FusedTail):
@@ -138,24 +161,7 @@ class _AncestralTail(_FusedTail):
     scheduler's ``step`` from the call's generator -- one seed gives the same noise on both paths -- and the launch reads it; the last
     row has c = 0 and its plane is drawn (the generator advances as in ``step``) but not read"""
 
-    walk, whole_schedule, entry = "ancestral_coefficients", True, "mi355x_sd_ancestral_update"
-
-    def __init__(self, lib, emulated, coef, scales, generator):
-        super().__init__(lib, emulated, coef, scales)
-        self.generator, self.noise = generator, None
-
-    @classmethod
-    def build(cls, lib, emulated, coef, scales, scheduler, generator):
-        return cls(lib, emulated, coef, scales, generator)
-
-    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
-        self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32)
-        return super().update(latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale)
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        return self.lib.mi355x_sd_ancestral_update(lat.data_ptr(), eps, eps_text, self.noise.data_ptr(), out.data_ptr(),
-                                                   self.coef.data_ptr() + 12 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0],
-                                                   stream)
+    form = FORMS["ancestral"]
 
 
 class _HeunTail(_FusedTail):
@@ -164,14 +170,7 @@ class _HeunTail(_FusedTail):
     owns the step's parked sample and derivative; stage 1 writes them without reading, so fresh ones are not initialised, and their
     pointers stay fixed for the whole loop"""
 
-    walk, whole_schedule, entry = "heun_coefficients", True, "mi355x_sd_heun_update"
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:
-            self.history = (torch.empty_like(lat), torch.empty_like(lat))
-        sample, deriv = self.history
-        return self.lib.mi355x_sd_heun_update(lat.data_ptr(), eps, eps_text, sample.data_ptr(), deriv.data_ptr(), out.data_ptr(),
-                                              self.coef.data_ptr() + 20 * i, gs, gr, lat.shape[0], lat.numel() // lat.shape[0], stream)
+    form = FORMS["heun"]
 
 
 class _Dpm2Tail(_FusedTail):
@@ -183,30 +182,7 @@ class _Dpm2Tail(_FusedTail):
     evaluation the draw goes into the same buffer (``out=``: the same values, the same generator state), so the noise pointer stays
     fixed too. Only the stage-2 rows read the plane. DPM2 draws nothing and passes a null noise (c = 0 on every row)"""
 
-    walk, whole_schedule, entry = "dpm2_coefficients", True, "mi355x_sd_dpm2_update"
-
-    def __init__(self, lib, emulated, coef, scales, noisy, generator):
-        super().__init__(lib, emulated, coef, scales)
-        self.noisy, self.generator, self.noise = noisy, generator, None
-
-    @classmethod
-    def build(cls, lib, emulated, coef, scales, scheduler, generator):
-        return cls(lib, emulated, coef, scales, "generator" in inspect.signature(scheduler.step).parameters, generator)
-
-    def update(self, latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale):
-        if self.noisy:
-            if self.noise is None:
-                self.noise = torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32)
-            else:
-                torch.randn(latents.shape, generator=self.generator, device=latents.device, dtype=torch.float32, out=self.noise)
-        return super().update(latents, noise_pred, i, t, do_cfg, guidance_scale, guidance_rescale)
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:
-            self.history = torch.empty_like(lat)
-        return self.lib.mi355x_sd_dpm2_update(lat.data_ptr(), eps, eps_text, self.noise.data_ptr() if self.noisy else None,
-                                              self.history.data_ptr(), out.data_ptr(), self.coef.data_ptr() + 20 * i, gs, gr,
-                                              lat.shape[0], lat.numel() // lat.shape[0], stream)
+    form = FORMS["dpm2"]
 
 
 class _PlmsTail(_FusedTail):
@@ -216,14 +192,7 @@ class _PlmsTail(_FusedTail):
     reads neither and every later one only what an earlier launch wrote, so fresh ones are not initialised, no plane is ever copied
     and their pointers stay fixed for the whole loop"""
 
-    walk, entry = "plms_coefficients", "mi355x_sd_plms_update"
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:
-            self.history, self.park, self.first = lat.new_empty((3,) + tuple(lat.shape)), torch.empty_like(lat), i
-        return self.lib.mi355x_sd_plms_update(lat.data_ptr(), eps, eps_text, self.park.data_ptr(), self.history.data_ptr(),
-                                              out.data_ptr(), self.coef.data_ptr() + 48 * (i - self.first), gs, gr, lat.shape[0],
-                                              lat.numel() // lat.shape[0], stream)
+    form = FORMS["plms"]
 
 
 class _SinglestepTail(_FusedTail):
@@ -233,14 +202,7 @@ class _SinglestepTail(_FusedTail):
     first row has order 1 and reads neither, every later one reads only what an earlier launch of its group wrote, so fresh ones are
     not initialised, no plane is ever copied and their pointers stay fixed for the whole loop"""
 
-    walk, entry = "singlestep_coefficients", "mi355x_sd_singlestep_update"
-
-    def launch(self, lat, eps, eps_text, out, i, gs, gr, stream):
-        if self.history is None:
-            self.history, self.park, self.first = lat.new_empty((2,) + tuple(lat.shape)), torch.empty_like(lat), i
-        return self.lib.mi355x_sd_singlestep_update(lat.data_ptr(), eps, eps_text, self.park.data_ptr(), self.history.data_ptr(),
-                                                    out.data_ptr(), self.coef.data_ptr() + 32 * (i - self.first), gs, gr,
-                                                    lat.shape[0], lat.numel() // lat.shape[0], stream)
+    form = FORMS["singlestep"]
 
 
 # in priority order: the first whose walk the scheduler has
@@ -338,7 +300,7 @@ class StableDiffusionDenoiser(_VaeSwitches):
         except NotImplementedError:
             return None
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
-        return tail.build(lib, emulated, coef, scales, sch, generator)
+        return tail(lib, emulated, coef, scales, sch, generator)
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
         """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1)."""

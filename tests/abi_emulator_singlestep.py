@@ -13,7 +13,8 @@ restates a FAULT for tests/test_singlestep_bounds.py:
 from __future__ import annotations
 
 from tests.abi_emulator_guidance import F32, GuidanceEmulator, guided
-from tests.singlestep_bounds import FORM, flags
+from tests.singlestep_bounds import flags
+from tests.step_forms import FORMS
 
 
 def emulate(x, eu, et, P, H, coef, gs, gr, fault=None):
@@ -45,7 +46,7 @@ def emulate(x, eu, et, P, H, coef, gs, gr, fault=None):
 
 class SinglestepEmulator(GuidanceEmulator):
     def mi355x_sd_singlestep_update(self, x, eu, et, park, hist, out, coef, gs, gr, batch, per_sample, stream):
-        v = self.step_args(FORM, dict(x=x, eu=eu, et=et, P=park, H=hist, out=out, coef=coef), batch, per_sample, et and gr > 0)
+        v = self.step_args(FORMS["singlestep"], dict(x=x, eu=eu, et=et, P=park, H=hist, out=out, coef=coef), batch, per_sample, et and gr > 0)
         o, P, Hn = emulate(v["x"], v["eu"], v["et"], v["P"], v["H"], v["coef"], gs, gr if et else 0.0)
         order, keep, _ = flags(v["coef"])
         if order == 1:   # only what the kernel writes is written: everything else keeps whatever it holds

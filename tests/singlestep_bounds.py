@@ -48,13 +48,10 @@ from paddlemix_amd.schedulers import DPMSolverSinglestepScheduler
 from tests.guidance_bounds import RESIDENT
 from tests.multistep_bounds import guided
 from tests.rowmap_bounds import U32, check
-from tests.step_forms import _form
 from tests.step_pieces import base_inputs, counting
 
 SCHED = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
 WIDTH = 8   # fp32 values in a row
-# the row of the new entry for tests/step_forms.py's readers (kept here: that table is the seven earlier forms')
-FORM = _form("singlestep_update", "x eu et P H out coef", WIDTH, {"out": 1, "P": 1, "H": 2})
 
 
 def scheduler(**kw):

@@ -16,6 +16,7 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
 from tests import singlestep_bounds as SB  # noqa: E402
+from tests.step_forms import FORMS  # noqa: E402
 from tests.step_child import _in, _out, capture, launched, main, refusals, replay_rows, tally  # noqa: E402
 from tests.step_pieces import Recording, Replay  # noqa: E402
 
@@ -120,7 +121,7 @@ def _deviations(but, n, x, eu, et, P, H, out, coef):
 
 
 def run_refusals():
-    return refusals(SB.FORM, 16, (0, 1, 2, 4, 6, 10, 12), _deviations)   # H: the planes 6, 7
+    return refusals(FORMS["singlestep"], 16, (0, 1, 2, 4, 6, 10, 12), _deviations)   # H: the planes 6, 7
 
 
 def run_pipeline():

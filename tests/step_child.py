@@ -1,6 +1,6 @@
-"""What the GPU children of the seven fused-step families share (tests/{guidance,multistep,unipc,ancestral,heun,dpm2,plms}_child.py),
-beside tests/gpu_child.py: canary-backed views, the shape of a captured graph, one captured launch, the refusal runner and main().
-Each child keeps its cases' launches, its state, its refusal table, its graph rows and its JSON keys."""
+"""What the GPU children of the eight fused-step families share
+(tests/{guidance,multistep,unipc,ancestral,heun,dpm2,plms,singlestep}_child.py), beside tests/gpu_child.py: canary-backed views, the shape of a
+captured graph, one captured launch, the refusal runner and main(). Each child keeps its cases' launches, its state, its refusal table, its graph rows and its JSON keys."""
 import ctypes
 import sys
 import time

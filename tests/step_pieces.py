@@ -1,4 +1,4 @@
-"""What the seven fused-step test families (guidance, multistep, unipc, ancestral, heun, dpm2, plms) share on the host -- TEST
+"""What the eight fused-step test families (guidance, multistep, unipc, ancestral, heun, dpm2, plms, singlestep) share on the host -- TEST
 INFRASTRUCTURE ONLY: the start of every case's inputs, and the stand-ins a loop test puts around the model and the scheduler. Each
 family's *_bounds.py keeps its own float64 reference, bound, schedule rows and cases."""
 import functools

@@ -9,6 +9,7 @@ import torch
 
 from tests import singlestep_bounds as SB
 from tests.abi_emulator_singlestep import emulate
+from tests.step_forms import FORMS
 from tests.test_step_forms import _check
 
 
@@ -21,8 +22,9 @@ def _good(r):
 
 
 def test_the_form_row_agrees_with_its_signature():
-    _check(SB.FORM)
-    assert SB.FORM.entry == "singlestep_update" and SB.FORM.width == SB.WIDTH == 8
+    form = FORMS["singlestep"]
+    _check(form)
+    assert form.entry == "singlestep_update" and form.width == SB.WIDTH == 8
 
 
 @pytest.mark.parametrize("name", list(SB.CASES))
