@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 21
+#define MI355X_SD_ABI_VERSION 22
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -150,6 +150,10 @@ int mi355x_sd_unet_set_input(void* handle, const char* name, const void* device_
 /* IPAdapterAttnProcessor.scale of every cross-attention (the reference's set_ip_adapter_scale, loaders/ip_adapter.py; default 1; 0
  * drops the image-token attention launches). A constant of the planned launches: changing it discards the plan -- plan and bind again. */
 int mi355x_sd_unet_set_ip_adapter_scale(void* handle, float scale);
+/* FreeU (the reference's UNet2DConditionModel.enable_freeu / disable_freeu, unet_2d_condition.py:777-808; ABI 22): enabled != 0 plans
+ * one mi355x_sd_freeu launch in front of every resnet of up blocks 0 (b1, s1) and 1 (b2, s2); enabled == 0 plans none (the default).
+ * The four values must be finite. Constants of the planned launches: a change discards the plan -- plan and bind again. */
+int mi355x_sd_unet_set_freeu(void* handle, int enabled, float s1, float s2, float b1, float b2);
 /* ---- seam B2: any exported step program behind one handle (paddlemix_amd/csrc/program_exec.hip) --------------------------------
  * Every model of the path (UNet2DConditionModel, ControlNetModel, SD3Transformer2DModel, the DiT Transformer2DModel, AutoencoderKL
  * decode / encode, the CLIP and T5 text encoders) runs as a static list of the per-op launches below over weights + scratch. The
@@ -397,6 +401,21 @@ int mi355x_sd_copy_rows(const void* x, int ldx, void* y, int ldy, int64_t rows, 
  * on a bf16 NHWC row view (row stride ldx; C % 8 == 0), r NCHW fp32 as the reference passes it. */
 int mi355x_sd_add_nchw(void* x, int ldx, const float* r_nchw, int B, int C, int64_t HW, void* stream);
 int mi355x_sd_add_nchw_ex(void* x, int ldx, const float* r_nchw, int B, int C, int64_t HW, int x_f32, void* stream);
+
+/* FreeU (apply_freeu / fourier_filter, PPD/utils/paddle_utils.py:259-313; ABI 22) in place on a concat buffer of the U-Net's up path:
+ * cat is B*H*W rows of Cx backbone columns followed by Cs skip columns, row stride ld elements (bf16, or fp32 when elem_f32 != 0).
+ *   columns [0, Cx / 2)    *= b
+ *   columns [Cx, Cx + Cs)  <- the Fourier filter with threshold 1 and scale s of every (batch, channel) plane [H][W]: the four shifted
+ *                             FFT bins ky, kx in {-1, 0} scaled by s, i.e. with ty = 2 pi y / H, tx = 2 pi x / W and <.> the plane's mean
+ *                             out = x + (s - 1) (<x> + sum over phi in {ty, tx, ty + tx} of <x cos phi> cos phi + <x sin phi> sin phi)
+ *   columns [Cx / 2, Cx) and [Cx + Cs, ld) are not written.
+ * fp32 arithmetic, one rounding per stored element, no atomics: two runs give the same bits. `workspace` needs
+ * mi355x_sd_freeu_workspace_floats(B, H, W, Cs) floats (0 for arguments the call would refuse), 16-byte aligned.
+ * MI355X_SD_ERR_INVALID: a null pointer, B < 1, H < 2, W < 2, Cx < 0, Cs < 1, ld < Cx + Cs, cat or the row stride in bytes not a
+ * multiple of 16, b or s not finite. MI355X_SD_ERR_UNSUPPORTED: W > 4096 or B > 65535. */
+int64_t mi355x_sd_freeu_workspace_floats(int B, int H, int W, int Cs);
+int mi355x_sd_freeu(void* cat, int64_t ld, int B, int H, int W, int Cx, int Cs, float b, float s, int elem_f32, float* workspace,
+                    void* stream);
 
 /* DiagonalGaussianDistribution (PPD/models/vae.py:744-763, built by AutoencoderKL.encode, autoencoder_kl.py:266-283) from
  * the encoder's moments held as fp32 rows [B*HW][ld >= 2L] (channels mean_0..L-1, logvar_0..L-1): writes NCHW fp32

@@ -260,6 +260,15 @@ class CUNet2DConditionModel:
 
     __call__ = forward
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """the reference's ``enable_freeu`` (mi355x_sd_unet_set_freeu); constants of the plan: the next call plans again"""
+        _lib.check(self.hd.lib.mi355x_sd_unet_set_freeu(self.hd.h, 1, float(s1), float(s2), float(b1), float(b2)))
+        self._geom = None
+
+    def disable_freeu(self) -> None:
+        _lib.check(self.hd.lib.mi355x_sd_unet_set_freeu(self.hd.h, 0, 1.0, 1.0, 1.0, 1.0))
+        self._geom = None
+
     def set_ip_adapter_scale(self, scale: float) -> None:
         """IPAdapterAttnProcessor.scale (the reference's ``set_ip_adapter_scale``); a constant of the plan: the next call plans again"""
         if self.hd.config_dict.get("encoder_hid_dim_type") != "ip_image_proj":

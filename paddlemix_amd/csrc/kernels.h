@@ -145,6 +145,17 @@ int launch_conv_out3x3(const bf16* x, int ldx, const bf16* w, const float* bias,
                        int W, int Cout, hipStream_t stream);
 int launch_cast_rows(const float* x, int ldx, bf16* y, int ldy, long rows, int C, hipStream_t stream);
 int launch_add_nchw(void* x, int x_f32, int ldx, const float* r, int B, int C, long HW, hipStream_t stream);
+// FreeU on a concat buffer, in place (freeu.hip): backbone half * b, skip planes Fourier-filtered with scale s; ws: freeu_workspace_floats
+constexpr int FU_Q = 7;           // sums per plane
+constexpr int FU_MAX_SPLIT = 32;  // most row splits of a plane
+// an upper bound that needs neither Cx nor the element size: at most FU_MAX_SPLIT (and at most H) splits, and the skip span padded to
+// whole 16-byte groups at both ends. Stated here, once, for the library and for the host-only plan dump (scripts/c/unet_plan_dump.cpp)
+inline long freeu_workspace_floats(int B, int H, int W, int Cs) {
+  if (B < 1 || H < 2 || W < 2 || Cs < 1) return 0;
+  const long splits = H < FU_MAX_SPLIT ? H : FU_MAX_SPLIT;
+  return (long)B * splits * FU_Q * ((long)Cs + 16);
+}
+int launch_freeu(void* cat, int x_f32, long ld, int B, int H, int W, int Cx, int Cs, float b, float s, float* ws, hipStream_t stream);
 int launch_latent_dist(const float* m, int ld, int B, int L, long HW, const float* noise, float out_scale, float* mean,
                        float* logvar, float* sample, hipStream_t stream);
 int launch_embed_tokens(const int* ids, long n_tokens, int seq_len, const bf16* tok, const bf16* pos, int D, bf16* out,

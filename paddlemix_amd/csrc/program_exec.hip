@@ -68,7 +68,7 @@ const std::vector<Entry>& op_table() {   // every stream-ordered launch of the h
       SD_OP(mi355x_sd_conv_out3x3), SD_OP(mi355x_sd_copy_rows), SD_OP(mi355x_sd_add_nchw), SD_OP(mi355x_sd_add_nchw_ex),
       SD_OP(mi355x_sd_latent_dist), SD_OP(mi355x_sd_embed_tokens), SD_OP(mi355x_sd_activation), SD_OP(mi355x_sd_rmsnorm),
       SD_OP(mi355x_sd_gated_activation), SD_OP(mi355x_sd_conv1x1_nchw), SD_OP(mi355x_sd_softmax_rows), SD_OP(mi355x_sd_axpby),
-      SD_OP(mi355x_sd_cfg_axpby)};
+      SD_OP(mi355x_sd_cfg_axpby), SD_OP(mi355x_sd_freeu)};
   return t;
 }
 

@@ -129,6 +129,8 @@ struct Exec {
   Ref in_class, in_tcond, in_image;               // class_labels / timestep_cond / image_embeds as the program reads them (mi355x_sd_unet_set_input)
   const float* image_ptr = nullptr;
   float ip_scale = 1.0f;                          // IPAdapterAttnProcessor.scale (mi355x_sd_unet_set_ip_adapter_scale; a launch constant of the plan)
+  bool freeu = false;                             // FreeU (mi355x_sd_unet_set_freeu): launch constants of the plan, like ip_scale
+  float freeu_s[2] = {1.0f, 1.0f}, freeu_b[2] = {1.0f, 1.0f};   // (s1, s2), (b1, b2): up blocks 0 and 1
   const void* class_ptr = nullptr;                // caller's device tensors, read by every forward call until replaced
   const float* tcond_ptr = nullptr;
   // optional inputs chosen at plan time (mi355x_sd_unet_plan_ex flags)

@@ -113,6 +113,31 @@ int mi355x_sd_unet_set_ip_adapter_scale(void* handle, float scale) {
   return MI355X_SD_OK;
 }
 
+int mi355x_sd_unet_set_freeu(void* handle, int enabled, float s1, float s2, float b1, float b2) {
+  if (!handle) {
+    sd::set_last_error("mi355x_sd_unet_set_freeu: null handle");
+    return MI355X_SD_ERR_INVALID;
+  }
+  Exec* e = H_(handle);
+  for (float v : {s1, s2, b1, b2})
+    if (v - v != 0.0f) {
+      sd::set_last_error("mi355x_sd_unet_set_freeu: s1, s2, b1, b2 must be finite");
+      return MI355X_SD_ERR_INVALID;
+    }
+  const bool on = enabled != 0;
+  const bool same = on == e->freeu && (!on || (s1 == e->freeu_s[0] && s2 == e->freeu_s[1] && b1 == e->freeu_b[0] && b2 == e->freeu_b[1]));
+  if (!same && e->planned) {   // constants of the planned launches: the plan (and its graph) go
+    e->drop_graph();
+    e->drop_plan();
+  }
+  e->freeu = on;
+  if (on) {
+    e->freeu_s[0] = s1; e->freeu_s[1] = s2;
+    e->freeu_b[0] = b1; e->freeu_b[1] = b2;
+  }
+  return MI355X_SD_OK;
+}
+
 int mi355x_sd_unet_num_params(void* handle) { return handle ? (int)H_(handle)->order.size() : -1; }
 
 int mi355x_sd_unet_param_info(void* handle, int index, const char** name, int64_t* shape4, int* ndim) {

@@ -381,6 +381,22 @@ struct Planner {
     for (size_t k = 0; k < skips.size(); ++k) e.ctrl_down.push_back(add(skip_slot((int)k), skips[k].C, (int64_t)skips[k].h * skips[k].w));
     e.ctrl_mid = add(mid, mid.C, (int64_t)h * w_);
   }
+  // FreeU (apply_freeu, unet_2d_blocks.py:2329-2351, 2478-2500): the concat input of up resnet u, in place, before its first GroupNorm --
+  // backbone half * b, skip planes Fourier-filtered with scale s, for the resnets of up blocks 0 (b1, s1) and 1 (b2, s2)
+  void freeu(int u) {
+    if (!e.freeu) return;
+    const std::string& name = ups[u]->name;
+    const int i = name.rfind("up_blocks.0.", 0) == 0 ? 0 : name.rfind("up_blocks.1.", 0) == 0 ? 1 : -1;
+    if (i < 0) return;
+    const View cat = cats[u];
+    const Sk& s = skips[skips.size() - 1 - u];
+    const int h = s.h, w_ = s.w, cx = cat_xc[u], cs = cat.C - cat_xc[u], f32 = cat.es == 4;
+    const float b = e.freeu_b[i], sc_ = e.freeu_s[i];
+    const Ref ws = sc("freeu_ws", (size_t)4 * mi355x_sd_freeu_workspace_floats(B, h, w_, cs));
+    emit([=](const Exec& x, void* st) {
+      return mi355x_sd_freeu(x.at(cat.p), cat.ld, x.B, h, w_, cx, cs, b, sc_, f32, (float*)x.at(ws), st);
+    });
+  }
   View stem() {   // conv_in writes skip 0
     const View cur = skip_slot(0);
     const Ref smp = e.in_sample, scl = e.in_scale, wr = wref("conv_in.w"), br = wref("conv_in.b");
@@ -418,6 +434,7 @@ struct Planner {
         cur = dst;
       } else if (d.kind == Layer::CAT) {
         if (u == 0) controlnet_residuals(cur, h, w_);
+        freeu(u);
         cur = cats[u++];
       } else if (d.kind == Layer::UP) {
         const View dst = x_slot(u);

@@ -248,6 +248,14 @@ class StableDiffusionDenoiser(_VaeSwitches):
         self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2
         self.controlnet = controlnet   # ControlNetModel: StableDiffusionControlNetPipeline (controlnet/pipeline_controlnet.py)
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """FreeU on the U-Net's first two up blocks (pipeline_stable_diffusion.py ``enable_freeu`` -> ``unet.enable_freeu``); holds
+        with every scheduler tail and with a ControlNet, whose own model has no up path and is left alone"""
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self) -> None:
+        self.unet.disable_freeu()
+
     def encode_prompt(self, input_ids: torch.Tensor, input_ids_2: Optional[torch.Tensor] = None,
                       clip_skip: Optional[int] = None):
         """Token ids -> (prompt_embeds, pooled_prompt_embeds or None). Tokenisation stays with the caller (the CLIP

@@ -463,7 +463,8 @@ class _UNetWeights:
 class _UNetPlanner:
     """The launch plan of one input geometry, written stage by stage: ``inputs``, ``time_embedding`` (with ``class_embedding`` around its
     MLP), ``added_conditions``, ``block_embeddings``, ``context_kv``, ``skip_layout``, ``walk`` (``stem``, then per layer ``resnet`` /
-    ``transformer`` / ``downsample`` / ``upsample``, and ``controlnet_residuals`` where the up path starts) and ``head``. The attributes
+    ``transformer`` / ``downsample`` / ``upsample``, ``controlnet_residuals`` where the up path starts and ``freeu`` on every concat
+    input) and ``head``. The attributes
     are what crosses stages: ``emb_t`` / ``emb`` / ``cls_out``, ``temb_all``, ``kv_all``, ``kvip_all``, the masks' biases, the skip layout
     (``skips``, ``ups``, ``cats``, ``cat_xc``, ``cat_hw``, ``own_skips``) and ``RES``; everything else is a local of one stage."""
 
@@ -799,6 +800,23 @@ class _UNetPlanner:
         plan.ctrl_down = [add(self.skip_slot(k), *s) for k, s in enumerate(self.skips)]
         plan.ctrl_mid = add(mid, mid.C, h, w_)
 
+    def freeu(self, u: int):
+        """FreeU (apply_freeu, unet_2d_blocks.py:2329-2351, 2478-2500): the concat input of up resnet ``u``, in place, before its first
+        GroupNorm -- backbone half * b, skip planes Fourier-filtered with scale s, for the resnets of up blocks 0 (b1, s1) and 1 (b2, s2)"""
+        fu = self.m.freeu
+        if fu is None:
+            return
+        name = self.ups[u][1]
+        i = 0 if name.startswith("up_blocks.0.") else 1 if name.startswith("up_blocks.1.") else None
+        if i is None:
+            return
+        s, b = fu[i], fu[2 + i]
+        cat, cx, (h, w_) = self.cats[u], self.cat_xc[u], self.cat_hw[u]
+        cs = cat.C - cx
+        ws = self.pb.sc("freeu_ws", 4 * self.lib.mi355x_sd_freeu_workspace_floats(self.B, h, w_, cs))
+        self.pb.emit(self.lib.mi355x_sd_freeu, (cat.p, cat.ld, self.B, h, w_, cx, cs, b, s, 1 if cat.es == 4 else 0, ws, self.stream),
+                     "freeu", 0.0, f"{self.B}x{h}x{w_}x{cx}+{cs}")
+
     def stem(self) -> _V:
         """conv_in writes skip 0"""
         plan, pb, cfg = self.plan, self.pb, self.cfg
@@ -843,6 +861,7 @@ class _UNetPlanner:
             elif d[0] == "cat":
                 if u == 0:
                     self.controlnet_residuals(cur, h, w_)
+                self.freeu(u)
                 cur = self.cats[u]
                 u += 1
             elif d[0] == "up":
@@ -910,6 +929,7 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
         self._class_kind = "embedding" if (ct is None and self.cfg["num_class_embeds"] is not None) else ct
         self._ip = self.cfg["encoder_hid_dim_type"] == "ip_image_proj"
         self.ip_adapter_scale = 1.0
+        self.freeu: Optional[Tuple[float, float, float, float]] = None   # (s1, s2, b1, b2) while FreeU is on
         self._layers = _structure(self.cfg, self._encoder_only)
         self._Weights(self, params).load()
 
@@ -944,10 +964,23 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
             raise ValueError("this UNet has no IP-Adapter (config encoder_hid_dim_type != 'ip_image_proj')")
         self.ip_adapter_scale = float(scale)
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """FreeU (https://arxiv.org/abs/2309.11497; unet_2d_condition.py:777-801): in the first two up blocks the first half of the
+        backbone channels is multiplied by b1 / b2 and the skip features are Fourier-filtered with scale s1 / s2 before every resnet.
+        The four values are launch constants: plans are per setting."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        if not all(math.isfinite(v) for v in vals):
+            raise ValueError(f"enable_freeu: s1, s2, b1, b2 must be finite, got {vals}")
+        self.freeu = vals
+
+    def disable_freeu(self) -> None:
+        """unet_2d_condition.py:803-808"""
+        self.freeu = None
+
     def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False, self_mask_len: int = 0) -> _Plan:
         if masked and self._ip:
             raise NotImplementedError("encoder_attention_mask together with IP-Adapter image tokens")
-        return self.plan_for((B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len),
+        return self.plan_for((B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len, self.freeu),
                              lambda: self._Planner(self, B, H, W, L, masked, controlnet, self_mask_len).build())
 
     def stage_inputs(self, plan: _Plan, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
@@ -1229,6 +1262,9 @@ class ControlNetModel(UNet2DConditionModel):
 
     def _shapes(self) -> Dict[str, tuple]:
         return controlnet_param_shapes(self._full_config)
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        raise ValueError("ControlNetModel has no up blocks: FreeU applies to the UNet2DConditionModel it conditions")
 
     def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False) -> _Plan:
         return self.plan_for((B, H, W, L, masked) + self._cn_key, lambda: self._Planner(self, B, H, W, L, masked).build())

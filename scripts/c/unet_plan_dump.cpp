@@ -4,7 +4,8 @@
 // that are only ever subtracted again. scripts/compare_unet_plans.py builds this against a csrc directory and walks the case grid.
 //
 //   hipcc -x hip --offload-arch=gfx950 -std=c++17 -O1 -I <csrc> scripts/c/unet_plan_dump.cpp -o unet_plan_dump
-//   unet_plan_dump config.json image.bin B,H,W,L,flags,resid_f32 [B,H,W,L,flags,resid_f32 ...]
+//   unet_plan_dump config.json image.bin B,H,W,L,flags,resid_f32[,freeu] [B,H,W,L,flags,resid_f32[,freeu] ...]
+// (freeu = 1: the plan with FreeU on, s1 = 0.9, s2 = 0.2, b1 = 1.3, b2 = 1.4; a checkout from before ABI 22 prints an error line for it)
 #if __has_include("unet_plan.hip")
 #include "unet_config.hip"
 #include "unet_weights.hip"
@@ -95,6 +96,12 @@ int mi355x_sd_conv_out3x3(CV x, int ldx, CV w, CF b, float* y, int B, int Ci, in
   return rec("conv_out3x3", x, ldx, w, b, y, B, Ci, H, W, Co, st);
 }
 int mi355x_sd_add_nchw_ex(void* x, int ldx, CF r, int B, int C, I8 HW, int f32, void* st) { return rec("add_nchw_ex", x, ldx, r, B, C, HW, f32, st); }
+#if MI355X_SD_ABI_VERSION >= 22
+I8 mi355x_sd_freeu_workspace_floats(int B, int H, int W, int Cs) { return sd::freeu_workspace_floats(B, H, W, Cs); }   // the library's own (kernels.h)
+int mi355x_sd_freeu(void* cat, I8 ld, int B, int H, int W, int Cx, int Cs, float b, float s, int f32, float* ws, void* st) {
+  return rec("freeu", cat, ld, B, H, W, Cx, Cs, b, s, f32, (CV)ws, st);
+}
+#endif
 }
 
 #define CHECK(call)                                                        \
@@ -125,10 +132,18 @@ static int run(int argc, char** argv) {
   for (auto& kv : e->w) printf("packed %s off=%zu bytes=%zu rows=%d cols=%d\n", kv.first.c_str(), kv.second.off, kv.second.bytes, kv.second.rows, kv.second.cols);
   CHECK(mi355x_sd_unet_attach_weights(h, WBASE, g_wbytes));
   for (int a = 3; a < argc; ++a) {
-    int B, H, W, L, flags, f32;
-    if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d", &B, &H, &W, &L, &flags, &f32) != 6) return 2;
+    int B, H, W, L, flags, f32, freeu = 0;
+    if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d,%d", &B, &H, &W, &L, &flags, &f32, &freeu) < 6) return 2;
     printf("plan %s\n", argv[a]);
     e->resid_f32 = f32 != 0;
+#if MI355X_SD_ABI_VERSION >= 22
+    CHECK(mi355x_sd_unet_set_freeu(h, freeu, 0.9f, 0.2f, 1.3f, 1.4f));
+#else
+    if (freeu) {
+      printf("error: this checkout has no FreeU\n");
+      continue;
+    }
+#endif
     if (int rc = mi355x_sd_unet_plan_ex(h, B, H, W, L, flags, &g_sbytes)) {
       printf("error %d: %s\n", rc, g_last);
       continue;

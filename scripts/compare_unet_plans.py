@@ -9,7 +9,8 @@
 Builds scripts/c/unet_plan_dump.cpp against the given csrc directory (host code only; no GPU is touched) and runs it over: the 15
 configs of tests/test_cexec_host_logic.py at (2, 16, 16, 7) with the 16-bit and the fp32 residual stream; every combination of the
 mi355x_sd_unet_plan_ex flags on TINY, MINI_XL and two one-level models whose attention runs at full resolution (the only ones a
-self-attention mask fits; head_dim 8 and 64); MINI_XL at the odd sizes; SDXL at (2, 128, 128, 77). One file per config: every packed
+self-attention mask fits; head_dim 8 and 64); MINI_XL at the odd sizes; SDXL at (2, 128, 128, 77); TINY, MINI_XL and SDXL with FreeU
+on (a seventh field, with and without ControlNet residuals and the fp32 residual stream). One file per config: every packed
 tensor's place, every buffer, every launch with every argument; `images.sha256` holds the hash of every packed weight image."""
 import hashlib
 import json
@@ -29,6 +30,8 @@ CASES = {"tiny": (TINY, FLAGS), "mini-xl": (MINI_XL, FLAGS + ["1,18,18,77,0,0", 
          "sd15": (SD15, BOTH), "sdxl": (SDXL, BOTH + ["2,128,128,77,0,0"]),
          "one-level": (ONE_LEVEL, FLAGS), "one-level-hd64": (dict(ONE_LEVEL, attention_head_dim=1), FLAGS)}
 CASES.update({k: (v, BOTH) for k, v in CLASS_CONFIGS.items()})
+FREEU = ["2,16,16,7,0,0,1", "2,16,16,7,0,1,1", "2,16,16,7,4,0,1", "1,18,18,77,0,0,1"]   # (the files of a checkout without FreeU differ here only)
+CASES.update({"tiny-freeu": (TINY, FREEU[:3]), "mini-xl-freeu": (MINI_XL, FREEU), "sdxl-freeu": (SDXL, FREEU[:2])})
 
 
 def main(csrc, out):
