@@ -44,10 +44,11 @@ import math
 
 import torch
 
-U_OUT = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10}
+from tests import bound_pieces as BP
+from tests.bound_pieces import U32, U_OUT, fp32  # noqa: F401  (U_OUT, fp32: for the importers of this module)
+
 U_P = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 P_TINY = {torch.bfloat16: 0.0, torch.float16: 2.0 ** -14}
-U32 = 2.0 ** -24
 C_RND = 8
 EXP_REL = 2.0 ** -20
 LN2 = math.log(2.0)
@@ -56,11 +57,6 @@ LN2 = math.log(2.0)
 def gamma(n: int) -> float:
     """fp32 accumulation error factor of an n-deep sum in chains of 16-deep MFMA steps"""
     return (n / 16 + 32) * U32
-
-
-def fp32(x: float) -> float:
-    """the value a float argument of the C ABI arrives with"""
-    return float(torch.tensor(x, dtype=torch.float32))
 
 
 def reference(q, k, v, *, scale=None, bias=None, log2=False, accum=None, old=None, exact_p=False):
@@ -125,16 +121,9 @@ def reference(q, k, v, *, scale=None, bias=None, log2=False, accum=None, old=Non
 
 
 def check(out, ref, e):
-    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit output against reference() (non-finite -> inf)"""
-    u = U_OUT[out.dtype]
-    o = out.double()
-    err = (o - ref).abs()
-    bound = u * ref.abs() + (1 + u) * e + U32
-    ratio = (err / bound).max().item()
-    if not torch.isfinite(o).all() or ratio != ratio:
-        ratio = float("inf")
-    rel = ((o - ref).norm() / ref.norm().clamp_min(1e-300)).item()
-    return ratio, rel
+    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit output against reference() (non-finite -> inf); rel-L2's
+    denominator is clamped at 1e-300 (a fully masked output has a zero reference)"""
+    return BP.check(out, ref, e, rel_floor=1e-300)
 
 
 def bound_check(out, q, k, v, **kw):

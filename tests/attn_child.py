@@ -18,9 +18,8 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import attn_bounds as AB  # noqa: E402
 from tests import attn_cases as AC  # noqa: E402
-from tests.gpu_child import Routes, emit  # noqa: E402
+from tests import kernel_pieces as KP  # noqa: E402
 
-CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 CASES = {}        # name: (spec, family the route log must show, aligned O)
 
 
@@ -107,17 +106,11 @@ _add("flash160 D160 accum S2", "flash160", 2, 3, 200, 257, 160, "S2", accum=0.6)
 _add("flash160 D128 Skv1 S3", "flash160", 2, 3, 200, 1, 128, "S3")
 
 
-def _strided(B, S, H, D, row_pad, extra_rows, off, fill):
-    """a [B, S, H, D] view inside a flat 16-bit buffer of `fill` bits: row stride H*D + row_pad, batch stride (S + extra_rows) rows,
-    `off` elements in. Returns (view, flat buffer, bool mask of the view's elements in the buffer)."""
+def _geom(B, S, H, D, row_pad, extra_rows, off):
+    """(shape, strides, off, n) of a [B, S, H, D] view in a flat buffer: rows H*D + row_pad and batches S + extra_rows rows apart, from `off`, 64 behind"""
     ts = H * D + row_pad
     bs = (S + extra_rows) * ts
-    n = off + B * bs + 64
-    buf = torch.full((n,), fill, dtype=torch.int16, device="cuda").view(_lib.elem_dtype())
-    view = buf.as_strided((B, S, H, D), (bs, ts, D, 1), off)
-    inside = torch.zeros(n, dtype=torch.bool, device="cuda")
-    inside.as_strided((B, S, H, D), (bs, ts, D, 1), off).fill_(True)
-    return view, buf, inside
+    return (B, S, H, D), (bs, ts, D, 1), off, off + B * bs + 64
 
 
 def run_case(name):
@@ -129,22 +122,17 @@ def run_case(name):
         c["bias"][1, 2, 5, :64] = -math.inf
     B, Sq, H, D = c["q"].shape
     Skv = c["k"].shape[1]
-    nan = 0x7FC0 if ed == torch.bfloat16 else 0x7E00
-    kv = []
-    for t in (c["k"], c["v"]):   # NaN rows behind Skv, NaN columns behind the last head
-        view, _, _ = _strided(B, Skv, H, D, 16, 40, 0, nan)
-        view.copy_(t)
-        kv.append(view)
+    # K, V: NaN rows behind Skv (40 of them), NaN columns behind the last head (16)
+    kv = [KP.nan_embed(t, *_geom(B, Skv, H, D, 16, 40, 0)[1:])[0] for t in (c["k"], c["v"])]
     # O: 16-byte-aligned base and rows (the 16-byte store forms), or an 8-byte-aligned base and rows (the 8-byte forms)
-    out, obuf, inside = _strided(B, Sq, H, D, 8 if aligned else 4, 3, 0 if aligned else 4, CANARY)
+    og = KP.Guarded.strided(*_geom(B, Sq, H, D, 8 if aligned else 4, 3, 0 if aligned else 4), 16, dt=ed)
+    out = og.view
     if c["accum"] is not None:
         out.copy_(c["old"])
     scale = None if c["log2"] else c["scale"]
     ops.sdpa(c["q"], kv[0], kv[1], bias=c["bias"], scale=scale, out=out, accum=c["accum"], log2=c["log2"])
     torch.cuda.synchronize()
-    bits = obuf.view(torch.int16)
-    unwritten = int(((bits == CANARY) & inside).sum().item())
-    overwritten = int(((bits != CANARY) & ~inside).sum().item())
+    unwritten, overwritten = og.counts()
     ratio, rel = AB.bound_check(out, c["q"], c["k"], c["v"], scale=c["scale"], bias=c["bias"], log2=c["log2"], accum=c["accum"],
                                 old=c["old"], exact_p=c["exact_p"])
     same_v = None
@@ -156,18 +144,5 @@ def run_case(name):
     return dict(ratio=ratio, rel=rel, unwritten=unwritten, overwritten=overwritten, same_v=same_v, zero_rows=zero_rows)
 
 
-def main(names):
-    ops.init(0)
-    routes = Routes("MI355X_SD_ATTN_LOG")
-    routes.take()
-    res = {}
-    for name in names or CASES:
-        r = run_case(name)
-        r["route"] = routes.take()
-        res[name] = r
-        torch.cuda.empty_cache()
-    emit("ATTN_JSON", res)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(CASES, run_case, route_log="MI355X_SD_ATTN_LOG", tag="ATTN_JSON", names=sys.argv[1:])

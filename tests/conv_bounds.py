@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 from tests import gemm_bounds as GB
 
-check = GB.check
+check = GB.check   # (the GEMM's conventions: an fp32 output is the epilogue value itself, rel-L2 unclamped)
 U32 = GB.U32
 
 

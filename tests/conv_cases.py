@@ -13,7 +13,7 @@ the CPU). Every value is exact in bf16 and in fp16. Three kinds, each usable wit
 
 Buffers: x is a channel slice of a wider NHWC allocation (pixel stride Cin + 24, first channel 8), the gap channels and one image's
 worth of elements before and after the tensor are NaN. The output is a column slice of a canary-filled buffer with canary rows above
-and below; guard_count() counts disturbed canary elements.
+and below (tests/kernel_pieces.py Guarded.block); its counts() give the disturbed canary elements.
 """
 import math
 from collections import namedtuple
@@ -21,13 +21,13 @@ from collections import namedtuple
 import torch
 
 from tests import conv_bounds as CB
+from tests import kernel_pieces as KP
 
 # geometry name -> (stride, upsample, pad_br): every combination mi355x_sd_conv3x3 accepts (pad_br is the stride-2 downsampler's)
 GEOMS = {"s1": (1, False, False), "s1up": (1, True, False), "s2": (2, False, False), "s2up": (2, True, False), "s2br": (2, False, True)}
 Case = namedtuple("Case", "kind B H W Cin Cout geom kb64 epi")
 X_GAP, X_OFF = 24, 8        # spare channels per pixel of the wider NHWC allocation, first channel of the slice
 C_GAP, C_OFF, C_ROWS = 16, 8, 64   # spare columns / first column / canary rows above and below the output
-CANARY16, CANARY32 = 0x7FA5, 0x7FA5A5A5   # NaN bit patterns (bf16, fp16 / fp32): never a result
 
 
 def _cases():
@@ -129,31 +129,20 @@ def mask_w(Cout, Cin):
 
 
 def nan_embedded(x):
-    """x [B, H, W, C] values -> (view of the same shape inside a NaN-filled wider allocation, the flat allocation, first element)"""
+    """x [B, H, W, C] values -> (view of the same shape inside a NaN-filled wider allocation, the flat allocation, first element):
+    pixel stride C + X_GAP, first channel X_OFF, one image's worth of NaN before and after the tensor"""
     B, H, W, C = x.shape
     ldx = C + X_GAP
     img = H * W * ldx
-    full = torch.full(((B + 2) * img,), float("nan"), dtype=x.dtype, device=x.device)
-    view = full[img:(B + 1) * img].view(B, H, W, ldx)[..., X_OFF:X_OFF + C]
-    view.copy_(x)
+    view, full = KP.nan_embed(x, (img, W * ldx, ldx, 1), img + X_OFF, (B + 2) * img)
     return view, full, img + X_OFF
 
 
 def alloc_out(M, N, dtype, device):
-    """(out view [M, N], the canary-filled buffer around it)"""
-    if dtype == torch.float32:
-        full = torch.full((M + 2 * C_ROWS, N + C_GAP), CANARY32, dtype=torch.int32, device=device).view(torch.float32)
-    else:
-        full = torch.full((M + 2 * C_ROWS, N + C_GAP), CANARY16, dtype=torch.int16, device=device).view(dtype)
-    return full[C_ROWS:C_ROWS + M, C_OFF:C_OFF + N], full
-
-
-def guard_count(full, M, N):
-    """number of canary elements of alloc_out()'s buffer that no longer hold the canary"""
-    bits = full.view(torch.int32 if full.dtype == torch.float32 else torch.int16)
-    ok = bits == (CANARY32 if full.dtype == torch.float32 else CANARY16)
-    ok[C_ROWS:C_ROWS + M, C_OFF:C_OFF + N] = True
-    return int((~ok).sum().item())
+    """the [M, N] output as a column slice of a canary buffer with C_ROWS canary rows above and below (KP.Guarded: .view, and
+    .counts()[1] the number of canary elements that no longer hold the canary)"""
+    return KP.Guarded.block(M, N, 32 if dtype == torch.float32 else 16, above=C_ROWS, below=C_ROWS, left=C_OFF, right=C_GAP - C_OFF,
+                            dt=dtype, device=device)
 
 
 def build(name, case, elem, device):

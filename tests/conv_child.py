@@ -18,31 +18,22 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import conv_bounds as CB  # noqa: E402
 from tests import conv_cases as CC  # noqa: E402
+from tests import kernel_pieces as KP  # noqa: E402
 from tests.gpu_child import Routes, emit, sha  # noqa: E402
 
 
-def run_gemm_case(name, ed):
+def run_gemm_case(name):
+    ed = _lib.elem_dtype()
     case = CC.CASES[name]
     d = CC.build(name, case, ed, "cuda")
     s, up, br = CC.GEOMS[case.geom]
-    out, full = CC.alloc_out(d["M"], case.Cout, torch.float32 if d["out_f32"] else ed, "cuda")
+    og = CC.alloc_out(d["M"], case.Cout, torch.float32 if d["out_f32"] else ed, "cuda")
+    out = og.view
     ops.conv3x3(d["x"], d["w_dev"], d["bias"], stride=s, upsample=up, rowbias=d["rowbias"], residual=d["residual"], out=out,
                 out_scale=d["out_scale"], pad_br=br, kb64=case.kb64, silu=d["silu"], out_f32=d["out_f32"])
     torch.cuda.synchronize()
     res = CC.judge(case, d, out)
-    res.update(guard=CC.guard_count(full, d["M"], case.Cout), sha=sha(out), M=d["M"])
-    return res
-
-
-def main_gemm(names):
-    ed = _lib.elem_dtype()
-    routes = Routes("MI355X_SD_GEMM_LOG")
-    routes.take()
-    res = {}
-    for name in names or CC.CASES:
-        res[name] = run_gemm_case(name, ed)
-        res[name]["route"] = routes.take()
-        torch.cuda.empty_cache()
+    res.update(guard=og.counts()[1], sha=sha(out), M=d["M"])
     return res
 
 
@@ -52,22 +43,12 @@ MARGIN = 4096   # elements of NaN in front of and behind a dense fp32 input, of 
 
 def nan_margins(x):
     """a dense fp32 tensor -> the same values in the middle of a NaN-filled allocation (a read outside the tensor poisons the result)"""
-    full = torch.full((x.numel() + 2 * MARGIN,), float("nan"), dtype=torch.float32, device=x.device)
-    v = full[MARGIN:MARGIN + x.numel()].view(x.shape)
-    v.copy_(x)
-    return v, full
+    return KP.nan_embed(x, x.contiguous().stride(), MARGIN, x.numel() + 2 * MARGIN)
 
 
 def canary_nchw(shape):
-    """(dense fp32 NCHW output in the middle of a canary-filled allocation, the allocation)"""
-    n = math.prod(shape)
-    full = torch.full((n + 2 * MARGIN,), CC.CANARY32, dtype=torch.int32, device="cuda").view(torch.float32)
-    return full[MARGIN:MARGIN + n].view(shape), full
-
-
-def canary_margins_disturbed(full):
-    bits = full.view(torch.int32)
-    return int((bits[:MARGIN] != CC.CANARY32).sum().item() + (bits[-MARGIN:] != CC.CANARY32).sum().item())
+    """a dense fp32 NCHW output in the middle of a canary-filled allocation (KP.Guarded: .view, .counts()[1] the disturbed margin)"""
+    return KP.Guarded.strided(shape, torch.empty(shape, device="meta").stride(), MARGIN, math.prod(shape) + 2 * MARGIN, 32)
 
 
 def _exact_or_bound(out, ref, e, exact):
@@ -99,14 +80,15 @@ def conv_in_case(ed, kind, Cin, Cout, B, H, W, scale, f32, seed):
     x, x_full = nan_margins(x)
     sc = torch.tensor([scale], dtype=torch.float32, device="cuda") if scale is not None else None
     M = B * H * W
-    out, full = CC.alloc_out(M, Cout, torch.float32 if f32 else ed, "cuda")
+    og = CC.alloc_out(M, Cout, torch.float32 if f32 else ed, "cuda")
+    out = og.view
     _lib.check(lib.mi355x_sd_conv_in3x3_ex(x.data_ptr(), sc.data_ptr() if sc is not None else None, w.data_ptr(),
                                            bias.data_ptr() if bias is not None else None, out.data_ptr(), B, Cin, H, W, Cout,
                                            out.stride(0), int(f32), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     ref, e = CB.conv_in3x3_reference(x, w, bias, sc, ed)
     r = _exact_or_bound(out, ref, e, kind != "random")
-    r["guard"] = CC.guard_count(full, M, Cout)
+    r["guard"] = og.counts()[1]
     return r
 
 
@@ -131,13 +113,14 @@ def conv_out_case(ed, kind, Cin, Cout, B, H, W, seed, tap0=0):
     w = w.cuda().to(ed)
     view, full, first = CC.nan_embedded(x.to(ed))
     rows = full.as_strided((B * H * W, Cin), (Cin + CC.X_GAP, 1), first)
-    out, out_full = canary_nchw((B, Cout, H, W))
+    og = canary_nchw((B, Cout, H, W))
+    out = og.view
     _lib.check(_lib.load().mi355x_sd_conv_out3x3(rows.data_ptr(), rows.stride(0), w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                                  out.data_ptr(), B, Cin, H, W, Cout, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     ref, e = CB.conv_out3x3_reference(view, w, bias)
     r = _exact_or_bound(out, ref, e, kind != "random")
-    r["guard"] = canary_margins_disturbed(out_full)
+    r["guard"] = og.counts()[1]
     return r
 
 
@@ -154,13 +137,14 @@ def conv1x1_case(ed, kind, Cin, Cout, B, H, W, scale, seed):
         bias = torch.randn(Cout, generator=g).cuda()
     w = w.cuda().to(ed)
     x, x_full = nan_margins(x)
-    out, out_full = canary_nchw((B, Cout, H, W))
+    og = canary_nchw((B, Cout, H, W))
+    out = og.view
     _lib.check(_lib.load().mi355x_sd_conv1x1_nchw(x.data_ptr(), float(scale), w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                                   out.data_ptr(), B, Cin, Cout, H * W, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     ref, e = CB.conv1x1_nchw_reference(x, w, bias, scale, ed)
     r = _exact_or_bound(out, ref, e, kind != "random")
-    r["guard"] = canary_margins_disturbed(out_full)
+    r["guard"] = og.counts()[1]
     return r
 
 
@@ -214,7 +198,8 @@ def main_wide():
 
 
 if __name__ == "__main__":
-    ops.init(0)
-    mode = sys.argv[1]
-    res = main_gemm(sys.argv[2:]) if mode == "gemm" else main_direct() if mode == "direct" else main_wide()
-    emit("CONV_JSON", res)
+    if sys.argv[1] == "gemm":
+        KP.run_cases(CC.CASES, run_gemm_case, route_log="MI355X_SD_GEMM_LOG", tag="CONV_JSON", names=sys.argv[2:])
+    else:
+        ops.init(0)
+        emit("CONV_JSON", main_direct() if sys.argv[1] == "direct" else main_wide())

@@ -80,8 +80,9 @@ wrong sub-tile or a doubled bias lands far above 1) and the rel-L2 of the same c
 """
 import torch
 
-U_OUT = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10}
-U32 = 2.0 ** -24
+from tests import bound_pieces as BP
+from tests.bound_pieces import U32, U_OUT  # noqa: F401  (U_OUT: for the importers of this module)
+
 EPI_OPS = 4
 SLOPE = {"silu": 1.10, "gelu_tanh": 1.13, "gelu_erf": 1.13}
 ACT_REL = 2.0 ** -20
@@ -164,20 +165,9 @@ def reference(a, w, *, bias=None, w_scale=None, out_scale=1.0, act=None, geglu=F
 
 
 def check(out, ref, e):
-    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit or fp32 output against reference() (non-finite -> inf)"""
-    o = out.double()
-    err = (o - ref).abs()
-    if out.dtype == torch.float32:   # (u_out = 0: the epilogue value, stored as it is)
-        bound = e + U32 * ref.abs()
-        bound = torch.where((bound == 0) & (err == 0), torch.ones_like(bound), bound)   # (an exact zero: 0 / 0 is a pass)
-    else:
-        u = U_OUT[out.dtype]
-        bound = u * ref.abs() + (1 + u) * e + U32
-    ratio = (err / bound).max().item()
-    if not torch.isfinite(o).all() or ratio != ratio:
-        ratio = float("inf")
-    rel = ((o - ref).norm() / ref.norm()).item()
-    return ratio, rel
+    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit or fp32 output against reference() (non-finite -> inf).
+    fp32: u_out = 0, the epilogue value stored as it is, so the bound is e + 2^-24 |ref|. rel-L2's denominator is not clamped."""
+    return BP.check(out, ref, e, f32_rel=U32, rel_floor=0.0)
 
 
 def bound_check(out, a, w, **kw):

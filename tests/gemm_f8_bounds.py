@@ -69,13 +69,14 @@ import math
 
 import torch
 
+from tests import bound_pieces as BP
 from tests import gemm_bounds as GB
+from tests.kernel_pieces import F8_NAN  # noqa: F401  (NaN in e4m3fn: the filler of every gap of A and W, the canary of the e4m3 output)
 
 U32 = GB.U32
 STEP = 256          # roundings inside one 16x16x128 step, in units of 2^-24 (raised once from the derived 128, see above)
 EPI_OPS8 = 5        # as, ws, bias, gate, residual
 MULTI_CAP = 0.05    # share of e4m3 outputs whose interval may hold more than one code
-F8_NAN = 0x7F       # NaN in e4m3fn: the filler of every gap of A and W, and the canary of the e4m3 output
 F8 = torch.float8_e4m3fn
 KT = 128            # elements per K-tile (128 bytes), 16-byte chunks of 16 elements
 
@@ -206,8 +207,7 @@ def exact_reference(o, ed):
 
 def exact_off(out, ref):
     """number of elements of the 16-bit output whose bits differ from ref.to(out.dtype)"""
-    want = ref.to(out.dtype)
-    return int((out.contiguous().view(torch.int16) != want.contiguous().view(torch.int16)).sum().item())
+    return BP.exact_off(out, ref.to(out.dtype))
 
 
 # ---- class 2: dense operands at realistic magnitudes ---------------------------------------------------------------------------------
@@ -262,11 +262,6 @@ def reference8(qa, sa, qw, sw, *, bias=None, gate=None, rows_per_batch=0, residu
         e = GB.SLOPE["gelu_tanh"] * e + GB.ACT_REL * z.abs()
         z = GB._act("gelu_tanh", z)
     return z, e
-
-
-def check(out, ref, e):
-    """(worst |out - ref| / bound over every element, rel-L2) of a 16-bit output: gemm_bounds.check"""
-    return GB.check(out, ref, e)
 
 
 # ---- e4m3 output -----------------------------------------------------------------------------------------------------------------

@@ -27,8 +27,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-CANARY = 0x7FA5        # (tests/norm_child.py)
-CANARY32 = 0x7FA5A5A5
+from tests import kernel_pieces as KP  # noqa: E402
+
 SEG = (77, 40)         # the two segments of a joint buffer's batch
 BATCH_ROWS = sum(SEG)  # 117
 NBATCH = 3
@@ -82,57 +82,29 @@ def _bytes_rows(q, ld, rpb=0, bstride=0, base=0, total_rows=None):
 
 def _vec_nan(v):
     """fp32 vector followed by 64 NaN"""
-    import torch
-    buf = torch.full((v.numel() + 64,), float("nan"), dtype=torch.float32, device="cuda")
-    buf[:v.numel()] = v.cuda().float()
-    return buf[:v.numel()]
+    return KP.nan_rows(v.cuda().float().reshape(1, -1), v.numel(), tail=64)[0]
 
 
 def _rows_nan(vals, ld):
-    """[R, C] values as a view with row stride ld inside a NaN buffer"""
+    """[R, C] values as a view with row stride ld inside a NaN buffer, 64 NaN behind"""
+    return KP.nan_rows(vals.cuda(), ld, tail=64)
+
+
+def _out(M, N, ld, kind, ed=None, rpb=0, bstride=0, base=0, total_rows=None):
+    """an [M, N] output placed row by row (tests/gemm_f8_bounds.row_offsets) in a flat canary buffer with 3 more rows and 64 more
+    elements: 16-bit (0x7FA5), e4m3 bytes (0x7F) or fp32 (0x7FA5A5A5)"""
     import torch
-    R, C = vals.shape
-    buf = torch.full((R * ld + 64,), float("nan"), dtype=vals.dtype, device="cuda")
-    view = buf.as_strided((R, C), (ld, 1), 0)
-    view.copy_(vals.cuda())
-    return view
-
-
-class _Out:
-    """an [M, N] output placed row by row in a flat canary buffer: 16-bit (0x7FA5), e4m3 bytes (0x7F) or fp32 (0x7FA5A5A5)"""
-    def __init__(self, M, N, ld, kind, ed=None, rpb=0, bstride=0, base=0, total_rows=None):
-        import torch
-        from tests import gemm_f8_bounds as FB
-        rows = (total_rows if total_rows is not None else M) + 3
-        self.canary, it = {16: (CANARY, torch.int16), 8: (FB.F8_NAN, torch.uint8), 32: (CANARY32, torch.int32)}[kind]
-        self.bits = torch.full((rows * ld + 64,), self.canary, dtype=it, device="cuda")
-        self.buf = self.bits if kind == 8 else self.bits.view(ed if kind == 16 else torch.float32)
-        self.idx = base + FB.row_offsets(M, ld, rpb, bstride, "cuda")[:, None] + torch.arange(N, device="cuda")
-        self.inside = torch.zeros(self.bits.numel(), dtype=torch.bool, device="cuda")
-        self.inside[self.idx] = True
-        self.ptr = self.buf.data_ptr() + base * self.buf.element_size()
-
-    def get(self):
-        return self.buf[self.idx]
-
-    def counts(self):
-        un = int(((self.bits == self.canary) & self.inside).sum().item())
-        ov = int(((self.bits != self.canary) & ~self.inside).sum().item())
-        return un, ov
-
-
-def _bits_off(a, b):
-    import torch
-    if tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype:
-        return max(a.numel(), b.numel())
-    it = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[a.element_size()]
-    return int((a.contiguous().view(it) != b.contiguous().view(it)).sum().item())
+    from tests import gemm_f8_bounds as FB
+    rows = (total_rows if total_rows is not None else M) + 3
+    idx = base + FB.row_offsets(M, ld, rpb, bstride, "cuda")[:, None] + torch.arange(N, device="cuda")
+    return KP.Guarded.at(idx, rows * ld + 64, kind, base=base, dt=ed, canary=KP.F8_NAN if kind == 8 else None)
 
 
 # ---- one launch of each entry ----------------------------------------------------------------------------------------------------
 def _run16(o, ed, M, N, K, *, a_seg=None, c_seg=None, c_rpb=0):
     """mi355x_sd_linear_f8 on the operands o -> (result dict, output [M, N])"""
     import torch
+    from tests.bound_pieces import exact_off
     from paddlemix_amd import _lib, ops
     lib, st = _lib.load(), ops._stream()
     lda, ldc = K + 16, N + 8
@@ -151,7 +123,7 @@ def _run16(o, ed, M, N, K, *, a_seg=None, c_seg=None, c_rpb=0):
         c_rpb, c_bs, c_base, total = SEG[c_seg], BATCH_ROWS * ldc, (SEG[0] * ldc if c_seg else 0), NBATCH * BATCH_ROWS
     elif c_rpb:             # batches of c_rpb rows written behind 40 other rows each
         c_bs, total = (c_rpb + 40) * ldc, ((M + c_rpb - 1) // c_rpb) * (c_rpb + 40)
-    out = _Out(M, N, ldc, 16, ed, c_rpb, c_bs, c_base, total)
+    out = _out(M, N, ldc, 16, ed, c_rpb, c_bs, c_base, total)
     flags = _lib.GELU_TANH if o.get("gelu") else 0
     rc = lib.mi355x_sd_linear_f8(A.data_ptr() + a_base, lda, a_rpb, a_bs, sa.data_ptr(), W.data_ptr(), sw.data_ptr(), out.ptr, ldc,
                                  c_rpb, c_bs, M, N, K, ops._p(bias), ops._p(gate), N + 8 if gate is not None else 0, o["rpb"],
@@ -164,21 +136,22 @@ def _run16(o, ed, M, N, K, *, a_seg=None, c_seg=None, c_rpb=0):
         w = ops.linear_f8(o["qa"].cuda(), sa, o["qw"].cuda(), sw, bias, gate=None if gate is None else gate.contiguous(),
                           rows_per_batch=o["rpb"], residual=None if res is None else res.contiguous(), gelu_tanh=bool(o.get("gelu")))
         torch.cuda.synchronize()
-        r["wrapper_off"] = _bits_off(w, got)
+        r["wrapper_off"] = exact_off(w, got)
     return r, got
 
 
 def _run8(o, M, N, K, ldc):
     """mi355x_sd_linear_f8_q on the operands o -> (result dict, bytes [M, N], c_scale [M])"""
     import torch
+    from tests.bound_pieces import exact_off
     from paddlemix_amd import _lib, ops
     lib, st = _lib.load(), ops._stream()
     lda = K + 16
     A, W = _bytes_rows(o["qa"], lda), _bytes_rows(o["qw"], K)
     sa, sw, l2 = _vec_nan(o["sa"]), _vec_nan(o["sw"]), _vec_nan(o["a_l2"])
     bias = _vec_nan(o["bias"]) if o["bias"] is not None else None
-    out = _Out(M, N, ldc, 8)
-    cs = _Out(M, 1, 1, 32, total_rows=M + 8)
+    out = _out(M, N, ldc, 8)
+    cs = _out(M, 1, 1, 32, total_rows=M + 8)
     flags = _lib.GELU_TANH if o.get("gelu") else 0
     rc = lib.mi355x_sd_linear_f8_q(A.data_ptr(), lda, sa.data_ptr(), l2.data_ptr(), W.data_ptr(), sw.data_ptr(), o["w_norm_max"],
                                    out.ptr, ldc, cs.ptr, M, N, K, ops._p(bias), o["bias_abs_max"], flags, st)
@@ -191,7 +164,7 @@ def _run8(o, M, N, K, ldc):
         wq, wc = ops.linear_f8_q(o["qa"].cuda(), sa, l2, o["qw"].cuda(), sw, o["w_norm_max"], bias, o["bias_abs_max"],
                                  gelu_tanh=bool(o.get("gelu")))
         torch.cuda.synchronize()
-        r["wrapper_off"] = _bits_off(wq, q) + _bits_off(wc, c)
+        r["wrapper_off"] = exact_off(wq, q) + exact_off(wc, c)
     return r, q, c
 
 
@@ -208,6 +181,7 @@ def _check_q(r, o, q, c, ref, e):
 
 def run_exact(s, ed):
     import torch
+    from tests import gemm_bounds as GB
     from tests import gemm_f8_bounds as FB
     M, N, K = s["M"], s["N"], s["K"]
     o = FB.exact_operands(M, N, K, s["mirror"], s["sub"], ed)
@@ -215,7 +189,7 @@ def run_exact(s, ed):
     ref = FB.exact_reference(d, ed)   # (asserts the precondition)
     r, got = _run16(o, ed, M, N, K, a_seg=s.get("a_seg"), c_seg=s.get("c_seg"))
     r["off"] = FB.exact_off(got, ref)
-    r["ratio"], r["rel"] = FB.check(got, ref, torch.zeros_like(ref))
+    r["ratio"], r["rel"] = GB.check(got, ref, torch.zeros_like(ref))
     if s.get("q"):   # the same operands through the e4m3 output, judged by the interval rule
         FB.exact_q_operands(o)
         _, e = FB.reference8(d["qa"], d["sa"], d["qw"], d["sw"])
@@ -226,6 +200,7 @@ def run_exact(s, ed):
 
 
 def run_dense(s, ed):
+    from tests import gemm_bounds as GB
     from tests import gemm_f8_bounds as FB
     M, N, K = s["M"], s["N"], s["K"]
     o = FB.dense_operands(M, N, K, s["form"], ed)
@@ -237,7 +212,7 @@ def run_dense(s, ed):
         _check_q(r, d, q, c, ref, e)
         return r
     r, got = _run16(o, ed, M, N, K, c_rpb=s.get("c_rpb", 0))
-    r["ratio"], r["rel"] = FB.check(got, ref, e)
+    r["ratio"], r["rel"] = GB.check(got, ref, e)
     return r
 
 
@@ -245,7 +220,7 @@ def run_refusal(s, ed):
     """one broken argument of an otherwise valid 32 x 8 x 128 launch -> the status, and how much of the canary changed"""
     import torch
     from paddlemix_amd import _lib, ops
-    from tests import gemm_f8_bounds as FB
+    from tests.kernel_pieces import CANARY16, CANARY32, F8_NAN
     lib, st = _lib.load(), ops._stream()
     what = s["what"]
     M, N, K = 32, 8, 128
@@ -279,19 +254,19 @@ def run_refusal(s, ed):
     gate = torch.ones(4 * 64, device="cuda")
     res = torch.ones(4 * M * 64, device="cuda").to(ed)
     if q8:
-        bits = torch.full((4 * M * 64,), FB.F8_NAN, dtype=torch.uint8, device="cuda")
+        bits = torch.full((4 * M * 64,), F8_NAN, dtype=torch.uint8, device="cuda")
         cs = torch.full((M + 8,), CANARY32, dtype=torch.int32, device="cuda")
         rc = lib.mi355x_sd_linear_f8_q(A.data_ptr(), a["lda"], ones.data_ptr(), ones.data_ptr(), W.data_ptr(), ones.data_ptr(), 1.0,
                                        bits.data_ptr(), a["ldc"], cs.data_ptr(), M, a["N"], a["K"], None, 0.0, 0, st)
         torch.cuda.synchronize()
-        return dict(rc=rc, overwritten=int((bits != FB.F8_NAN).sum().item()) + int((cs != CANARY32).sum().item()))
-    bits = torch.full((4 * M * 64,), CANARY, dtype=torch.int16, device="cuda")
+        return dict(rc=rc, overwritten=int((bits != F8_NAN).sum().item()) + int((cs != CANARY32).sum().item()))
+    bits = torch.full((4 * M * 64,), CANARY16, dtype=torch.int16, device="cuda")
     rc = lib.mi355x_sd_linear_f8(A.data_ptr(), a["lda"], a["a_rpb"], a["a_bs"], ones.data_ptr(), W.data_ptr(), ones.data_ptr(),
                                  bits.data_ptr(), a["ldc"], a["c_rpb"], a["c_bs"], M, a["N"], a["K"], None,
                                  gate.data_ptr() if a["gate"] else None, 8 if a["gate"] else 0, a["rpb"],
                                  res.data_ptr() if a["res"] else None, a["ldr"], a["flags"], st)
     torch.cuda.synchronize()
-    r = dict(rc=rc, overwritten=int((bits != CANARY).sum().item()))
+    r = dict(rc=rc, overwritten=int((bits != CANARY16).sum().item()))
     if what == "K%128":   # through the wrapper: MI355XError
         try:
             ops.linear_f8(A[:M * 64].view(M, 64), ones[:M], W[:N * 64].view(N, 64), ones[:N])
@@ -301,23 +276,11 @@ def run_refusal(s, ed):
     return r
 
 
-def run_case(name, ed):
+def run_case(name):
+    from paddlemix_amd import _lib
     s = CASES[name]
-    return {"exact": run_exact, "dense": run_dense, "denseq": run_dense, "refuse": run_refusal}[s["cls"]](s, ed)
-
-
-def main(names):
-    import torch
-    from paddlemix_amd import _lib, ops
-    from tests.gpu_child import emit
-    ops.init(0)
-    ed = _lib.elem_dtype()
-    res = {}
-    for name in names or CASES:
-        res[name] = run_case(name, ed)
-        torch.cuda.empty_cache()
-    emit("F8_JSON", res)
+    return {"exact": run_exact, "dense": run_dense, "denseq": run_dense, "refuse": run_refusal}[s["cls"]](s, _lib.elem_dtype())
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(CASES, run_case, route_log=None, tag="F8_JSON", names=sys.argv[1:])

@@ -17,7 +17,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
+from tests import kernel_pieces as KP  # noqa: E402
+
 EXTRA = 154       # rows of other data between the batches of a remapped operand
 
 # ---- switch sets (debug-switch build) ----------------------------------------------------------------------------------------------
@@ -243,21 +244,19 @@ def run_case(name, ed):
         bk.update(gate=gt, rows_per_batch=rpb, residual=r)
     elif kind == "c-remap":   # batches of 77 rows written behind EXTRA other rows each
         nb = M // 77
-        buf = torch.full((nb * (77 + EXTRA) * N,), CANARY, device="cuda", dtype=torch.int16).view(ed)
-        ops.linear_ex(a, w, b, out=buf, c_rows_per_batch=77, c_batch_stride=(77 + EXTRA) * N, M=M)
-        v = buf.view(nb, 77 + EXTRA, N)
-        out = v[:, :77].reshape(M, N)
-        guard = int((v[:, 77:].view(torch.int16) != CANARY).sum().item())
+        og = KP.Guarded.strided((nb, 77, N), ((77 + EXTRA) * N, N, 1), 0, nb * (77 + EXTRA) * N, 16, dt=ed)
+        ops.linear_ex(a, w, b, out=og.buf, c_rows_per_batch=77, c_batch_stride=(77 + EXTRA) * N, M=M)
+        out = og.view.reshape(M, N)
+        guard = og.counts()[1]
     elif kind == "a-remap":   # A rows of batches of 77 read out of a buffer with EXTRA other rows behind each batch
         nb = M // 77
         abuf = torch.randn(nb * (77 + EXTRA) * K, device="cuda", generator=g).to(ed)
         out = ops.linear_ex(abuf, w, b, a_rows_per_batch=77, a_batch_stride=(77 + EXTRA) * K, M=M)
         a = abuf.view(nb, 77 + EXTRA, K)[:, :77].reshape(M, K)
     elif kind == "strided":
-        buf = torch.full((M + 40, N + 16), CANARY, device="cuda", dtype=torch.int16).view(ed)
-        out = ops.linear(a, w, b, out=buf[:M, :N])
-        bi = buf.view(torch.int16)
-        guard = int((bi[:M, N:] != CANARY).sum().item() + (bi[M:] != CANARY).sum().item())
+        og = KP.Guarded.block(M, N, 16, above=0, below=40, left=0, right=16, dt=ed)
+        out = ops.linear(a, w, b, out=og.view)
+        guard = og.counts()[1]
     elif kind.startswith("ln"):
         # the statistics the kernel reads: exact ones rounded to fp32 once (row_stats has its own bound, tests/norm_bounds.py)
         mean, var = a.double().mean(1), a.double().var(1, unbiased=False)
@@ -272,22 +271,12 @@ def run_case(name, ed):
     return out, GB.bound_check(out, a, w_ref, bias=b, **bk), guard
 
 
-def main(names):
-    import torch
-    from paddlemix_amd import _lib, ops
-    from tests.gpu_child import Routes, emit, sha
-    ops.init(0)
-    ed = _lib.elem_dtype()
-    routes = Routes("MI355X_SD_GEMM_LOG")
-    routes.take()
-    res = {}
-    for name in names or COMMON:
-        out, (ratio, rel), guard = run_case(name, ed)
-        res[name] = dict(sha=sha(out), ratio=ratio, rel=rel, guard=guard, route=routes.take())
-        del out
-        torch.cuda.empty_cache()
-    emit("LINEAR_JSON", res)
+def _result(name):
+    from paddlemix_amd import _lib
+    from tests.gpu_child import sha
+    out, (ratio, rel), guard = run_case(name, _lib.elem_dtype())
+    return dict(sha=sha(out), ratio=ratio, rel=rel, guard=guard)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(COMMON, _result, route_log="MI355X_SD_GEMM_LOG", tag="LINEAR_JSON", names=sys.argv[1:])

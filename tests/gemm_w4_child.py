@@ -15,9 +15,9 @@ import torch  # noqa: E402
 from paddlemix_amd import _lib, ops  # noqa: E402
 from paddlemix_amd.sd3 import dequantize_fp8_rows, quantize_fp8_rows  # noqa: E402
 from tests import gemm_bounds as GB  # noqa: E402
-from tests.gpu_child import Routes, emit, sha  # noqa: E402
+from tests import kernel_pieces as KP  # noqa: E402
+from tests.gpu_child import sha  # noqa: E402
 
-CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
 
 # name: (M, N, K, kind, picker) -- picker: the launch is one the picker gives the four-wave 256 x 256 tile (M >= 2048, N >= 1536,
 # >= 192 tiles of 256 x 256). kind: plain | nobias | scale | silu | gelu (tanh, linear_ex) | geglu | gate+R:<rows per batch> |
@@ -107,11 +107,10 @@ def run_case(name, ed):
         bk = dict(residual=r, out_scale=0.5)
     elif kind == "c-remap":   # batches of 256 rows written behind EXTRA other rows each
         nb = M // 256
-        buf = torch.full((nb * (256 + EXTRA) * N,), CANARY, device="cuda", dtype=torch.int16).view(ed)
-        ops.linear_ex(a, w, b, out=buf, c_rows_per_batch=256, c_batch_stride=(256 + EXTRA) * N, M=M)
-        v = buf.view(nb, 256 + EXTRA, N)
-        out = v[:, :256].reshape(M, N)
-        guard = int((v[:, 256:].view(torch.int16) != CANARY).sum().item())
+        og = KP.Guarded.strided((nb, 256, N), ((256 + EXTRA) * N, N, 1), 0, nb * (256 + EXTRA) * N, 16, dt=ed)
+        ops.linear_ex(a, w, b, out=og.buf, c_rows_per_batch=256, c_batch_stride=(256 + EXTRA) * N, M=M)
+        out = og.view.reshape(M, N)
+        guard = og.counts()[1]
     elif kind == "a-remap":   # A rows of batches of 256 read out of a buffer with EXTRA other rows behind each batch
         nb = M // 256
         abuf = torch.randn(nb * (256 + EXTRA) * K, device="cuda", generator=g).to(ed)
@@ -123,29 +122,19 @@ def run_case(name, ed):
         out = ops.linear_ex(a, w8, b, w_scale=ws, gelu_tanh=True)
         bk = dict(act="gelu_tanh")
     elif kind == "strided":
-        buf = torch.full((M + 256, N + 16), CANARY, device="cuda", dtype=torch.int16).view(ed)
-        out = ops.linear(a, w, b, out=buf[:M, :N])
-        bi = buf.view(torch.int16)
-        guard = int((bi[:M, N:] != CANARY).sum().item() + (bi[M:] != CANARY).sum().item())
+        og = KP.Guarded.block(M, N, 16, above=0, below=256, left=0, right=16, dt=ed)
+        out = ops.linear(a, w, b, out=og.view)
+        guard = og.counts()[1]
     else:
         raise ValueError(kind)
     torch.cuda.synchronize()
     return out, GB.bound_check(out, a, w_ref, bias=b, **bk), guard
 
 
-def main(names):
-    ops.init(0)
-    ed = _lib.elem_dtype()
-    routes = Routes("MI355X_SD_GEMM_LOG")
-    routes.take()
-    res = {}
-    for name in names or CASES:
-        out, (ratio, rel), guard = run_case(name, ed)
-        res[name] = dict(sha=sha(out), ratio=ratio, rel=rel, guard=guard, route=routes.take())
-        del out
-        torch.cuda.empty_cache()
-    emit("W4_JSON", res)
+def _result(name):
+    out, (ratio, rel), guard = run_case(name, _lib.elem_dtype())
+    return dict(sha=sha(out), ratio=ratio, rel=rel, guard=guard)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(CASES, _result, route_log="MI355X_SD_GEMM_LOG", tag="W4_JSON", names=sys.argv[1:])

@@ -88,6 +88,48 @@ class ChildRunner:
 RUNNER = ChildRunner()
 
 
+class Family:
+    """one kernel family's case-matrix child (tests/kernel_pieces.py run_cases) as its parent test file sees it: the script, the tag
+    of its JSON line, the route log of its debug build and its time limit, said once. Every child goes through RUNNER."""
+    def __init__(self, script, tag, route_log, timeout):
+        self.script, self.tag, self.route_log, self.timeout = script, tag, route_log, timeout
+
+    def spec(self, args=(), env_extra=None, dbg=False):
+        """RUNNER.run's arguments for one child (what RUNNER.run_many takes)"""
+        return dict(script=self.script, args=tuple(args), env_extra=env_extra or {}, tag=self.tag, timeout=self.timeout, dbg=dbg,
+                    route_log=self.route_log)
+
+    def child(self, args=(), env_extra=None, dbg=False):
+        return RUNNER.run(**self.spec(args, env_extra, dbg))
+
+    def run(self, dtype, names=(), env_extra=None):
+        """the matrix on one build: "bf16" is the debug-switch build with its route log, any other dtype the production library of
+        that element type, values only"""
+        if dtype == "bf16":
+            return self.child(names, env_extra, True)
+        return self.child(names, dict(env_extra or {}, MI355X_SD_DTYPE=dtype), False)
+
+    @staticmethod
+    def reached(got, key, declared, width):
+        """the set of instantiations the cases' route lines name (key: route line -> instantiation), with a printed count of the
+        cases that reach each declared one"""
+        per_case = [{key(ln) for ln in v["route"]} for v in got.values()]
+        for inst in declared:
+            print(f"{inst:<{width}} reached by {sum(inst in c for c in per_case)} cases")
+        return set().union(*per_case)
+
+    @staticmethod
+    def collect_failures(cases, got, check):
+        """the messages of the AssertionErrors check(name, got[name]) raises over all cases: one failing case does not hide the rest"""
+        bad = []
+        for name in cases:
+            try:
+                check(name, got[name])
+            except AssertionError as e:
+                bad.append(str(e))
+        return bad
+
+
 # ---- child side -------------------------------------------------------------------------------------------------------------------
 class Routes:
     """the lines the launchers appended to the route log that env_var names (MI355X_SD_GEMM_LOG, MI355X_SD_ATTN_LOG,

@@ -50,8 +50,10 @@ import math
 import numpy as np
 import torch
 
-U32 = 2.0 ** -24
-U_OUT = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10, torch.float32: 0.0}
+from tests import bound_pieces as BP
+from tests.bound_pieces import U32, fp32  # noqa: F401  (fp32: for the importers of this module)
+
+U_OUT = {**BP.U_OUT, torch.float32: 0.0}
 RSQ = 2 * U32        # v_rsq_f32 (1 ulp), or the double 1 / sqrt cast to fp32
 RCP = 2 * U32        # v_rcp_f32 (1 ulp)
 EXP_REL = 2.0 ** -21  # v_exp_f32
@@ -62,11 +64,6 @@ GN_ITERS_STATS, GNF_MAXD = 16, 24
 def gamma(n: int) -> float:
     """fp32 accumulation error factor of an n-deep chain of additions"""
     return n * U32 / (1 - n * U32)
-
-
-def fp32(x: float) -> float:
-    """the value a float argument of the C ABI arrives with"""
-    return float(np.float32(x))
 
 
 # ---- the launchers' geometry: longest fp32 chain L and NCH ------------------------------------------------------------------------
@@ -242,16 +239,9 @@ def fused_adaln_out(resi, scale, shift, rpb, weight, bias, eps, L):
 
 # ---- checks -------------------------------------------------------------------------------------------------------------------
 def check(out, ref, e, u_out=None):
-    """(worst |out - ref| / bound over every element, rel-L2); u_out defaults to the output's own (16-bit) rounding"""
-    u = U_OUT[out.dtype] if u_out is None else u_out
-    o = out.double()
-    err = (o - ref).abs()
-    bound = u * ref.abs() + (1 + u) * e + U32
-    ratio = (err / bound).max().item()
-    if not torch.isfinite(o).all() or ratio != ratio:
-        ratio = float("inf")
-    rel = ((o - ref).norm() / ref.norm().clamp_min(1e-300)).item()
-    return ratio, rel
+    """(worst |out - ref| / bound over every element, rel-L2); u_out defaults to the output's own rounding out of this module's
+    U_OUT: an fp32 output takes the 16-bit form at u = 0 (e + 2^-24). rel-L2's denominator is clamped at 1e-300."""
+    return BP.check(out, ref, e, u_out=U_OUT[out.dtype] if u_out is None else u_out, rel_floor=1e-300)
 
 
 def e4m3_value(q):

@@ -8,6 +8,7 @@ tensor the case checks -- what a comparison of two builds' bits reads.
 
   python tests/norm_child.py [case ...]     (no names: every case)
 """
+import functools
 import os
 import sys
 
@@ -17,11 +18,9 @@ import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import norm_bounds as NB  # noqa: E402
-from tests.gpu_child import Routes, emit, sha  # noqa: E402
+from tests import kernel_pieces as KP  # noqa: E402
+from tests.gpu_child import sha  # noqa: E402
 
-CANARY = 0x7FA5   # (a NaN bit pattern in bf16 and fp16: never a result)
-CANARY32 = 0x7FA5A5A5
-CANARY8 = 0xA5
 EPS = 1e-5
 CASES = {}        # name: (entry, spec, the route lines the log must show, without C)
 
@@ -171,43 +170,12 @@ _fa("fa constant rows", 5, 1024, False, False, "const", 3.0)
 
 # ---- buffers ------------------------------------------------------------------------------------------------------------------
 def _canary(shape, ld, kind):
-    """a [rows, C] (or [B, HW, C] with rows = B * HW) view with row stride ld inside a flat canary buffer with 3 extra rows:
-    (view, flat bits, mask of the view)"""
-    rows = 1
-    for s in shape[:-1]:
-        rows *= s
-    C = shape[-1]
-    n = (rows + 3) * ld + 64
-    if kind == 16:
-        bits = torch.full((n,), CANARY, dtype=torch.int16, device="cuda")
-        buf = bits.view(_lib.elem_dtype())
-    elif kind == 32:
-        bits = torch.full((n,), CANARY32, dtype=torch.int32, device="cuda")
-        buf = bits.view(torch.float32)
-    else:
-        bits = torch.full((n,), CANARY8, dtype=torch.uint8, device="cuda")
-        buf = bits
-    strides = tuple(ld * (shape[1] if len(shape) == 3 and i == 0 else 1) for i in range(len(shape) - 1)) + (1,)
-    view = buf.as_strided(shape, strides, 0)
-    inside = torch.zeros(n, dtype=torch.bool, device="cuda")
-    inside.as_strided(shape, strides, 0).fill_(True)
-    return view, bits, inside
+    """a [rows, C] or [B, HW, C] view with row stride ld in a flat canary buffer, 3 extra rows and 64 elements behind: (view, guard)"""
+    g = KP.Guarded.rows(shape, ld, kind, extra_rows=3, tail=64, dt=_lib.elem_dtype())
+    return g.view, g
 
 
-def _counts(bits, inside, canary):
-    return int(((bits == canary) & inside).sum().item()), int(((bits != canary) & ~inside).sum().item())
-
-
-def _nan_rows(vals, ld):
-    """vals [..., C] -> a view with row stride ld inside a NaN buffer (the gaps ld > C hold NaN)"""
-    shape = tuple(vals.shape)
-    C = shape[-1]
-    rows = vals.numel() // C
-    buf = torch.full((rows * ld + 64,), float("nan"), dtype=vals.dtype, device="cuda")
-    strides = tuple(ld * (shape[1] if len(shape) == 3 and i == 0 else 1) for i in range(len(shape) - 1)) + (1,)
-    view = buf.as_strided(shape, strides, 0)
-    view.copy_(vals)
-    return view
+_nan_rows = functools.partial(KP.nan_rows, tail=64)   # (vals [..., C], ld) -> a view with row stride ld in a NaN buffer, 64 NaN behind
 
 
 def _values(shape, kind, r, dt, g):
@@ -280,15 +248,15 @@ def run_case(name):
         gamma, beta = _gamma_beta(C, g, s["kind"] == "silu_big")
         ldx = C + (8 if entry == "gn" else 2)
         x = _nan_rows(vals, ldx)
-        y, ybits, yin = _canary((B, HW, C), C + 8, 16)
+        y, ybits = _canary((B, HW, C), C + 8, 16)
         if entry == "gn":
             ws = torch.empty(max(1, lib.mi355x_sd_groupnorm_workspace_floats(B, HW, C)), device="cuda")
             ss = torch.empty((B, 2, C), device="cuda")
             rc = lib.mi355x_sd_groupnorm_stats_ex(x.data_ptr(), B, HW, C, ldx, groups, EPS, gamma.data_ptr(), beta.data_ptr(),
                                                   ws.data_ptr(), ss.data_ptr(), 1 if s["xf32"] else 0, st)
-            raw = rbits = rin = None
+            raw = rbits = None
             if s["raw16"]:
-                raw, rbits, rin = _canary((B, HW, C), C + 16, 16)
+                raw, rbits = _canary((B, HW, C), C + 16, 16)
             rc = rc or lib.mi355x_sd_scale_shift_act_ex(x.data_ptr(), B, HW, C, ldx, ss.data_ptr(), 1 if s["silu"] else 0,
                                                         y.data_ptr(), C + 8, 1 if s["xf32"] else 0,
                                                         raw.data_ptr() if raw is not None else None, C + 16, st)
@@ -300,15 +268,15 @@ def run_case(name):
         torch.cuda.synchronize()
         res["rc"] = rc
         if s.get("refused"):   # nothing written anywhere
-            res["unwritten"], res["overwritten"] = 0, int((ybits != CANARY).sum().item())
+            res["unwritten"], res["overwritten"] = 0, int((ybits.bits != ybits.canary).sum().item())
             return res
         ref, e = NB.groupnorm(vals, gamma, beta, groups, EPS, s["silu"], L=L)
         res["ratio"], res["rel"] = NB.check(y, ref, e)
-        res["unwritten"], res["overwritten"] = _counts(ybits, yin, CANARY)
+        res["unwritten"], res["overwritten"] = ybits.counts()
         res["sha"] = {"y": sha(y)}
         if entry == "gn" and s["raw16"]:
             res["sha"]["raw16"] = sha(raw)
-            uw, ow = _counts(rbits, rin, CANARY)
+            uw, ow = rbits.counts()
             res["unwritten"] += uw
             res["overwritten"] += ow
             res["raw16_exact"] = bool(torch.equal(raw.contiguous().view(torch.int16), vals.to(ed).view(torch.int16)))
@@ -320,38 +288,38 @@ def run_case(name):
         vals = _values((rows, C), s["kind"], s["r"], xdt, g)
         gamma, beta = _gamma_beta(C, g) if s["affine"] else (None, None)
         x = _nan_rows(vals, C + 16)
-        y, bits, inside = _canary((rows, C), C + 8, 16)
+        y, bits = _canary((rows, C), C + 8, 16)
         res["rc"] = lib.mi355x_sd_layernorm_ex(x.data_ptr(), rows, C, C + 16, ops._p(gamma), ops._p(beta), EPS, y.data_ptr(), C + 8,
                                                1 if s["xf32"] else 0, st)
         torch.cuda.synchronize()
         res["sha"] = {"y": sha(y)}
         ref, e = NB.layernorm(vals, gamma, beta, EPS, NB.chain_rows("layernorm", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
-        res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
+        res["unwritten"], res["overwritten"] = bits.counts()
         if s["kind"] == "const":   # z' = 0 exactly: y = beta
             want = (beta if beta is not None else torch.zeros(C, device="cuda")).to(ed).expand(rows, C)
             res["exact"] = bool(torch.equal(y.contiguous().view(torch.int16), want.contiguous().view(torch.int16)))
     elif entry == "rs":
         vals = _values((rows, C), s["kind"], s["r"], ed, g)
         x = _nan_rows(vals, C + 8)
-        y, bits, inside = _canary((rows, 2), 2, 32)
+        y, bits = _canary((rows, 2), 2, 32)
         res["rc"] = lib.mi355x_sd_row_stats(x.data_ptr(), rows, C, C + 8, EPS, y.data_ptr(), st)
         torch.cuda.synchronize()
         res["sha"] = {"stats": sha(y)}
         ref, e = NB.row_stats(vals, EPS, NB.chain_rows("row_stats", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e, u_out=0.0)
-        res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY32)
+        res["unwritten"], res["overwritten"] = bits.counts()
     elif entry == "rms":
         vals = _values((rows, C), s["kind"], s["r"], ed, g)
         w = (1 + 0.3 * torch.randn(C, generator=g, device="cuda")).float()
         x = _nan_rows(vals, C + 24)
-        y, bits, inside = _canary((rows, C), C + 8, 16)
+        y, bits = _canary((rows, C), C + 8, 16)
         res["rc"] = lib.mi355x_sd_rmsnorm(x.data_ptr(), rows, C, C + 24, w.data_ptr(), 1e-6, y.data_ptr(), C + 8, st)
         torch.cuda.synchronize()
         res["sha"] = {"y": sha(y)}
         ref, e = NB.rmsnorm(vals, w, 1e-6, NB.chain_rows("rmsnorm", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
-        res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
+        res["unwritten"], res["overwritten"] = bits.counts()
         if s["kind"] == "zero_row":
             res["exact"] = bool((y[1::2].float() == 0).all().item())
     elif entry == "ad":
@@ -360,14 +328,14 @@ def run_case(name):
         vals = _values((rows, C), s["kind"], s["r"], ed, g)
         x = _nan_rows(vals, C + 8)
         sc, sh = _mod(nb, C, s["m16"], g), _mod(nb, C, s["m16"], g, scale=2.0)
-        y, bits, inside = _canary((rows, C), C + 8, 16)
+        y, bits = _canary((rows, C), C + 8, 16)
         res["rc"] = lib.mi355x_sd_adaln_ex(x.data_ptr(), rows, C, C + 8, sc.data_ptr(), sh.data_ptr(), sc.stride(0),
                                            _lib.MOD_ELEM if s["m16"] else _lib.MOD_F32, rpb, 1e-6, y.data_ptr(), C + 8, st)
         torch.cuda.synchronize()
         res["sha"] = {"y": sha(y)}
         ref, e = NB.adaln(vals, sc, sh, rpb, 1e-6, NB.chain_rows("adaln", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
-        res["unwritten"], res["overwritten"] = _counts(bits, inside, CANARY)
+        res["unwritten"], res["overwritten"] = bits.counts()
         if s["kind"] == "const":   # y = shift[b]
             want = sh.to(ed)[torch.arange(rows, device="cuda") // rpb]
             res["exact"] = bool(torch.equal(y.contiguous().view(torch.int16), want.contiguous().view(torch.int16)))
@@ -377,11 +345,11 @@ def run_case(name):
         vals = _values((rows, C), s["kind"], s["r"], ed, g)
         x = _nan_rows(vals, C + 8)
         sc, sh = _mod(nb, C, False, g), _mod(nb, C, False, g, scale=2.0)
-        y8, bits, inside = _canary((rows, C), C + 16, 8)
-        qs, qbits, qin = _canary((rows, 1), 1, 32)
-        l2 = l2bits = l2in = None
+        y8, bits = _canary((rows, C), C + 16, 8)
+        qs, qbits = _canary((rows, 1), 1, 32)
+        l2 = l2bits = None
         if s["l2"]:
-            l2, l2bits, l2in = _canary((rows, 1), 1, 32)
+            l2, l2bits = _canary((rows, 1), 1, 32)
         res["rc"] = lib.mi355x_sd_adaln_f8(x.data_ptr(), rows, C, C + 8, sc.data_ptr(), sh.data_ptr(), sc.stride(0), rpb, 1e-6,
                                            y8.data_ptr(), C + 16, qs.data_ptr(), l2.data_ptr() if l2 is not None else None, st)
         torch.cuda.synchronize()
@@ -391,9 +359,9 @@ def run_case(name):
         ref, e = NB.adaln_pre(vals, sc, sh, rpb, 1e-6, NB.chain_rows("adaln_f8", C))
         r_val, r_qs, r_l2, nan = NB.check_f8(y8, qs[:, 0], l2[:, 0] if l2 is not None else None, ref, e)
         res["ratio"], res["ratio_qs"], res["ratio_l2"], res["nan_bytes"] = r_val, r_qs, r_l2, nan
-        res["unwritten"] = _counts(qbits, qin, CANARY32)[0] + (_counts(l2bits, l2in, CANARY32)[0] if l2 is not None else 0)
-        res["overwritten"] = (_counts(bits, inside, CANARY8)[1] + _counts(qbits, qin, CANARY32)[1]
-                              + (_counts(l2bits, l2in, CANARY32)[1] if l2 is not None else 0))
+        res["unwritten"] = qbits.counts()[0] + (l2bits.counts()[0] if l2 is not None else 0)
+        res["overwritten"] = (bits.counts()[1] + qbits.counts()[1]
+                              + (l2bits.counts()[1] if l2 is not None else 0))
     elif entry == "q8":
         rpb = s["rpb"]
         vals = _values((rows, C), s["kind"], s["r"], ed, g)
@@ -407,8 +375,8 @@ def run_case(name):
         else:
             x = _nan_rows(vals, C + 8)
             xp, ldx, bst = x.data_ptr(), C + 8, 0
-        y8, bits, inside = _canary((rows, C), C + 8, 8)
-        qs, qbits, qin = _canary((rows, 1), 1, 32)
+        y8, bits = _canary((rows, C), C + 8, 8)
+        qs, qbits = _canary((rows, 1), 1, 32)
         res["rc"] = lib.mi355x_sd_quantize_rows(xp, rows, C, ldx, rpb, bst, y8.data_ptr(), C + 8, qs.data_ptr(), st)
         torch.cuda.synchronize()
         res["sha"] = {"y8": sha(y8), "yscale": sha(qs)}
@@ -418,8 +386,8 @@ def run_case(name):
         res["exact_scale_off"] = int((qs[:, 0].cpu() != qs_ref).sum().item())
         res["nan_bytes"] = int(((got & 0x7F) == 0x7F).sum().item())
         res["ratio"], _, _, _ = NB.check_f8(y8, qs[:, 0], None, vals.double(), torch.zeros_like(vals, dtype=torch.float64))
-        res["unwritten"] = _counts(qbits, qin, CANARY32)[0]
-        res["overwritten"] = _counts(bits, inside, CANARY8)[1] + _counts(qbits, qin, CANARY32)[1]
+        res["unwritten"] = qbits.counts()[0]
+        res["overwritten"] = bits.counts()[1] + qbits.counts()[1]
     elif entry == "fa":
         rpb = s["rpb"]
         nb = (rows + rpb - 1) // rpb
@@ -431,8 +399,8 @@ def run_case(name):
         if s["affine"]:
             mdt = ed if s["m16"] else torch.float32
             w, b = (1 + 0.3 * torch.randn(C, generator=g, device="cuda")).to(mdt), (0.3 * torch.randn(C, generator=g, device="cuda")).to(mdt)
-        resi, rbits, rin = _canary((rows, C), C + 8, 16)
-        y, bits, inside = _canary((rows, C), C + 24, 16)
+        resi, rbits = _canary((rows, C), C + 8, 16)
+        y, bits = _canary((rows, C), C + 24, 16)
         res["rc"] = lib.mi355x_sd_fused_adaln_scale_residual_ex(
             x.data_ptr(), C + 8, mha.data_ptr(), C + 16, gate.data_ptr(), sc.data_ptr(), sh.data_ptr(), gate.stride(0),
             _lib.MOD_ELEM if s["m16"] else _lib.MOD_F32, rpb, ops._p(w), ops._p(b), EPS, rows, C, resi.data_ptr(), C + 8,
@@ -443,8 +411,8 @@ def run_case(name):
         res["ratio_resi"], _ = NB.check(resi, rref, re_)
         ref, e = NB.fused_adaln_out(resi.float(), sc, sh, rpb, w, b, EPS, NB.chain_rows("fused_adaln", C))
         res["ratio"], res["rel"] = NB.check(y, ref, e)
-        uw, ow = _counts(bits, inside, CANARY)
-        uw2, ow2 = _counts(rbits, rin, CANARY)
+        uw, ow = bits.counts()
+        uw2, ow2 = rbits.counts()
         res["unwritten"], res["overwritten"] = uw + uw2, ow + ow2
         if s["kind"] == "const":   # mha = 0: resi = x, z' = 0, y = shift[b]
             want = sh.to(ed)[torch.arange(rows, device="cuda") // rpb]
@@ -452,18 +420,5 @@ def run_case(name):
     return res
 
 
-def main(names):
-    ops.init(0)
-    routes = Routes("MI355X_SD_NORM_LOG")
-    routes.take()
-    res = {}
-    for name in names or CASES:
-        r = run_case(name)
-        r["route"] = routes.take()
-        res[name] = r
-        torch.cuda.empty_cache()
-    emit("NORM_JSON", res)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(CASES, run_case, route_log="MI355X_SD_NORM_LOG", tag="NORM_JSON", names=sys.argv[1:])

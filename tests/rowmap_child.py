@@ -8,6 +8,7 @@ case the worst err / bound or the number of differing elements, and the unwritte
 
   python tests/rowmap_child.py [case ...]     (no names: every case)
 """
+import functools
 import os
 import sys
 
@@ -17,8 +18,7 @@ import torch  # noqa: E402
 
 from paddlemix_amd import _lib, ops  # noqa: E402
 from tests import rowmap_bounds as RB  # noqa: E402
-from tests.gpu_child import emit  # noqa: E402
-from tests.norm_child import CANARY, CANARY32, _canary, _counts, _nan_rows  # noqa: E402
+from tests import kernel_pieces as KP  # noqa: E402
 
 CASES = {}   # name: (family, spec)
 F32 = torch.float32
@@ -93,6 +93,15 @@ for n in (77, 300, _over("mask_to_bias", 77)):
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------------
+def _canary(shape, ld, kind):
+    """a [rows, C] or [B, HW, C] view with row stride ld in a flat canary buffer, 3 extra rows and 64 elements behind: (view, guard)"""
+    g = KP.Guarded.rows(shape, ld, kind, extra_rows=3, tail=64, dt=_lib.elem_dtype())
+    return g.view, g
+
+
+_nan_rows = functools.partial(KP.nan_rows, tail=64)   # (vals [..., C], ld) -> a view with row stride ld in a NaN buffer, 64 NaN behind
+
+
 def _flat_in(vals):
     """a flat floating-point input followed by NaN (an empty input: a valid pointer to NaN alone)"""
     if vals.numel() == 0:
@@ -101,12 +110,12 @@ def _flat_in(vals):
 
 
 def _flat_out(n, kind):
-    view, bits, inside = _canary((1, n), n, kind)
-    return view[0], bits, inside
+    view, g = _canary((1, n), n, kind)
+    return view[0], g
 
 
-def _tally(res, bits, inside, canary):
-    uw, ow = _counts(bits, inside, canary)
+def _tally(res, g):
+    uw, ow = g.counts()
     res["unwritten"] = res.get("unwritten", 0) + uw
     res["overwritten"] = res.get("overwritten", 0) + ow
 
@@ -135,23 +144,23 @@ def run_case(name):
         x = _flat_in(vals)
         if s["n"] == "sweep" and idt == odt:   # the wrapper's own path (same dtype in and out); its output has no canary
             y0 = ops.silu(x.clone())
-        y, bits, inside = _flat_out(vals.numel(), 32 if s["out_f32"] else 16)
+        y, bits = _flat_out(vals.numel(), 32 if s["out_f32"] else 16)
         res["rc"] = lib.mi355x_sd_silu(x.data_ptr(), y.data_ptr(), vals.numel(), s["in_f32"], s["out_f32"], st)
         torch.cuda.synchronize()
         ref, e = RB.act("silu", vals.double())
         res["ratio"] = RB.check(y, ref, e)
         if s["n"] == "sweep" and idt == odt:
             res["wrapper_off"] = RB.exact_off(y0, y.clone())
-        _tally(res, bits, inside, CANARY32 if s["out_f32"] else CANARY)
+        _tally(res, bits)
     elif fam == "act":
         vals = RB.sweep16(ed, "cuda") if s["n"] == "sweep" else _randn(s["n"], g, 3.0).to(ed)
         x = _flat_in(vals)
-        y, bits, inside = _flat_out(vals.numel(), 16)
+        y, bits = _flat_out(vals.numel(), 16)
         res["rc"] = lib.mi355x_sd_activation(x.data_ptr(), y.data_ptr(), vals.numel(), RB.KINDS[s["kind"]], st)
         torch.cuda.synchronize()
         ref, e = RB.act(s["kind"], vals.double())
         res["ratio"] = RB.check(y, ref, e)
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam == "gated":
         F = s["F"]
         if s["rows"] == "sweep":
@@ -163,31 +172,31 @@ def run_case(name):
             a, b = _randn((s["rows"], F), g, 3.0).to(ed), _randn((s["rows"], F), g, 2.0).to(ed)
         rows = a.shape[0]
         x = _nan_rows(torch.cat([a, b], 1), 2 * F + s["xpad"])
-        y, bits, inside = _canary((rows, F), F + 8, 16)
+        y, bits = _canary((rows, F), F + 8, 16)
         res["rc"] = lib.mi355x_sd_gated_activation(x.data_ptr(), x.stride(0), y.data_ptr(), F + 8, rows, F, RB.KINDS[s["kind"]], st)
         torch.cuda.synchronize()
         ref, e = RB.gated(s["kind"], a.double(), b.double())
         res["ratio"] = RB.check(y, ref, e)
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
         if s["xpad"] == 0:   # the wrapper's compact call is the same launch
             res["wrapper_off"] = RB.exact_off(ops.gated_activation(x, s["kind"]), y.contiguous())
     elif fam == "softmax":
         vals = RB.softmax_rows_input(s["n"], "cuda")
         x = _nan_rows(vals, s["n"] + 12)
-        y, bits, inside = _canary(tuple(vals.shape), s["n"] + 8, 16)
+        y, bits = _canary(tuple(vals.shape), s["n"] + 8, 16)
         ops.softmax_rows(x, out=y)
         torch.cuda.synchronize()
         res["rc"] = 0
         ref, e = RB.softmax(vals)
         res["ratio"] = RB.check(y, ref, e)
         res["wrapper_off"] = RB.exact_off(ops.softmax_rows(vals), y.contiguous())   # compact rows: the same bits
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam == "temb":
         dim, group = s["dim"], s.get("group", 1)
         t = torch.tensor(s.get("t", TS), dtype=F32, device="cuda")
         n = s.get("n", t.numel())
         ldo = group * dim + (8 if group == 1 else 40)
-        y, bits, inside = _canary((n // group, group * dim), ldo, 16)
+        y, bits = _canary((n // group, group * dim), ldo, 16)
         tin = _flat_in(t)
         args = (s["flip"], s["shift"], s.get("scale", 1.0), s.get("period", 10000.0))
         res["rc"] = lib.mi355x_sd_timestep_embedding(tin.data_ptr(), t.numel(), n, dim, group, *args, y.data_ptr(), ldo, st)
@@ -200,7 +209,7 @@ def run_case(name):
         if group == 1 and t.numel() == n:   # the wrapper's compact call
             res["wrapper_off"] = RB.exact_off(ops.timestep_embedding(t, dim, bool(s["flip"]), s["shift"], s.get("scale", 1.0),
                                                                      s.get("period", 10000.0)), got.contiguous())
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam in ("axpby", "cfg"):
         n = s["n"]
         coef = _flat_in(torch.tensor(s["coef"], dtype=F32, device="cuda"))
@@ -208,7 +217,7 @@ def run_case(name):
         if fam == "axpby":
             yv = xv * (1 + 2.0 ** -12 * _randn(n, g)) if s["kind"] == "cancel" else _randn(n, g)
             yin = _flat_in(yv)
-            out, bits, inside = _flat_out(n, 32)
+            out, bits = _flat_out(n, 32)
             if s["alias"]:   # out = x, as the benchmark's denoising loop updates its latents
                 out.copy_(xv)
                 xin = out
@@ -223,13 +232,13 @@ def run_case(name):
                 uv = xv * (1 + 2.0 ** -12 * _randn(n, g))   # coefficients of opposite sign, cancelling operands
             both = _flat_in(torch.cat([uv, tv]))
             xin = _flat_in(xv)
-            out, bits, inside = _flat_out(n, 32)
+            out, bits = _flat_out(n, 32)
             res["rc"] = lib.mi355x_sd_cfg_axpby(xin.data_ptr(), both.data_ptr(), both.data_ptr() + 4 * n, out.data_ptr(),
                                                 coef.data_ptr(), s["gs"], n, st)
             ref, e = RB.cfg_axpby(xv, uv, tv, coef, s["gs"])
         torch.cuda.synchronize()
         res["ratio"] = RB.check(out, ref, e)
-        _tally(res, bits, inside, CANARY32)
+        _tally(res, bits)
     elif fam == "latent":
         B, L, HW = s["B"], s["L"], s["HW"]
         mv = torch.cat([_randn((B * HW, L), g, 3.0), _randn((B * HW, L), g, 20.0)], 1)
@@ -249,8 +258,8 @@ def run_case(name):
             res["ratio"] = RB.check(got[2], *RB.latent_sample(mv, B, L, nv, 0.18215))
         else:
             res["off"] += RB.exact_off(got[2], mode)
-        for _, bits, inside in outs:
-            _tally(res, bits, inside, CANARY32)
+        for _, bits in outs:
+            _tally(res, bits)
     elif fam in ("copy", "cast"):
         rows, C = s["rows"], s["C"]
         if fam == "copy":
@@ -260,36 +269,36 @@ def run_case(name):
             vals[0, :8] = torch.tensor([float("inf"), -float("inf"), 3.4e38, 65520.0, 65519.9, 2.0 ** -25, 1.5 * 2.0 ** -24, -0.0],
                                        device="cuda")
         x = _nan_rows(vals, C + 16)
-        y, bits, inside = _canary((rows, C), C + 8, 16)
+        y, bits = _canary((rows, C), C + 8, 16)
         fn = lib.mi355x_sd_copy_rows if fam == "copy" else lib.mi355x_sd_cast_rows
         res["rc"] = fn(x.data_ptr(), C + 16, y.data_ptr(), C + 8, rows, C, st)
         torch.cuda.synchronize()
         res["off"] = RB.exact_off(y, vals.to(ed))
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam == "patchify":
         B, C, H, W, p = s["B"], s["C"], s["H"], s["W"], s["p"]
         K, rows = C * p * p, B * (H // p) * (W // p)
         xv = RB.codes(B * C * H * W, ed, "cuda").float().reshape(B, C, H, W)
         x = _flat_in(xv).reshape(B, C, H, W)
-        y, bits, inside = _canary((rows, K), K + s["pad"], 16)
+        y, bits = _canary((rows, K), K + s["pad"], 16)
         res["rc"] = lib.mi355x_sd_patchify(x.data_ptr(), B, C, H, W, p, y.data_ptr(), K + s["pad"], st)
         torch.cuda.synchronize()
         res["off"] = RB.exact_off(y, RB.patchify(xv, p, ed))
         if s["pad"] == 0:
             res["wrapper_off"] = RB.exact_off(ops.patchify(xv, p), y.contiguous())
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam == "unpatchify":
         B, C, H, W, p = s["B"], s["C"], s["H"], s["W"], s["p"]
         K, rows = C * p * p, B * (H // p) * (W // p)
         xv = RB.codes(rows * K, ed, "cuda").reshape(rows, K)
         x = _nan_rows(xv, K + s["pad"])
-        y, bits, inside = _flat_out(B * C * H * W, 32)
+        y, bits = _flat_out(B * C * H * W, 32)
         res["rc"] = lib.mi355x_sd_unpatchify(x.data_ptr(), K + s["pad"], B, C, H, W, p, y.data_ptr(), st)
         torch.cuda.synchronize()
         want = RB.unpatchify(xv, B, C, H, W, p)
         res["off"] = RB.exact_off(y.reshape(B, C, H, W), want)
         res["wrapper_off"] = RB.exact_off(ops.unpatchify(x, B, C, H, W, p), want)
-        _tally(res, bits, inside, CANARY32)
+        _tally(res, bits)
     elif fam == "split":
         B, S1, S2, C = s["B"], s["S1"], s["S2"], s["C"]
         allv = RB.codes(B * (S1 + S2) * 3 * C, ed, "cuda")
@@ -302,8 +311,8 @@ def run_case(name):
         res["off"] = sum(RB.exact_off(o[0].reshape(B, S1 + S2, C), w) for o, w in zip(outs, want))
         if S1 and S2:
             res["wrapper_off"] = sum(RB.exact_off(a, w) for a, w in zip(ops.split_concat(xv, yv), want))
-        for _, bits, inside in outs:
-            _tally(res, bits, inside, CANARY)
+        for _, bits in outs:
+            _tally(res, bits)
     elif fam == "embed":
         n, seq, V, D = s["n"], s["seq"], s["V"], s["D"]
         ids = torch.randint(0, V, (n,), generator=g, device="cuda").to(torch.int32)
@@ -319,14 +328,14 @@ def run_case(name):
             tok[0, 0] = -0.0   # float(-0) + 0 = +0
         tk = _nan_rows(tok, D)
         ps = _nan_rows(pos, D) if s["mode"] != "tok" else None
-        y, bits, inside = _canary((n, D), D + 8, 16)
+        y, bits = _canary((n, D), D + 8, 16)
         res["rc"] = lib.mi355x_sd_embed_tokens(ids.data_ptr(), n, seq, tk.data_ptr(), ops._p(ps), D, y.data_ptr(), D + 8, st)
         torch.cuda.synchronize()
         want = RB.embed_tokens(ids, tok, pos if ps is not None else None, seq)
         res["off"] = RB.exact_off(y, want)
         if ps is not None:
             res["wrapper_off"] = RB.exact_off(ops.embed_tokens(ids, tk, ps, seq), want)
-        _tally(res, bits, inside, CANARY)
+        _tally(res, bits)
     elif fam == "add":
         B, C, HW, xf32 = s["B"], s["C"], s["HW"], s["xf32"]
         xdt = F32 if xf32 else ed
@@ -335,38 +344,33 @@ def run_case(name):
             rv = RB.codes(B * C * HW, ed, "cuda").float().reshape(B, C, HW)
         else:
             xv, rv = _randn((B, HW, C), g, 3.0).to(xdt), _randn((B, C, HW), g)
-        x, bits, inside = _canary((B, HW, C), C + s["pad"], 32 if xf32 else 16)
+        x, bits = _canary((B, HW, C), C + s["pad"], 32 if xf32 else 16)
         x.copy_(xv)
         r = _flat_in(rv)
         res["rc"] = lib.mi355x_sd_add_nchw_ex(x.data_ptr(), C + s["pad"], r.data_ptr(), B, C, HW, xf32, st)
         torch.cuda.synchronize()
         res["off"] = RB.exact_off(x, RB.add_nchw(xv, rv))
-        _tally(res, bits, inside, CANARY32 if xf32 else CANARY)
+        _tally(res, bits)
     elif fam == "mask":
         n = s["n"]
         mv = (torch.rand(n, generator=g, device="cuda") < 0.5).float()
         mv[:8] = torch.tensor([0.0, 1.0, 0.5, 0.3, -0.0, 1e-8, 0.999999, 2.0], device="cuda")
         m = _flat_in(mv)
-        y, bits, inside = _flat_out(n, 32)
+        y, bits = _flat_out(n, 32)
         res["rc"] = lib.mi355x_sd_mask_to_bias(m.data_ptr(), y.data_ptr(), n, st)
         torch.cuda.synchronize()
         res["off"] = RB.exact_off(y, RB.mask_to_bias(mv))
-        _tally(res, bits, inside, CANARY32)
+        _tally(res, bits)
     return res
 
 
-def main(names):
-    ops.init(0)
-    res = {}
-    for name in names or CASES:
-        try:
-            res[name] = run_case(name)
-        except (ValueError, TypeError, IndexError, ZeroDivisionError, AssertionError, _lib.MI355XError) as ex:
-            # a refusal or a mistake of the case's own host code: reported as that case's failure (a device error ends the child)
-            res[name] = {"error": f"{type(ex).__name__}: {ex}"}
-        torch.cuda.empty_cache()
-    emit("ROWMAP_JSON", res)
+def _case_or_error(name):
+    try:
+        return run_case(name)
+    except (ValueError, TypeError, IndexError, ZeroDivisionError, AssertionError, _lib.MI355XError) as ex:
+        # a refusal or a mistake of the case's own host code: reported as that case's failure (a device error ends the child)
+        return {"error": f"{type(ex).__name__}: {ex}"}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    KP.run_cases(CASES, _case_or_error, route_log=None, tag="ROWMAP_JSON", names=sys.argv[1:])

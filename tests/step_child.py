@@ -9,7 +9,8 @@ import torch
 
 from paddlemix_amd import _lib, ops
 from tests.gpu_child import emit
-from tests.norm_child import CANARY32, _counts
+from tests.kernel_pieces import CANARY32
+from tests.kernel_pieces import counts as _counts
 from tests.step_forms import TAIL
 
 PAD = 64   # elements (256 bytes) of canary / NaN in front of and behind every view

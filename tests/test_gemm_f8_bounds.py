@@ -6,6 +6,7 @@ never the bound."""
 import pytest
 import torch
 
+from tests import gemm_bounds as GB
 from tests import gemm_f8_bounds as FB
 from tests.gemm_f8_child import CASES
 
@@ -87,7 +88,7 @@ def test_class_1_preconditions_of_every_committed_case(name):
 @pytest.mark.parametrize("form", ["", "bias", "bias+gelu", "gate", "gate+gelu"])
 def test_class_2_correct_emulation_stays_below_half_the_bound(ed, form):
     o = FB.dense_operands(M, N, K, form, ed)
-    ratio, rel = FB.check(_emu(o, ed), *_ref(o))
+    ratio, rel = GB.check(_emu(o, ed), *_ref(o))
     assert ratio < 0.5, ratio
     assert rel < (4e-3 if ed == torch.bfloat16 else 6e-4)
 
@@ -144,7 +145,7 @@ CLASS2_FAULTS = [("swap_chunks_a", ""), ("drop_last_ktile", "bias"), ("a_scale_n
 @pytest.mark.parametrize("fault,form", CLASS2_FAULTS)
 def test_class_2_catches_each_planted_mistake(ed, fault, form):
     o = FB.dense_operands(M, N, K, form, ed)
-    ratio, _ = FB.check(_emu(o, ed, fault=fault), *_ref(o))
+    ratio, _ = GB.check(_emu(o, ed, fault=fault), *_ref(o))
     assert ratio > 1.0, ratio
 
 
@@ -170,7 +171,7 @@ def test_a_remap_is_followed_and_ignoring_the_batch_stride_is_caught(seg, mirror
     assert FB.exact_off(FB.emulate(buf, o["sa"], o["qw"], o["sw"], ed, a_remap=rm, fault="a_remap_no_stride"), ref) > 0
     d = FB.dense_operands(40, N, K, "", ed)
     buf, rm = _remapped(d, seg)
-    ratio, _ = FB.check(FB.emulate(buf, d["sa"], d["qw"], d["sw"], ed, a_remap=rm, fault="a_remap_no_stride"), *_ref(d))
+    ratio, _ = GB.check(FB.emulate(buf, d["sa"], d["qw"], d["sw"], ed, a_remap=rm, fault="a_remap_no_stride"), *_ref(d))
     assert ratio > 1.0
 
 

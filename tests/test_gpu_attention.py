@@ -6,7 +6,7 @@ named for and that the cases together reach every instantiation, once on the IEE
 import pytest
 
 from tests.attn_child import CASES
-from tests.gpu_child import RUNNER
+from tests.gpu_child import Family
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +25,15 @@ INSTANTIATIONS = [
 NOM16 = [n for n in CASES if n.startswith("nom16")]
 
 
-def _child(env_extra, names, dbg):
-    return RUNNER.run("attn_child.py", names, env_extra, tag="ATTN_JSON", timeout=900, dbg=dbg, route_log="MI355X_SD_ATTN_LOG")
+FAMILY = Family("attn_child.py", "ATTN_JSON", "MI355X_SD_ATTN_LOG", timeout=900)
 
 
 def _run(dtype):
     """every case's result; a child runs once (tests/gpu_child.py: a failed child is remembered, not run again per test)"""
     if dtype == "bf16":
-        got = _child({}, [n for n in CASES if n not in NOM16], True)
-        return dict(got, **_child({"MI355X_SD_ATTN_NO_M16": "1"}, NOM16, True))   # (started only after the first child gave its result)
-    return _child({"MI355X_SD_DTYPE": dtype}, [], False)
+        got = FAMILY.run("bf16", [n for n in CASES if n not in NOM16])
+        return dict(got, **FAMILY.run("bf16", NOM16, {"MI355X_SD_ATTN_NO_M16": "1"}))   # (started only after the first child gave its result)
+    return FAMILY.run(dtype)
 
 
 def _check(name, v, rel_bar):
@@ -63,10 +62,7 @@ def test_case_meets_the_fp64_bound_on_its_route(name):
 
 def test_every_launch_dp_instantiation_is_reached():
     got = _run("bf16")
-    reached = {v["route"][0].split()[-1] for v in got.values() if v["route"]}
-    for fam in INSTANTIATIONS:
-        n = sum(1 for v in got.values() if v["route"] and v["route"][0].split()[-1] == fam)
-        print(f"{fam:<20} reached by {n} cases")
+    reached = FAMILY.reached(got, lambda ln: ln.split()[-1], INSTANTIATIONS, width=20)
     assert set(INSTANTIATIONS) <= reached, sorted(set(INSTANTIATIONS) - reached)
     assert reached <= set(INSTANTIATIONS), sorted(reached - set(INSTANTIATIONS))
 
@@ -75,12 +71,9 @@ def test_fp16_build_meets_the_fp64_bound():
     """The IEEE-half build on the same matrix: the float64 bound at u_out = 2^-10, u_p = 2^-11 over the whole output. (No route log
     in the production library: the debug build shares the dispatch code, and the tests above prove the routes.)"""
     got = _run("fp16")
-    bad = []
-    for name in CASES:
-        v = got[name]
+    def check(name, v):
         print(f"fp16 {name:<36} err/bound {v['ratio']:.3f}  rel {v['rel']:.2e}")
-        try:
-            _check(name, v, 6e-4)   # (fp16 bar of tests/test_gpu_fp16.py: fp32 accumulation, one fp16 rounding)
-        except AssertionError as e:
-            bad.append(str(e))
+        _check(name, v, 6e-4)   # (fp16 bar of tests/test_gpu_fp16.py: fp32 accumulation, one fp16 rounding)
+
+    bad = FAMILY.collect_failures(CASES, got, check)
     assert not bad, bad

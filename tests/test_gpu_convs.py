@@ -10,7 +10,7 @@ run names or its tabled fallback. The three direct kernels of csrc/misc.hip have
 import pytest
 
 from tests.conv_cases import CASES, GEOMS, out_hw
-from tests.gpu_child import RUNNER
+from tests.gpu_child import RUNNER, Family
 
 pytestmark = pytest.mark.gpu
 WS_BYTES = 32 << 20   # the split-K scratch ops.conv3x3 hands over (paddlemix_amd/ops.py _workspace)
@@ -18,9 +18,11 @@ WS_BYTES = 32 << 20   # the split-K scratch ops.conv3x3 hands over (paddlemix_am
 FORCED_BASE = {"MI355X_SD_GEMM_NO_BIAS_ACC": "1"}
 
 
+CHILD = Family("conv_child.py", "CONV_JSON", "MI355X_SD_GEMM_LOG", timeout=600)
+
+
 def _spec(mode, env_extra, names=(), dbg=True):
-    return dict(script="conv_child.py", args=(mode, *names), env_extra=env_extra, tag="CONV_JSON", timeout=600, dbg=dbg,
-                route_log="MI355X_SD_GEMM_LOG")
+    return CHILD.spec((mode, *names), env_extra, dbg)
 
 
 def _all_runs():

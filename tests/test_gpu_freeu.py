@@ -17,15 +17,19 @@ import torch
 from oracle import unet_ref as U
 from tests import freeu_bounds as FB
 from tests.freeu_child import CASES, CHANNELS
-from tests.gpu_child import RUNNER
+from tests.gpu_child import Family
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-2   # tests/test_gpu_unet.py test_small_unet_vs_oracle ("tiny", "mini-xl")
 GEOM = {"tiny": ("TINY", 2, 16, 16, 7), "mini-xl": ("MINI_XL", 2, 16, 16, 77)}
 
 
+KERNEL = Family("freeu_child.py", "FREEU_JSON", None, timeout=300)
+UNET = Family("freeu_child.py", "FREEU_JSON", None, timeout=600)
+
+
 def _kernel(dtype):
-    return RUNNER.run("freeu_child.py", ("kernel",), {"MI355X_SD_DTYPE": dtype}, tag="FREEU_JSON", timeout=300)
+    return KERNEL.child(("kernel",), {"MI355X_SD_DTYPE": dtype})
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
@@ -69,7 +73,7 @@ def refs(tmp_path_factory):
 
 
 def _unet(refs):
-    return RUNNER.run("freeu_child.py", ("unet", refs[0]), {"MI355X_SD_DTYPE": "bf16"}, tag="FREEU_JSON", timeout=600)
+    return UNET.child(("unet", refs[0]), {"MI355X_SD_DTYPE": "bf16"})
 
 
 @pytest.mark.parametrize("name", list(GEOM))

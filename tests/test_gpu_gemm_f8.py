@@ -12,16 +12,19 @@ import pytest
 
 from tests.gemm_f8_bounds import MULTI_CAP
 from tests.gemm_f8_child import CASES
-from tests.gpu_child import RUNNER
+from tests.gpu_child import RUNNER, Family
 
 pytestmark = pytest.mark.gpu
 REL_BAR = {"bf16": 4e-3, "fp16": 6e-4}   # the rel-L2 bars of tests/test_gpu_gemm_linear.py
 BUILDS = {"bf16": {}, "fp16": {"MI355X_SD_DTYPE": "fp16"}}
 
 
+# (a child: library load + ~300 launches of at most 1 GFLOP + their float64 references on the device: seconds)
+CHILD = Family("gemm_f8_child.py", "F8_JSON", None, timeout=300)
+
+
 def _spec(build):
-    # (a child: library load + ~300 launches of at most 1 GFLOP + their float64 references on the device: seconds)
-    return dict(script="gemm_f8_child.py", args=(), env_extra=BUILDS[build], tag="F8_JSON", timeout=300)
+    return CHILD.spec((), BUILDS[build])
 
 
 def _run(build):

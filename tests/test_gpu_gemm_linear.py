@@ -10,18 +10,20 @@ expects: a launch that falls back to another kernel fails. Where two families wa
 import pytest
 
 from tests.gemm_linear_child import COMMON, GENERIC_OF, SWITCHES, expected_route, names_of
-from tests.gpu_child import RUNNER
+from tests.gpu_child import RUNNER, Family
 
 pytestmark = pytest.mark.gpu
 REL_BAR = {"bf16": 4e-3, "fp16": 6e-4}   # the rel-L2 bars of tests/test_gpu_gemm_variants.py and tests/test_gpu_fp16.py
 PROD = {"prod": {}, "fp16": {"MI355X_SD_DTYPE": "fp16"}}   # the production libraries: no switches, no route log
 
 
+# (a child: library load + ~50 launches of at most a few GFLOP + their float64 references: seconds)
+CHILD = Family("gemm_linear_child.py", "LINEAR_JSON", "MI355X_SD_GEMM_LOG", timeout=240)
+
+
 def _spec(sw):
     dbg = sw not in PROD
-    # (a child: library load + ~50 launches of at most a few GFLOP + their float64 references: seconds)
-    return dict(script="gemm_linear_child.py", args=tuple(names_of(sw)) if dbg else (), env_extra=(SWITCHES if dbg else PROD)[sw],
-                tag="LINEAR_JSON", timeout=240, dbg=dbg, route_log="MI355X_SD_GEMM_LOG")
+    return CHILD.spec(names_of(sw) if dbg else (), (SWITCHES if dbg else PROD)[sw], dbg)
 
 
 def _run(sw):

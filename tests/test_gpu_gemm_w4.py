@@ -13,7 +13,7 @@ import torch
 
 from tests import gemm_bounds as GB
 from tests.gemm_w4_child import CASES
-from tests.gpu_child import RUNNER
+from tests.gpu_child import Family
 
 pytestmark = pytest.mark.gpu
 REF = {"MI355X_SD_GEMM_TILE": "256", "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_NO_BIAS_ACC": "1", "MI355X_SD_NO_SPLITK": "1",
@@ -21,8 +21,11 @@ REF = {"MI355X_SD_GEMM_TILE": "256", "MI355X_SD_NO_PIPE": "1", "MI355X_SD_GEMM_N
 REL_BAR = 4e-3   # rel-L2 bar of the GEMM variant cases (tests/test_gpu_gemm_variants.py), bf16 stores
 
 
+CHILD = Family("gemm_w4_child.py", "W4_JSON", "MI355X_SD_GEMM_LOG", timeout=600)
+
+
 def _run(env_extra, names=(), dbg=True):
-    return RUNNER.run("gemm_w4_child.py", names, env_extra, tag="W4_JSON", timeout=600, dbg=dbg, route_log="MI355X_SD_GEMM_LOG")
+    return CHILD.child(names, env_extra, dbg)
 
 
 def _family(name, bn):

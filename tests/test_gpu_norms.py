@@ -7,7 +7,7 @@ debug-switch build with MI355X_SD_NORM_LOG, whose route log proves each case rea
 cases together reach all 38, once on the IEEE-half build (values only)."""
 import pytest
 
-from tests.gpu_child import RUNNER
+from tests.gpu_child import Family
 from tests.norm_child import CASES
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +26,8 @@ INSTANTIATIONS = (
     + [f"fused_adaln {n} 1 {m}" for n in (2, 4, 8) for m in ("m16", "m32")])                          # fused_adaln_scale_residual_kernel<NCH, M16>
 
 
-def _run(dtype):
-    """every case's result; the child runs once per build (tests/gpu_child.py: a failed child is remembered, not run again per test)"""
-    return RUNNER.run("norm_child.py", (), {} if dtype == "bf16" else {"MI355X_SD_DTYPE": dtype}, tag="NORM_JSON", timeout=900,
-                      dbg=dtype == "bf16", route_log="MI355X_SD_NORM_LOG")
+FAMILY = Family("norm_child.py", "NORM_JSON", "MI355X_SD_NORM_LOG", timeout=900)
+_run = FAMILY.run   # every case's result on one build; the child runs once per build (a failed child is remembered, not run again per test)
 
 
 def _check(name, v):
@@ -69,10 +67,7 @@ def test_case_meets_the_fp64_bound_on_its_route(name):
 
 def test_every_norm_instantiation_is_reached():
     got = _run("bf16")
-    reached = {" ".join(ln.split()[:1] + ln.split()[2:]) for v in got.values() for ln in v["route"]}
-    for inst in INSTANTIATIONS:
-        n = sum(1 for v in got.values() if any(" ".join(ln.split()[:1] + ln.split()[2:]) == inst for ln in v["route"]))
-        print(f"{inst:<28} reached by {n} cases")
+    reached = FAMILY.reached(got, lambda ln: " ".join(ln.split()[:1] + ln.split()[2:]), INSTANTIATIONS, width=28)
     assert len(INSTANTIATIONS) == 38
     assert set(INSTANTIATIONS) == reached, (sorted(set(INSTANTIATIONS) - reached), sorted(reached - set(INSTANTIATIONS)))
 
@@ -93,12 +88,9 @@ def test_fp16_build_meets_the_fp64_bound():
     """The IEEE-half build on the same matrix: the float64 bounds at u_out = 2^-10 over the whole output. (No route log in the
     production library: the debug build shares the dispatch code, and the tests above prove the routes.)"""
     got = _run("fp16")
-    bad = []
-    for name in CASES:
-        v = got[name]
+    def check(name, v):
         print(f"fp16 {name:<44} err/bound {v.get('ratio', 0):.3f}")
-        try:
-            _check(name, v)
-        except AssertionError as e:
-            bad.append(str(e))
+        _check(name, v)
+
+    bad = FAMILY.collect_failures(CASES, got, check)
     assert not bad, bad

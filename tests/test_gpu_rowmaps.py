@@ -11,7 +11,7 @@ ValueError and leave a canary output untouched."""
 import pytest
 import torch
 
-from tests.gpu_child import RUNNER
+from tests.gpu_child import Family
 from tests.rowmap_child import CASES
 
 pytestmark = pytest.mark.gpu
@@ -19,9 +19,12 @@ FAMILY = {"silu": "activations", "act": "activations", "gated": "activations", "
           "axpby": "axpby / cfg_axpby", "cfg": "axpby / cfg_axpby", "latent": "latent_dist"}
 
 
+CHILD = Family("rowmap_child.py", "ROWMAP_JSON", None, timeout=300)
+
+
 def _run(dtype):
     """every case's result on one build; a child runs once"""
-    return RUNNER.run("rowmap_child.py", (), {"MI355X_SD_DTYPE": dtype}, tag="ROWMAP_JSON", timeout=300)
+    return CHILD.child((), {"MI355X_SD_DTYPE": dtype})   # (the production library of either element type: these launchers log no route)
 
 
 def _check(name, v):
