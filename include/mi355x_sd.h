@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 22
+#define MI355X_SD_ABI_VERSION 23
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -114,7 +114,9 @@ int mi355x_sd_unet_forward(void* handle, void* stream, const float* sample, cons
  *              fails on the shapes of the add)
  *   CONTROLNET down_block_additional_residuals (one fp32 NCHW tensor per skip connection, in the order the down path produces
  *              them: conv_in first) + mid_block_additional_residual (:1121-1132, 1151-1155), e.g. the outputs of
- *              ControlNetModel; both or neither
+ *              ControlNetModel; both or neither. Down residuals without the mid one are the reference's deprecated T2I-Adapter form
+ *              (:1084-1094): MI355X_SD_ERR_UNSUPPORTED here -- the intrablock adds (down_intrablock_additional_residuals, ABI 23)
+ *              are planned by the Python planner only
  * class_labels, timestep_cond and the IP-Adapter image_embeds: mi355x_sd_unet_set_input below. */
 #define MI355X_SD_UNET_ENC_MASK 1
 #define MI355X_SD_UNET_SELF_MASK 2
@@ -416,6 +418,26 @@ int mi355x_sd_add_nchw_ex(void* x, int ldx, const float* r_nchw, int B, int C, i
 int64_t mi355x_sd_freeu_workspace_floats(int B, int H, int W, int Cs);
 int mi355x_sd_freeu(void* cat, int64_t ld, int B, int H, int W, int Cx, int Cs, float b, float s, int elem_f32, float* workspace,
                     void* stream);
+
+/* ---- T2I-Adapter (PPD/models/adapter.py; ABI 23): the three layers the adapter has and no other model here does. Its convolutions
+ * are mi355x_sd_conv3x3 and mi355x_sd_linear. ----
+ * nn.PixelUnshuffle(r) (adapter.py:306, :356, :484) fused with the NCHW fp32 -> NHWC bf16 change the next convolution needs:
+ *   y[(b*(H/r) + i)*(W/r) + j][c*r*r + dy*r + dx] = bf16(x[b][c][i*r + dy][j*r + dx])        one rounding per element
+ * x NCHW fp32 [B][C][H][W]; y rows of ldy bf16 elements; columns [C*r*r, ldy) are not written. r % 8 == 0 with x 16-byte aligned
+ * stores 16 bytes per thread (the adapter's r = 8, 16); any other r goes element by element.
+ * MI355X_SD_ERR_INVALID: a null pointer, B, C, H, W or r < 1, H % r or W % r nonzero, ldy < C*r*r, ldy % 8 nonzero, y not 16-byte
+ * aligned. MI355X_SD_ERR_UNSUPPORTED: C*r*r >= 2^31. */
+int mi355x_sd_pixel_unshuffle(const float* x_nchw, int B, int C, int H, int W, int r, void* y, int ldy, void* stream);
+/* nn.AvgPool2D(kernel_size=2, stride=2, ceil_mode=True) (adapter.py:411, :537) on NHWC bf16 rows: x [B*H*W][ldx] -> y
+ * [B*ceil(H/2)*ceil(W/2)][ldy], C channels. A window that hangs over the bottom or right edge averages its in-bounds elements only
+ * (Paddle's exclusive=True default). fp32 sum in the order (0,0), (0,1), (1,0), (1,1), one multiply by 1, 1/2 or 1/4, one rounding.
+ * MI355X_SD_ERR_INVALID: a null pointer, B, H, W or C < 1, ldx < C, ldy < C. MI355X_SD_ERR_UNSUPPORTED: C, ldx or ldy not a
+ * multiple of 8, x or y not 16-byte aligned. */
+int mi355x_sd_avgpool2(const void* x, int ldx, int B, int H, int W, int C, void* y, int ldy, void* stream);
+/* nn.ReLU (adapter.py:450, :571): y[row][c] = max(x[row][c], 0) on `rows` bf16 rows of C elements (row strides ldx, ldy); y == x (in
+ * place) is allowed, any other overlap is not. C, ldx, ldy multiples of 8 and both pointers 16-byte aligned: 16 bytes per thread.
+ * MI355X_SD_ERR_INVALID: a null pointer, rows < 1, C < 1, ldx < C, ldy < C. */
+int mi355x_sd_relu(const void* x, int ldx, void* y, int ldy, int64_t rows, int C, void* stream);
 
 /* DiagonalGaussianDistribution (PPD/models/vae.py:744-763, built by AutoencoderKL.encode, autoencoder_kl.py:266-283) from
  * the encoder's moments held as fp32 rows [B*HW][ld >= 2L] (channels mean_0..L-1, logvar_0..L-1): writes NCHW fp32

@@ -6,3 +6,12 @@ C ABI of ``libmi355x_sd.so`` (include/mi355x_sd.h).  There is no CPU or PyTorch 
 library every op raises.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # ``paddlemix_amd.T2IAdapter`` / ``paddlemix_amd.MultiAdapter``: resolved on first use, so importing the package stays as light as it
+    # was (the element type of the library build is still chosen before the first model module is imported)
+    if name in ("T2IAdapter", "MultiAdapter"):
+        from . import adapter
+        return getattr(adapter, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -26,7 +26,7 @@ if os.environ.get("MI355X_SD_LIB") == "dbg":
         raise ValueError("MI355X_SD_LIB=dbg: the debug-switch build exists for bf16 elements only")
     LIB_PATH = os.path.join(_HERE, "libmi355x_sd_dbg.so")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 GEGLU, OUT_F32, SILU, GELU_TANH, PAD_BR, R_F32, CONV_KB64 = 1, 2, 4, 8, 16, 32, 64
 UNET_ENC_MASK, UNET_SELF_MASK, UNET_CONTROLNET = 1, 2, 4   # mi355x_sd_unet_plan_ex flags
 SDPA_LOG2 = 1
@@ -122,6 +122,10 @@ SIGNATURES = {
     # FreeU on a concat buffer of the U-Net's up path (csrc/freeu.hip, ABI 22)
     "mi355x_sd_freeu_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int]),
     "mi355x_sd_freeu": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p]),
+    # the T2I-Adapter's own layers (csrc/adapter.hip, ABI 23)
+    "mi355x_sd_pixel_unshuffle": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mi355x_sd_avgpool2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mi355x_sd_relu": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "mi355x_sd_latent_dist": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "mi355x_sd_embed_tokens": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),

@@ -133,7 +133,8 @@ class CUNet2DConditionModel:
 
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, return_dict: bool = True, in_scale=None,
                 attention_mask=None, encoder_attention_mask=None, down_block_additional_residuals=None,
-                mid_block_additional_residual=None, class_labels=None, timestep_cond=None):
+                mid_block_additional_residual=None, class_labels=None, timestep_cond=None,
+                down_intrablock_additional_residuals=None):
         lib, h = self.hd.lib, self.hd.h
         cfgd = self.hd.config_dict
         if sample.dim() != 4 or sample.shape[1] != cfgd.get("in_channels", 4):
@@ -196,9 +197,13 @@ class CUNet2DConditionModel:
             if tuple(ie.shape) != (B, cfgd["encoder_hid_dim"]):
                 raise ValueError(f"image_embeds of shape {tuple(ie.shape)}, expected {(B, cfgd['encoder_hid_dim'])}")
         controlnet = down_block_additional_residuals is not None
+        if down_intrablock_additional_residuals is not None:
+            raise NotImplementedError("the C executor (mi355x_sd_unet_*) plans no T2I-Adapter residuals "
+                                      "(`down_intrablock_additional_residuals`); use paddlemix_amd.unet.UNet2DConditionModel")
         if controlnet != (mid_block_additional_residual is not None):
             raise NotImplementedError("ControlNet residuals need both `down_block_additional_residuals` and "
-                                      "`mid_block_additional_residual` (the T2I-adapter form is not implemented)")
+                                      "`mid_block_additional_residual`; down residuals alone are the deprecated T2I-Adapter form, which "
+                                      "the C executor (mi355x_sd_unet_*) does not plan: use paddlemix_amd.unet.UNet2DConditionModel")
         flags = ((_lib.UNET_ENC_MASK if encoder_attention_mask is not None else 0) | (_lib.UNET_SELF_MASK if attention_mask is not None else 0) |
                  (_lib.UNET_CONTROLNET if controlnet else 0))
         if encoder_attention_mask is not None and tuple(encoder_attention_mask.shape) != (B, L):

@@ -156,6 +156,10 @@ inline long freeu_workspace_floats(int B, int H, int W, int Cs) {
   return (long)B * splits * FU_Q * ((long)Cs + 16);
 }
 int launch_freeu(void* cat, int x_f32, long ld, int B, int H, int W, int Cx, int Cs, float b, float s, float* ws, hipStream_t stream);
+// T2I-Adapter layers (adapter.hip): pixel-unshuffle into NHWC rows, 2 x 2 average pooling with ceil mode, ReLU (y may be x)
+int launch_pixel_unshuffle(const float* x_nchw, int B, int C, int H, int W, int r, bf16* y, int ldy, hipStream_t stream);
+int launch_avgpool2(const bf16* x, int ldx, int B, int H, int W, int C, bf16* y, int ldy, hipStream_t stream);
+int launch_relu(const bf16* x, int ldx, bf16* y, int ldy, long rows, int C, hipStream_t stream);
 int launch_latent_dist(const float* m, int ld, int B, int L, long HW, const float* noise, float out_scale, float* mean,
                        float* logvar, float* sample, hipStream_t stream);
 int launch_embed_tokens(const int* ids, long n_tokens, int seq_len, const bf16* tok, const bf16* pos, int D, bf16* out,

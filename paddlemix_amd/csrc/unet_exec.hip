@@ -424,10 +424,11 @@ int mi355x_sd_unet_forward_ex(void* handle, void* stream, const float* sample, c
   }
   if (want_ctrl) {
     if (!down_block_additional_residuals || !mid_block_additional_residual) {
-      // the reference's T2I-adapter form (down residuals only) is not built
+      // down residuals alone are the reference's deprecated T2I-Adapter form (unet_2d_condition.py:1084-1094): the intrablock adds
+      // are planned by the Python planner only (paddlemix_amd.unet), not by this handle
       sd::set_last_error("mi355x_sd_unet_forward_ex: ControlNet residuals need both down_block_additional_residuals and "
-                         "mid_block_additional_residual");
-      return MI355X_SD_ERR_INVALID;
+                         "mid_block_additional_residual; T2I-Adapter (intrablock) residuals are not supported by the C handle");
+      return MI355X_SD_ERR_UNSUPPORTED;
     }
     if (num_down_residuals != (int)e->ctrl_down.size()) {
       sd::set_last_error("mi355x_sd_unet_forward_ex: wrong number of down_block_additional_residuals (mi355x_sd_unet_num_skips)");

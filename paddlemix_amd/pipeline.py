@@ -243,10 +243,11 @@ class _VaeSwitches:
 class StableDiffusionDenoiser(_VaeSwitches):
     """``pipe = StableDiffusionDenoiser(unet, scheduler); latents = pipe(prompt_embeds=..., ...)``"""
 
-    def __init__(self, unet, scheduler, vae=None, text_encoder=None, text_encoder_2=None, controlnet=None):
+    def __init__(self, unet, scheduler, vae=None, text_encoder=None, text_encoder_2=None, controlnet=None, adapter=None):
         self.unet, self.scheduler, self.vae = unet, scheduler, vae
         self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2
         self.controlnet = controlnet   # ControlNetModel: StableDiffusionControlNetPipeline (controlnet/pipeline_controlnet.py)
+        self.adapter = adapter         # T2IAdapter / MultiAdapter: StableDiffusion(XL)AdapterPipeline (pipelines/t2i_adapter/)
 
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
         """FreeU on the U-Net's first two up blocks (pipeline_stable_diffusion.py ``enable_freeu`` -> ``unet.enable_freeu``); holds
@@ -309,6 +310,31 @@ class StableDiffusionDenoiser(_VaeSwitches):
             return None
         coef = torch.tensor(coefs, dtype=torch.float32, device=device).contiguous()
         return tail(lib, emulated, coef, scales, sch, generator)
+
+    def _adapter_state(self, adapter_image, hw, scale, batch: int, do_cfg: bool):
+        """The adapter's features for the whole loop (pipeline_stable_diffusion_adapter.py:757-766, 823-836): the image(s) cropped to
+        the multiple of the downscale factor the call runs at, one adapter forward, the conditioning scale, the prompt batch, the
+        doubling under classifier-free guidance"""
+        from .adapter import MultiAdapter
+        crop = lambda im: im[..., :hw[0], :hw[1]].to(torch.float32).contiguous()  # noqa: E731
+        if isinstance(self.adapter, MultiAdapter):
+            if torch.is_tensor(adapter_image):
+                raise ValueError("a MultiAdapter takes a list of `adapter_image`s, one per adapter")
+            weights = list(scale) if isinstance(scale, (list, tuple)) else [scale] * len(adapter_image)
+            state = self.adapter([crop(im) for im in adapter_image], weights)
+        else:
+            if not torch.is_tensor(adapter_image):
+                raise ValueError("`adapter_image` has to be a [B, C, H, W] tensor (a list is for a MultiAdapter)")
+            if isinstance(scale, (list, tuple)):
+                raise ValueError("a list of `adapter_conditioning_scale`s is for a MultiAdapter")
+            state = [v * float(scale) for v in self.adapter(crop(adapter_image))]
+        out = []
+        for v in state:
+            if batch % v.shape[0]:
+                raise ValueError(f"Cannot duplicate `adapter_image` of batch size {v.shape[0]} to {batch} prompts.")
+            v = v.repeat(batch // v.shape[0], 1, 1, 1)
+            out.append(torch.cat([v] * 2) if do_cfg else v)
+        return out
 
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
         """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1)."""
@@ -437,7 +463,8 @@ class StableDiffusionDenoiser(_VaeSwitches):
                  image: Optional[torch.Tensor] = None, strength: Optional[float] = None, eta: float = 0.0,
                  mask_image: Optional[torch.Tensor] = None, masked_image_latents: Optional[torch.Tensor] = None,
                  control_image: Optional[torch.Tensor] = None, controlnet_conditioning_scale: float = 1.0,
-                 guess_mode: bool = False):
+                 guess_mode: bool = False, adapter_image=None, adapter_conditioning_scale=1.0,
+                 adapter_conditioning_factor: float = 1.0):
         """``image`` (extension of the text2img call = StableDiffusionImg2ImgPipeline.__call__,
         pipeline_stable_diffusion_img2img.py:735-1010): start from the encoded, re-noised image and run the last
         ``int(num_inference_steps * strength)`` steps (strength defaults to 0.8).
@@ -445,8 +472,27 @@ class StableDiffusionDenoiser(_VaeSwitches):
         ``image`` + ``mask_image`` [B|1, 1, H, W] in [0, 1], 1 = repaint (= StableDiffusionInpaintPipeline.__call__,
         pipeline_stable_diffusion_inpaint.py:1094-1236; strength defaults to 1.0): a 9-channel UNet gets
         ``[latents | mask | masked-image latents]`` every step, a 4-channel UNet has the kept region re-imposed after every
-        step from the re-noised image latents."""
+        step from the re-noised image latents.
+
+        ``adapter_image`` (= StableDiffusionAdapterPipeline / StableDiffusionXLAdapterPipeline.__call__,
+        pipelines/t2i_adapter/pipeline_stable_diffusion_adapter.py:748-854, pipeline_stable_diffusion_xl_adapter.py:958-1032): fp32 NCHW
+        in [0, 1], or a list of such images for a MultiAdapter. The adapter runs once before the loop; its features, times
+        ``adapter_conditioning_scale`` (a list for a MultiAdapter: its ``adapter_weights``), repeated to the prompt batch and doubled
+        under classifier-free guidance, go to the U-Net as ``down_intrablock_additional_residuals`` on the steps
+        ``i < int(num_inference_steps * adapter_conditioning_factor)``; the other steps run the plain plan. Height and width default
+        to the image's, floored to a multiple of ``adapter.downscale_factor``."""
         inpaint = mask_image is not None
+        adapter_hw = None
+        if adapter_image is not None:
+            if self.adapter is None:
+                raise ValueError("`adapter_image` needs an `adapter`")
+            if control_image is not None:
+                raise NotImplementedError("a T2I-Adapter and a ControlNet in one call are not implemented")
+            first = adapter_image if torch.is_tensor(adapter_image) else adapter_image[0]
+            f = self.adapter.downscale_factor   # _default_height_width (pipeline_stable_diffusion_adapter.py:572-597)
+            adapter_hw = ((height or first.shape[-2]) // f * f, (width or first.shape[-1]) // f * f)
+            if latents is None or height is not None or width is not None:
+                height, width = adapter_hw
         if inpaint and image is None:
             raise ValueError("`mask_image` needs `image`")
         if strength is None:
@@ -533,6 +579,16 @@ class StableDiffusionDenoiser(_VaeSwitches):
             or _GenericTail(self.scheduler, extra)
         guidance = (do_cfg, guidance_scale, guidance_rescale if rescale else 0.0)
         nine = inp is not None and cfg.in_channels != latents.shape[1]
+        adapter_state = None
+        if adapter_image is not None:
+            adapter_state = self._adapter_state(adapter_image, adapter_hw, adapter_conditioning_scale, B, do_cfg)
+        adapter_steps = int(num_inference_steps * adapter_conditioning_factor)
+
+        def adapt(i):
+            """this step's T2I-Adapter residuals: a fresh list every step, withheld from step int(n * factor) on"""
+            if adapter_state is None or i >= adapter_steps:
+                return {}
+            return dict(down_intrablock_additional_residuals=list(adapter_state))
 
         def control(x_in, t):
             """ControlNet residuals of this step (pipeline_controlnet.py:1148-1192): the ControlNet sees the UNet's input batch
@@ -567,7 +623,7 @@ class StableDiffusionDenoiser(_VaeSwitches):
         for i, t in enumerate(timesteps, start=first):
             model_input = tail.scale(torch.cat([latents] * 2) if do_cfg else latents, i, t)
             noise_pred = self.unet(extend(model_input), t, encoder_hidden_states=prompt_embeds, added_cond_kwargs=added_cond_kwargs,
-                                   return_dict=False, **unet_kw, **control(model_input, t))[0]
+                                   return_dict=False, **unet_kw, **control(model_input, t), **adapt(i))[0]
             latents = reimpose(tail.update(latents, noise_pred, i, t, *guidance), i - first)
             if callback_on_step_end is not None:
                 out = callback_on_step_end(self, i, t, {"latents": latents})

@@ -176,6 +176,21 @@ def _structure(cfg: dict, encoder_only: bool = False) -> List[tuple]:
     return L
 
 
+def intrablock_sites(layers: List[tuple]) -> List[int]:
+    """Indices into a layer list of the layers whose output takes a T2I-Adapter residual, in the order the reference pops them
+    (unet_2d_condition.py:1096-1119, 1146-1152): per down block the last attention of a CrossAttnDownBlock2D (unet_2d_blocks.py:1211-1213:
+    before its downsampler) or the last layer of a DownBlock2D (after its downsampler, if it has one); then the mid block's last resnet"""
+    last: Dict[int, int] = {}
+    for i, d in enumerate(layers):
+        if d[0] in ("resnet", "attn", "down") and d[1].startswith("down_blocks."):
+            b = int(d[1].split(".")[1])
+            has_attn = any(e[0] == "attn" and e[1].startswith(f"down_blocks.{b}.") for e in layers)
+            if d[0] == "attn" or not has_attn:
+                last[b] = i
+    sites = [last[b] for b in sorted(last)]
+    return sites + [i for i, d in enumerate(layers) if d[0] == "resnet" and d[1] == "mid_block.resnets.1"]
+
+
 def unet_param_shapes(config: Mapping) -> Dict[str, tuple]:
     """name -> shape (Paddle layouts) of every parameter the configured UNet owns, in construction order
     (unet_2d_condition.py:287-631 and the block ctors in unet_2d_blocks.py)."""
@@ -463,15 +478,17 @@ class _UNetWeights:
 class _UNetPlanner:
     """The launch plan of one input geometry, written stage by stage: ``inputs``, ``time_embedding`` (with ``class_embedding`` around its
     MLP), ``added_conditions``, ``block_embeddings``, ``context_kv``, ``skip_layout``, ``walk`` (``stem``, then per layer ``resnet`` /
-    ``transformer`` / ``downsample`` / ``upsample``, ``controlnet_residuals`` where the up path starts and ``freeu`` on every concat
-    input) and ``head``. The attributes
+    ``transformer`` / ``downsample`` / ``upsample``, ``intrablock_residual`` behind the producer of each T2I-Adapter site,
+    ``controlnet_residuals`` where the up path starts and ``freeu`` on every concat input) and ``head``. The attributes
     are what crosses stages: ``emb_t`` / ``emb`` / ``cls_out``, ``temb_all``, ``kv_all``, ``kvip_all``, the masks' biases, the skip layout
     (``skips``, ``ups``, ``cats``, ``cat_xc``, ``cat_hw``, ``own_skips``) and ``RES``; everything else is a local of one stage."""
 
-    def __init__(self, model: "UNet2DConditionModel", B, H, W, L, masked=False, controlnet=False, self_mask_len=0):
+    def __init__(self, model: "UNet2DConditionModel", B, H, W, L, masked=False, controlnet=False, self_mask_len=0, intrablock=0):
         self.m, self.cfg, self.lib, self.stream = model, model.cfg, model._lib, model._stream_ptr
         self.B, self.H, self.W, self.L = B, H, W, L
         self.masked, self.controlnet, self.self_mask_len = masked, controlnet, self_mask_len
+        # T2I-Adapter: layer index -> residual index, for the first `intrablock` sites (intrablock_sites)
+        self.intra_at = {i: n for n, i in enumerate(intrablock_sites(model._layers)[:intrablock])}
         self.pb = PlanBuilder(model, B)
         self.plan = self.pb.plan
         self.ted = self.cfg["block_out_channels"][0] * 4
@@ -787,18 +804,28 @@ class _UNetPlanner:
         once the down path and the mid block have consumed the originals"""
         if not self.controlnet:
             return
-        plan, pb, B = self.plan, self.pb, self.B
-
-        def add(dst: _V, c, hs, ws_) -> Tensor:
-            r = pb.persist((B, c, hs, ws_), torch.float32)
-            if dst.es == 2:
-                pb.emit(self.lib.mi355x_sd_add_nchw, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, self.stream), "misc")
-            else:
-                pb.emit(self.lib.mi355x_sd_add_nchw_ex, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, 1, self.stream), "misc")
-            return r
-
+        plan, add = self.plan, self.add_nchw
         plan.ctrl_down = [add(self.skip_slot(k), *s) for k, s in enumerate(self.skips)]
         plan.ctrl_mid = add(mid, mid.C, h, w_)
+
+    def add_nchw(self, dst: _V, c, hs, ws_) -> Tensor:
+        """dst += a residual the caller hands over as fp32 NCHW, in place; returns the persistent buffer ``stage_inputs`` fills"""
+        pb, B = self.pb, self.B
+        r = pb.persist((B, c, hs, ws_), torch.float32)
+        if dst.es == 2:
+            pb.emit(self.lib.mi355x_sd_add_nchw, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, self.stream), "misc")
+        else:
+            pb.emit(self.lib.mi355x_sd_add_nchw_ex, (dst.p, dst.ld, r.data_ptr(), B, c, hs * ws_, 1, self.stream), "misc")
+        return r
+
+    def intrablock_residual(self, i: int, cur: _V, h, w_):
+        """T2I-Adapter residuals (``down_intrablock_additional_residuals``, unet_2d_condition.py:1096-1119, 1146-1152;
+        unet_2d_blocks.py:1211-1213): layer ``i`` is a site -- the last resnet / attention pair of a CrossAttnDownBlock2D, the end of a
+        DownBlock2D (its downsampler if it has one), the mid block -- so its output gets its residual in place, directly behind the
+        launch that produced it and before anything reads it: the tensor is a skip and the next layer's input at once"""
+        if i in self.intra_at:
+            assert self.intra_at[i] == len(self.plan.intra)
+            self.plan.intra.append(self.add_nchw(cur, cur.C, h, w_))
 
     def freeu(self, u: int):
         """FreeU (apply_freeu, unet_2d_blocks.py:2329-2351, 2478-2500): the concat input of up resnet ``u``, in place, before its first
@@ -834,6 +861,7 @@ class _UNetPlanner:
         S, B = self.m._layers, self.B
         h, w_ = self.H, self.W
         k, u = 1, 0          # next skip index to produce (S[0] is the conv_in skip), next up resnet index
+        self.plan.intra = []
         cur = self.stem()
         for i in range(1, len(S)):
             d = S[i]
@@ -851,6 +879,7 @@ class _UNetPlanner:
                 else:
                     self.transformer(d[1], cur, h, w_, d[3], d[4], dst)
                 cur = dst
+                self.intrablock_residual(i, cur, h, w_)
             elif d[0] == "skip":
                 k += 1
             elif d[0] == "down":
@@ -858,6 +887,7 @@ class _UNetPlanner:
                 self.downsample(d[1], cur, h, w_, dst)
                 h, w_ = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
                 cur = dst
+                self.intrablock_residual(i, cur, h, w_)
             elif d[0] == "cat":
                 if u == 0:
                     self.controlnet_residuals(cur, h, w_)
@@ -977,17 +1007,65 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
         """unet_2d_condition.py:803-808"""
         self.freeu = None
 
-    def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False, self_mask_len: int = 0) -> _Plan:
+    def _get_plan(self, B, H, W, L, masked: bool = False, controlnet: bool = False, self_mask_len: int = 0,
+                  intrablock: int = 0) -> _Plan:
+        """``intrablock``: how many T2I-Adapter residuals the plan adds (the first so many of ``intrablock_shapes``); none leaves the
+        key and the plan what they are without the argument"""
         if masked and self._ip:
             raise NotImplementedError("encoder_attention_mask together with IP-Adapter image tokens")
-        return self.plan_for((B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len, self.freeu),
-                             lambda: self._Planner(self, B, H, W, L, masked, controlnet, self_mask_len).build())
+        key = (B, H, W, L, masked, controlnet, self.ip_adapter_scale, self_mask_len, self.freeu) + ((intrablock,) if intrablock else ())
+        return self.plan_for(key, lambda: self._Planner(self, B, H, W, L, masked, controlnet, self_mask_len, intrablock).build())
+
+    def intrablock_shapes(self, B, H, W) -> List[Tuple[int, int, int, int]]:
+        """shape of the residual each T2I-Adapter site takes for a [B, C, H, W] sample, in the order of
+        ``down_intrablock_additional_residuals``: one per down block, then the mid block's"""
+        out, h, w_, c = [], H, W, self.cfg["block_out_channels"][0]
+        sites = intrablock_sites(self._layers)
+        for i, d in enumerate(self._layers):
+            if d[0] == "resnet":
+                c = d[3]
+            elif d[0] == "down":
+                h, w_ = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+            if i in sites:
+                out.append((B, c, h, w_))
+        return out
+
+    def _intrablock_count(self, residuals, sample_shape, deprecated: bool) -> int:
+        """how many of ``residuals`` the forward adds, by the reference's rules (unet_2d_condition.py:1096-1119, 1146-1152): one per
+        down block while the list lasts, then the next one after the mid block if it has the mid output's shape; what is left over is
+        ignored. A down block's residual of another shape is an error (the reference's add fails on it)."""
+        B, _, H, W = sample_shape
+        shapes = self.intrablock_shapes(B, H, W)
+        n = min(len(residuals), len(shapes) - 1)
+        for k in range(n):
+            if tuple(residuals[k].shape) != shapes[k]:
+                if deprecated:
+                    raise NotImplementedError(
+                        "`down_block_additional_residuals` without `mid_block_additional_residual` is read as T2I-Adapter residuals "
+                        f"(the deprecated form of `down_intrablock_additional_residuals`), and residual {k} of shape "
+                        f"{tuple(residuals[k].shape)} is not down block {k}'s {shapes[k]}; ControlNet residuals need both "
+                        "`down_block_additional_residuals` and `mid_block_additional_residual`")
+                raise ValueError(f"down_intrablock_additional_residuals[{k}] of shape {tuple(residuals[k].shape)}, expected "
+                                 f"{shapes[k]} (the output of down block {k})")
+        if len(residuals) > n and tuple(residuals[n].shape) == shapes[-1]:
+            n += 1
+        return n
 
     def stage_inputs(self, plan: _Plan, sample, timestep, encoder_hidden_states, added_cond_kwargs=None,
                      in_scale: Optional[float] = None, encoder_attention_mask=None,
                      down_block_additional_residuals=None, mid_block_additional_residual=None, class_labels=None,
-                     timestep_cond=None, attention_mask=None) -> None:
+                     timestep_cond=None, attention_mask=None, down_intrablock_additional_residuals=None) -> None:
         cfg = self.cfg
+        intra = getattr(plan, "intra", None) or []
+        if intra:
+            given = down_intrablock_additional_residuals
+            if given is None or len(given) < len(intra):
+                raise ValueError(f"this plan adds {len(intra)} down_intrablock_additional_residuals, got "
+                                 f"{0 if given is None else len(given)}")
+            for k, (dst, r) in enumerate(zip(intra, given)):   # (surplus residuals are ignored, like the reference's pop)
+                if tuple(r.shape) != tuple(dst.shape):
+                    raise ValueError(f"down_intrablock_additional_residuals[{k}] of shape {tuple(r.shape)}, expected {tuple(dst.shape)}")
+                dst.copy_(r, non_blocking=True)
         if getattr(plan, "self_bias", None) is not None:
             # (1 - mask) * -10000 as an additive bias on the self-attention scores (unet_2d_condition.py:916-923)
             plan.self_bias.copy_((1.0 - attention_mask.to(torch.float32)) * -10000.0, non_blocking=True)
@@ -1072,24 +1150,39 @@ class UNet2DConditionModel(DeviceProgram, PretrainedMixin):
     def forward(self, sample, timestep, encoder_hidden_states, class_labels=None, timestep_cond=None,
                 attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
-                encoder_attention_mask=None, return_dict: bool = True):
+                encoder_attention_mask=None, return_dict: bool = True, down_intrablock_additional_residuals=None):
         self_mask_len = 0
         if attention_mask is not None:
             if attention_mask.dim() != 2 or attention_mask.shape[0] != sample.shape[0]:
                 raise ValueError(f"attention_mask: expected [batch, key_tokens], got {tuple(attention_mask.shape)}")
             self_mask_len = int(attention_mask.shape[1])
         # (class_labels without a class embedding are ignored, like unet_2d_condition.py:953)
+        # T2I-Adapter residuals (unet_2d_condition.py:1078-1094): their own argument, or -- deprecated, kept like the reference keeps
+        # it -- `down_block_additional_residuals` given without `mid_block_additional_residual`
+        intra, deprecated = down_intrablock_additional_residuals, False
+        if intra is None and down_block_additional_residuals is not None and mid_block_additional_residual is None:
+            intra, down_block_additional_residuals, deprecated = down_block_additional_residuals, None, True
         controlnet = down_block_additional_residuals is not None
         if controlnet != (mid_block_additional_residual is not None):
             raise NotImplementedError("ControlNet residuals need both `down_block_additional_residuals` and "
-                                      "`mid_block_additional_residual` (the T2I-adapter form is not implemented)")
+                                      "`mid_block_additional_residual`")
+        if intra is not None and controlnet:
+            raise NotImplementedError("`down_intrablock_additional_residuals` (T2I-Adapter) together with ControlNet residuals in one "
+                                      "forward is not implemented")
+        intra = None if intra is None else list(intra)
+        n_intra = 0 if intra is None else self._intrablock_count(intra, tuple(sample.shape), deprecated)
         ctrl = dict(down_block_additional_residuals=down_block_additional_residuals,
                     mid_block_additional_residual=mid_block_additional_residual, class_labels=class_labels,
                     timestep_cond=timestep_cond, attention_mask=attention_mask)
-        self.require_gpu(sample, encoder_hidden_states)
+        if n_intra:
+            ctrl["down_intrablock_additional_residuals"] = intra
+        self.require_gpu(sample, encoder_hidden_states, *(intra or ()))
         B, _, H, W = sample.shape
         L = encoder_hidden_states.shape[1]
-        plan = self._get_plan(B, H, W, L, encoder_attention_mask is not None, controlnet, self_mask_len)
+        if n_intra:
+            plan = self._get_plan(B, H, W, L, encoder_attention_mask is not None, controlnet, self_mask_len, n_intra)
+        else:
+            plan = self._get_plan(B, H, W, L, encoder_attention_mask is not None, controlnet, self_mask_len)
         with self.on_stream():
             # in_scale = 1: forward() takes the sample as the model input. (A host that drives the same geometry through the staged API
             # with scale_model_input folded into conv_in -- bench.py does -- leaves its factor in the plan; round 5's bs-8 parity leg
