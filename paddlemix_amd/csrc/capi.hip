@@ -90,6 +90,30 @@ static int check_ws(const void* ws, size_t bytes, const char* who) {
   return SD_OK;
 }
 
+// The GemmArgs of the six GEMM-class entries, stated once: gemm_args() zeroes the struct (a field an entry does not name is off) and sets
+// what all six share -- the scratch pair of an entry that takes one included, which that entry has passed through check_ws() -- and
+// epilogue_flags() decodes the flag bits the entry honours. An entry then states only what is its own.
+static GemmArgs gemm_args(const void* A, int lda, const void* W, void* C, int ldc, int M, int N, int K, void* ws = nullptr,
+                          size_t ws_bytes = 0) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = (const bf16*)A; g.W = (const bf16*)W; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  g.ws_base = ws; g.ws_bytes = ws ? ws_bytes : 0;
+  return g;
+}
+constexpr int EPILOGUE_CONV = MI355X_SD_OUT_F32 | MI355X_SD_R_F32 | MI355X_SD_SILU;   // (GEGLU is refused there, GELU_TANH not honoured)
+constexpr int EPILOGUE_LINEAR = EPILOGUE_CONV | MI355X_SD_GEGLU;                       // (mi355x_sd_linear: GELU_TANH not honoured)
+constexpr int EPILOGUE_ALL = EPILOGUE_LINEAR | MI355X_SD_GELU_TANH;
+static void epilogue_flags(GemmArgs& g, int flags, int honoured) {
+  flags &= honoured;
+  g.geglu = (flags & MI355X_SD_GEGLU) ? 1 : 0;
+  g.out_f32 = (flags & MI355X_SD_OUT_F32) ? 1 : 0;
+  g.r_f32 = (flags & MI355X_SD_R_F32) ? 1 : 0;
+  g.silu = (flags & MI355X_SD_SILU) ? 1 : 0;
+  g.gelu_tanh = (flags & MI355X_SD_GELU_TANH) ? 1 : 0;
+}
+
 // The argument rule of the step-tail entries (step_tail.hip), stated once: step_entry() checks a call against its operands and
 // launches. An entry names its operands in the header's order -- paddlemix_amd/step_forms.py holds the same row for the Python side,
 // tests/test_step_forms.py generates every refusal from it. Blocks write their part of the written spans while other blocks still read
@@ -188,17 +212,10 @@ int mi355x_sd_linear(const void* A, int lda, const void* W, void* C, int ldc, in
                      int flags, void* ws, size_t ws_bytes, void* stream) {
   if (!A || !W || !C) return fail(SD_ERR_INVALID, "mi355x_sd_linear: null pointer");
   if (int rc = check_ws(ws, ws_bytes, "mi355x_sd_linear")) return rc;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ws_base = ws; g.ws_bytes = ws ? ws_bytes : 0;
-  g.A = (const bf16*)A; g.W = (const bf16*)W; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  GemmArgs g = gemm_args(A, lda, W, C, ldc, M, N, K, ws, ws_bytes);
   g.bias = bias; g.rowbias = rowbias; g.rows_per_batch = rows_per_batch; g.ld_rowbias = ld_rowbias;
   g.R = (const bf16*)R; g.ldr = ldr; g.out_scale = out_scale;
-  g.geglu = (flags & MI355X_SD_GEGLU) ? 1 : 0;
-  g.out_f32 = (flags & MI355X_SD_OUT_F32) ? 1 : 0;
-  g.r_f32 = (flags & MI355X_SD_R_F32) ? 1 : 0;
-  g.silu = (flags & MI355X_SD_SILU) ? 1 : 0;
+  epilogue_flags(g, flags, EPILOGUE_LINEAR);
   return finish(launch_gemm(g, S(stream)), "mi355x_sd_linear");
 }
 
@@ -209,22 +226,14 @@ int mi355x_sd_linear_ex(const void* A, int lda, int a_rows_per_batch, int64_t a_
                         const void* R, int ldr, float out_scale, int flags, void* ws, size_t ws_bytes, void* stream) {
   if (!A || !W || !C) return fail(SD_ERR_INVALID, "mi355x_sd_linear_ex: null pointer");
   if (int rc = check_ws(ws, ws_bytes, "mi355x_sd_linear_ex")) return rc;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ws_base = ws; g.ws_bytes = ws ? ws_bytes : 0;
-  g.A = (const bf16*)A; g.W = (const bf16*)W; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  GemmArgs g = gemm_args(A, lda, W, C, ldc, M, N, K, ws, ws_bytes);
   g.a_rpb = a_rows_per_batch; g.a_bstride = (long)a_batch_stride;
   g.c_rpb = c_rows_per_batch; g.c_bstride = (long)c_batch_stride;
   g.bias = bias; g.rowbias = rowbias; g.rows_per_batch = rows_per_batch; g.ld_rowbias = ld_rowbias;
   g.gate = gate; g.ld_gate = ld_gate;
   g.wscale = w_scale;
   g.R = (const bf16*)R; g.ldr = ldr; g.out_scale = out_scale;
-  g.geglu = (flags & MI355X_SD_GEGLU) ? 1 : 0;
-  g.out_f32 = (flags & MI355X_SD_OUT_F32) ? 1 : 0;
-  g.r_f32 = (flags & MI355X_SD_R_F32) ? 1 : 0;
-  g.silu = (flags & MI355X_SD_SILU) ? 1 : 0;
-  g.gelu_tanh = (flags & MI355X_SD_GELU_TANH) ? 1 : 0;
+  epilogue_flags(g, flags, EPILOGUE_ALL);
   return finish(launch_gemm(g, S(stream)), "mi355x_sd_linear_ex");
 }
 
@@ -237,18 +246,10 @@ int mi355x_sd_linear_ln(const void* A, int lda, const float* row_stats, const vo
                         int ldc, int M, int N, int K, const float* bias, int flags, void* ws, size_t ws_bytes, void* stream) {
   if (!A || !W || !C || !row_stats || !w_rowsum) return fail(SD_ERR_INVALID, "mi355x_sd_linear_ln: null pointer");
   if (int rc = check_ws(ws, ws_bytes, "mi355x_sd_linear_ln")) return rc;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ws_base = ws; g.ws_bytes = ws ? ws_bytes : 0;
-  g.A = (const bf16*)A; g.W = (const bf16*)W; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  GemmArgs g = gemm_args(A, lda, W, C, ldc, M, N, K, ws, ws_bytes);
   g.rowstat = row_stats; g.wsum = w_rowsum;
   g.bias = bias; g.out_scale = 1.0f;
-  g.geglu = (flags & MI355X_SD_GEGLU) ? 1 : 0;
-  g.out_f32 = (flags & MI355X_SD_OUT_F32) ? 1 : 0;
-  g.r_f32 = (flags & MI355X_SD_R_F32) ? 1 : 0;
-  g.silu = (flags & MI355X_SD_SILU) ? 1 : 0;
-  g.gelu_tanh = (flags & MI355X_SD_GELU_TANH) ? 1 : 0;
+  epilogue_flags(g, flags, EPILOGUE_ALL);
   return finish(launch_gemm(g, S(stream)), "mi355x_sd_linear_ln");
 }
 
@@ -257,17 +258,14 @@ int mi355x_sd_linear_f8(const void* A8, int lda, int a_rows_per_batch, int64_t a
                         int64_t c_batch_stride, int M, int N, int K, const float* bias, const float* gate, int ld_gate,
                         int rows_per_batch, const void* R, int ldr, int flags, void* stream) {
   if (!A8 || !W8 || !C || !a_scale || !w_scale) return fail(SD_ERR_INVALID, "mi355x_sd_linear_f8: null pointer");
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = (const bf16*)A8; g.W = (const bf16*)W8; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  if (flags & ~MI355X_SD_GELU_TANH) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_linear_f8: only MI355X_SD_GELU_TANH is supported");
+  GemmArgs g = gemm_args(A8, lda, W8, C, ldc, M, N, K);
   g.a_rpb = a_rows_per_batch; g.a_bstride = (long)a_batch_stride;
   g.c_rpb = c_rows_per_batch; g.c_bstride = (long)c_batch_stride;
   g.ascale = a_scale; g.wscale = w_scale;
   g.bias = bias; g.gate = gate; g.ld_gate = ld_gate; g.rows_per_batch = rows_per_batch;
   g.R = (const bf16*)R; g.ldr = ldr; g.out_scale = 1.0f;
-  g.gelu_tanh = (flags & MI355X_SD_GELU_TANH) ? 1 : 0;
-  if (flags & ~MI355X_SD_GELU_TANH) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_linear_f8: only MI355X_SD_GELU_TANH is supported");
+  epilogue_flags(g, flags, MI355X_SD_GELU_TANH);
   return finish(launch_gemm_f8(g, S(stream)), "mi355x_sd_linear_f8");
 }
 
@@ -284,13 +282,10 @@ int mi355x_sd_linear_f8_q(const void* A8, int lda, const float* a_scale, const f
   if (!A8 || !W8 || !C8 || !a_scale || !a_l2 || !w_scale || !c_scale)
     return fail(SD_ERR_INVALID, "mi355x_sd_linear_f8_q: null pointer");
   if (flags & ~MI355X_SD_GELU_TANH) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_linear_f8_q: only MI355X_SD_GELU_TANH is supported");
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = (const bf16*)A8; g.W = (const bf16*)W8; g.C = C8;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
+  GemmArgs g = gemm_args(A8, lda, W8, C8, ldc, M, N, K);
   g.ascale = a_scale; g.wscale = w_scale; g.bias = bias; g.out_scale = 1.0f;
   g.out_f8 = 1; g.a_l2 = a_l2; g.w_norm_max = w_norm_max; g.bias_abs_max = bias_abs_max; g.oscale = c_scale;
-  g.gelu_tanh = (flags & MI355X_SD_GELU_TANH) ? 1 : 0;
+  epilogue_flags(g, flags, MI355X_SD_GELU_TANH);
   return finish(launch_gemm_f8(g, S(stream)), "mi355x_sd_linear_f8_q");
 }
 
@@ -301,22 +296,25 @@ int mi355x_sd_quantize_rows(const void* x, int64_t rows, int C, int ldx, int x_r
                                      (unsigned char*)y8, ldy, y_scale, S(stream)), "mi355x_sd_quantize_rows");
 }
 
+// ---- A base entry and its `_ex` form are one body (`*_entry`, which reports under the name of the entry that was called): the base
+// entry is that body with the neutral value of the argument the `_ex` form adds. ----
+static int adaln_entry(const char* who, const void* x, int rows, int C, int ldx, const void* scale, const void* shift, int ld_mod,
+                       int mod_dtype, int rows_per_batch, float eps, void* y, int ldy, void* stream) {
+  if (!x || !scale || !shift || !y) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  if (mod_dtype != MI355X_SD_MOD_F32 && mod_dtype != MI355X_SD_MOD_ELEM)
+    return fail(SD_ERR_INVALID, "%s: mod_dtype must be MI355X_SD_MOD_F32 or MI355X_SD_MOD_ELEM", who);
+  return finish(launch_adaln((const bf16*)x, rows, C, ldx, scale, shift, ld_mod, mod_dtype == MI355X_SD_MOD_ELEM, rows_per_batch, eps,
+                             (bf16*)y, ldy, S(stream)), who);
+}
+
 int mi355x_sd_adaln(const void* x, int rows, int C, int ldx, const float* scale, const float* shift, int ld_mod,
                     int rows_per_batch, float eps, void* y, int ldy, void* stream) {
-  if (!x || !scale || !shift || !y) return fail(SD_ERR_INVALID, "mi355x_sd_adaln: null pointer");
-  return finish(launch_adaln((const bf16*)x, rows, C, ldx, scale, shift, ld_mod, 0, rows_per_batch, eps, (bf16*)y, ldy,
-                             S(stream)),
-                "mi355x_sd_adaln");
+  return adaln_entry("mi355x_sd_adaln", x, rows, C, ldx, scale, shift, ld_mod, MI355X_SD_MOD_F32, rows_per_batch, eps, y, ldy, stream);
 }
 
 int mi355x_sd_adaln_ex(const void* x, int rows, int C, int ldx, const void* scale, const void* shift, int ld_mod, int mod_dtype,
                        int rows_per_batch, float eps, void* y, int ldy, void* stream) {
-  if (!x || !scale || !shift || !y) return fail(SD_ERR_INVALID, "mi355x_sd_adaln_ex: null pointer");
-  if (mod_dtype != MI355X_SD_MOD_F32 && mod_dtype != MI355X_SD_MOD_ELEM)
-    return fail(SD_ERR_INVALID, "mi355x_sd_adaln_ex: mod_dtype must be MI355X_SD_MOD_F32 or MI355X_SD_MOD_ELEM");
-  return finish(launch_adaln((const bf16*)x, rows, C, ldx, scale, shift, ld_mod, mod_dtype == MI355X_SD_MOD_ELEM, rows_per_batch, eps,
-                             (bf16*)y, ldy, S(stream)),
-                "mi355x_sd_adaln_ex");
+  return adaln_entry("mi355x_sd_adaln_ex", x, rows, C, ldx, scale, shift, ld_mod, mod_dtype, rows_per_batch, eps, y, ldy, stream);
 }
 
 int mi355x_sd_patchify(const float* x_nchw, int B, int C, int H, int W, int patch, void* out, int ldo, void* stream) {
@@ -338,54 +336,32 @@ int mi355x_sd_conv3x3(const void* X, int ldx, int B, int Hs, int Ws, int Cin, in
       (upsample != 0 && upsample != 1))
     return fail(SD_ERR_INVALID, "mi355x_sd_conv3x3: bad shape");
   if (flags & MI355X_SD_GEGLU) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_conv3x3: GEGLU epilogue is linear-only");
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ws_base = ws; g.ws_bytes = ws ? ws_bytes : 0;
-  g.A = (const bf16*)X; g.W = (const bf16*)W; g.C = C;
-  g.conv = 1; g.Hs = Hs; g.Ws = Ws; g.Cin = Cin; g.stride = stride; g.up = upsample;
-  g.pad = (flags & MI355X_SD_PAD_BR) ? 0 : 1;
-  g.kb64 = (flags & MI355X_SD_CONV_KB64) ? 1 : 0;
-  if (g.kb64 && (Cin & 63)) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_conv3x3: MI355X_SD_CONV_KB64 needs Cin % 64 == 0");
-  if (!g.pad && (stride != 2 || upsample))
+  const int pad = (flags & MI355X_SD_PAD_BR) ? 0 : 1, kb64 = (flags & MI355X_SD_CONV_KB64) ? 1 : 0;
+  if (kb64 && (Cin & 63)) return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_conv3x3: MI355X_SD_CONV_KB64 needs Cin % 64 == 0");
+  if (!pad && (stride != 2 || upsample))
     return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_conv3x3: MI355X_SD_PAD_BR is the stride-2 downsampler's padding");
   const int Hin = Hs << upsample, Win = Ws << upsample;
   // (bottom / right padding of a one-pixel row or column: the padded image is narrower than the window and has no output; C's
   // division truncates (1 + 1 - 3) / 2 to 0 and would compute one output row from a window that does not fit)
-  if (!g.pad && (Hin < 2 || Win < 2)) return fail(SD_ERR_INVALID, "mi355x_sd_conv3x3: image smaller than the padded 3 x 3 window");
-  g.Ho = (Hin + 1 + g.pad - 3) / stride + 1;
-  g.Wo = (Win + 1 + g.pad - 3) / stride + 1;
-  g.M = B * g.Ho * g.Wo; g.N = Cout; g.K = 9 * Cin; g.lda = ldx; g.ldc = ldc;
-  g.bias = bias; g.rowbias = rowbias; g.rows_per_batch = g.Ho * g.Wo; g.ld_rowbias = ld_rowbias;
+  if (!pad && (Hin < 2 || Win < 2)) return fail(SD_ERR_INVALID, "mi355x_sd_conv3x3: image smaller than the padded 3 x 3 window");
+  const int Ho = (Hin + 1 + pad - 3) / stride + 1, Wo = (Win + 1 + pad - 3) / stride + 1;
+  GemmArgs g = gemm_args(X, ldx, W, C, ldc, B * Ho * Wo, Cout, 9 * Cin, ws, ws_bytes);
+  g.conv = 1; g.Hs = Hs; g.Ws = Ws; g.Ho = Ho; g.Wo = Wo; g.Cin = Cin; g.stride = stride; g.up = upsample; g.pad = pad; g.kb64 = kb64;
+  g.bias = bias; g.rowbias = rowbias; g.rows_per_batch = Ho * Wo; g.ld_rowbias = ld_rowbias;
   g.R = (const bf16*)R; g.ldr = ldr; g.out_scale = out_scale;
-  g.out_f32 = (flags & MI355X_SD_OUT_F32) ? 1 : 0;
-  g.r_f32 = (flags & MI355X_SD_R_F32) ? 1 : 0;
-  g.silu = (flags & MI355X_SD_SILU) ? 1 : 0;
+  epilogue_flags(g, flags, EPILOGUE_CONV);
   return finish(launch_gemm(g, S(stream)), "mi355x_sd_conv3x3");
 }
 
-int mi355x_sd_sdpa(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
-                   int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts,
-                   int64_t o_bs, int o_ts, int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale,
-                   void* stream) {
-  if (!q || !k || !v || !out) return fail(SD_ERR_INVALID, "mi355x_sd_sdpa: null pointer");
-  AttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)out;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
-  a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-  a.q_ts = q_ts; a.k_ts = k_ts; a.v_ts = v_ts; a.o_ts = o_ts;
-  a.bias = bias; a.bias_bs = bias_bs; a.bias_hs = bias_hs; a.bias_qs = bias_qs;
-  a.scale = scale;
-  return finish(launch_attention(a, S(stream)), "mi355x_sd_sdpa");
-}
-
-int mi355x_sd_sdpa_ex(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
-                      int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts,
-                      int64_t o_bs, int o_ts, int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale, int flags,
-                      void* stream) {
-  if (!q || !k || !v || !out) return fail(SD_ERR_INVALID, "mi355x_sd_sdpa_ex: null pointer");
+// The three attention entries are one body: `flags` are mi355x_sd_sdpa_ex's, `accum` is mi355x_sd_sdpa_accum's out_scale (NULL: the
+// output is written, not added to).
+static int sdpa_entry(const char* who, const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
+                      int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts, int64_t o_bs, int o_ts,
+                      int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale, int flags, const float* accum, void* stream) {
+  if (!q || !k || !v || !out) return fail(SD_ERR_INVALID, "%s: null pointer", who);
   if ((flags & MI355X_SD_SDPA_LOG2) && (bias || D != 64))
-    return fail(SD_ERR_UNSUPPORTED, "mi355x_sd_sdpa_ex: MI355X_SD_SDPA_LOG2 needs D == 64 and no mask");
+    return fail(SD_ERR_UNSUPPORTED, "%s: MI355X_SD_SDPA_LOG2 needs D == 64 and no mask", who);
+  if (accum && *accum == 0.f) return SD_OK;   // out += 0 * attention
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)out;
@@ -395,43 +371,51 @@ int mi355x_sd_sdpa_ex(const void* q, const void* k, const void* v, const float* 
   a.bias = bias; a.bias_bs = bias_bs; a.bias_hs = bias_hs; a.bias_qs = bias_qs;
   a.log2 = (flags & MI355X_SD_SDPA_LOG2) ? 1 : 0;
   a.scale = a.log2 ? 1.0f : scale;
-  return finish(launch_attention(a, S(stream)), "mi355x_sd_sdpa_ex");
+  a.accum = accum ? *accum : 0.f;
+  return finish(launch_attention(a, S(stream)), who);
+}
+
+int mi355x_sd_sdpa(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
+                   int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts,
+                   int64_t o_bs, int o_ts, int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale,
+                   void* stream) {
+  return sdpa_entry("mi355x_sd_sdpa", q, k, v, bias, out, B, H, Sq, Skv, D, q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts, bias_bs,
+                    bias_hs, bias_qs, scale, 0, nullptr, stream);
+}
+
+int mi355x_sd_sdpa_ex(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
+                      int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts,
+                      int64_t o_bs, int o_ts, int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale, int flags,
+                      void* stream) {
+  return sdpa_entry("mi355x_sd_sdpa_ex", q, k, v, bias, out, B, H, Sq, Skv, D, q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts, bias_bs,
+                    bias_hs, bias_qs, scale, flags, nullptr, stream);
 }
 
 int mi355x_sd_sdpa_accum(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int H, int Sq,
                          int Skv, int D, int64_t q_bs, int q_ts, int64_t k_bs, int k_ts, int64_t v_bs, int v_ts,
                          int64_t o_bs, int o_ts, int64_t bias_bs, int64_t bias_hs, int64_t bias_qs, float scale,
                          float out_scale, void* stream) {
-  if (!q || !k || !v || !out) return fail(SD_ERR_INVALID, "mi355x_sd_sdpa_accum: null pointer");
-  if (out_scale == 0.f) return SD_OK;   // out += 0 * attention
-  AttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.Q = (const bf16*)q; a.K = (const bf16*)k; a.V = (const bf16*)v; a.O = (bf16*)out;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.D = D;
-  a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-  a.q_ts = q_ts; a.k_ts = k_ts; a.v_ts = v_ts; a.o_ts = o_ts;
-  a.bias = bias; a.bias_bs = bias_bs; a.bias_hs = bias_hs; a.bias_qs = bias_qs;
-  a.scale = scale;
-  a.accum = out_scale;
-  return finish(launch_attention(a, S(stream)), "mi355x_sd_sdpa_accum");
+  return sdpa_entry("mi355x_sd_sdpa_accum", q, k, v, bias, out, B, H, Sq, Skv, D, q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts,
+                    bias_bs, bias_hs, bias_qs, scale, 0, &out_scale, stream);
 }
 
 int mi355x_sd_groupnorm_workspace_floats(int B, int HW, int C) { return groupnorm_partial_floats(B, HW, C); }
 
+static int groupnorm_stats_entry(const char* who, const void* x, int B, int HW, int C, int ldx, int groups, float eps, const float* gamma,
+                                 const float* beta, float* workspace, float* scale_shift, int x_f32, void* stream) {
+  if (!x || !gamma || !beta || !workspace || !scale_shift) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  return finish(launch_groupnorm_stats(x, x_f32, B, HW, C, ldx, groups, eps, gamma, beta, workspace, scale_shift, S(stream)), who);
+}
+
 int mi355x_sd_groupnorm_stats(const void* x, int B, int HW, int C, int ldx, int groups, float eps, const float* gamma,
                               const float* beta, float* workspace, float* scale_shift, void* stream) {
-  if (!x || !gamma || !beta || !workspace || !scale_shift)
-    return fail(SD_ERR_INVALID, "mi355x_sd_groupnorm_stats: null pointer");
-  return finish(launch_groupnorm_stats(x, 0, B, HW, C, ldx, groups, eps, gamma, beta, workspace, scale_shift, S(stream)),
-                "mi355x_sd_groupnorm_stats");
+  return groupnorm_stats_entry("mi355x_sd_groupnorm_stats", x, B, HW, C, ldx, groups, eps, gamma, beta, workspace, scale_shift, 0, stream);
 }
 
 int mi355x_sd_groupnorm_stats_ex(const void* x, int B, int HW, int C, int ldx, int groups, float eps, const float* gamma,
                                  const float* beta, float* workspace, float* scale_shift, int x_f32, void* stream) {
-  if (!x || !gamma || !beta || !workspace || !scale_shift)
-    return fail(SD_ERR_INVALID, "mi355x_sd_groupnorm_stats_ex: null pointer");
-  return finish(launch_groupnorm_stats(x, x_f32, B, HW, C, ldx, groups, eps, gamma, beta, workspace, scale_shift, S(stream)),
-                "mi355x_sd_groupnorm_stats_ex");
+  return groupnorm_stats_entry("mi355x_sd_groupnorm_stats_ex", x, B, HW, C, ldx, groups, eps, gamma, beta, workspace, scale_shift, x_f32,
+                               stream);
 }
 
 int mi355x_sd_groupnorm_act_fits(int HW, int C, int groups) { return groupnorm_act_fits(HW, C, groups); }
@@ -443,59 +427,67 @@ int mi355x_sd_groupnorm_act(const void* x, int B, int HW, int C, int ldx, int gr
                 "mi355x_sd_groupnorm_act");
 }
 
+static int scale_shift_act_entry(const char* who, const void* x, int B, int HW, int C, int ldx, const float* scale_shift, int silu, void* y,
+                                 int ldy, int x_f32, void* raw16, int ld_raw, void* stream) {
+  if (!x || !scale_shift || !y) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  return finish(launch_scale_shift_act(x, x_f32, B, HW, C, ldx, scale_shift, silu, (bf16*)y, ldy, (bf16*)raw16, ld_raw, S(stream)), who);
+}
+
 int mi355x_sd_scale_shift_act(const void* x, int B, int HW, int C, int ldx, const float* scale_shift, int silu, void* y,
                               int ldy, void* stream) {
-  if (!x || !scale_shift || !y) return fail(SD_ERR_INVALID, "mi355x_sd_scale_shift_act: null pointer");
-  return finish(launch_scale_shift_act(x, 0, B, HW, C, ldx, scale_shift, silu, (bf16*)y, ldy, nullptr, 0, S(stream)),
-                "mi355x_sd_scale_shift_act");
+  return scale_shift_act_entry("mi355x_sd_scale_shift_act", x, B, HW, C, ldx, scale_shift, silu, y, ldy, 0, nullptr, 0, stream);
 }
 
 int mi355x_sd_scale_shift_act_ex(const void* x, int B, int HW, int C, int ldx, const float* scale_shift, int silu, void* y,
                                  int ldy, int x_f32, void* raw16, int ld_raw, void* stream) {
-  if (!x || !scale_shift || !y) return fail(SD_ERR_INVALID, "mi355x_sd_scale_shift_act_ex: null pointer");
-  return finish(launch_scale_shift_act(x, x_f32, B, HW, C, ldx, scale_shift, silu, (bf16*)y, ldy, (bf16*)raw16, ld_raw,
-                                       S(stream)),
-                "mi355x_sd_scale_shift_act_ex");
+  return scale_shift_act_entry("mi355x_sd_scale_shift_act_ex", x, B, HW, C, ldx, scale_shift, silu, y, ldy, x_f32, raw16, ld_raw, stream);
+}
+
+static int layernorm_entry(const char* who, const void* x, int rows, int C, int ldx, const float* gamma, const float* beta, float eps,
+                           void* y, int ldy, int x_f32, void* stream) {
+  if (!x || !y) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  return finish(launch_layernorm(x, x_f32, rows, C, ldx, gamma, beta, eps, (bf16*)y, ldy, S(stream)), who);
 }
 
 int mi355x_sd_layernorm(const void* x, int rows, int C, int ldx, const float* gamma, const float* beta, float eps,
                         void* y, int ldy, void* stream) {
-  if (!x || !y) return fail(SD_ERR_INVALID, "mi355x_sd_layernorm: null pointer");
-  return finish(launch_layernorm(x, 0, rows, C, ldx, gamma, beta, eps, (bf16*)y, ldy, S(stream)),
-                "mi355x_sd_layernorm");
+  return layernorm_entry("mi355x_sd_layernorm", x, rows, C, ldx, gamma, beta, eps, y, ldy, 0, stream);
 }
 
 int mi355x_sd_layernorm_ex(const void* x, int rows, int C, int ldx, const float* gamma, const float* beta, float eps,
                            void* y, int ldy, int x_f32, void* stream) {
-  if (!x || !y) return fail(SD_ERR_INVALID, "mi355x_sd_layernorm_ex: null pointer");
-  return finish(launch_layernorm(x, x_f32, rows, C, ldx, gamma, beta, eps, (bf16*)y, ldy, S(stream)),
-                "mi355x_sd_layernorm_ex");
+  return layernorm_entry("mi355x_sd_layernorm_ex", x, rows, C, ldx, gamma, beta, eps, y, ldy, x_f32, stream);
+}
+
+static int fused_adaln_scale_residual_entry(const char* who, const void* x, int ldx, const void* mha_out, int ld_mha, const void* gate_msa,
+                                            const void* scale_mlp, const void* shift_mlp, int ld_mod, int mod_dtype,
+                                            int rows_per_batch, const void* weight, const void* bias, float epsilon, int rows, int C,
+                                            void* resi_out, int ld_resi, void* adaln_out, int ld_out, void* stream) {
+  if (!x || !mha_out || !gate_msa || !scale_mlp || !shift_mlp || !resi_out || !adaln_out)
+    return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  if (mod_dtype != MI355X_SD_MOD_F32 && mod_dtype != MI355X_SD_MOD_ELEM)
+    return fail(SD_ERR_INVALID, "%s: mod_dtype must be MI355X_SD_MOD_F32 or MI355X_SD_MOD_ELEM", who);
+  return finish(launch_fused_adaln_scale_residual((const bf16*)x, ldx, (const bf16*)mha_out, ld_mha, gate_msa, scale_mlp, shift_mlp,
+                                                  ld_mod, mod_dtype == MI355X_SD_MOD_ELEM, rows_per_batch, weight, bias, epsilon, rows,
+                                                  C, (bf16*)resi_out, ld_resi, (bf16*)adaln_out, ld_out, S(stream)), who);
 }
 
 int mi355x_sd_fused_adaln_scale_residual(const void* x, int ldx, const void* mha_out, int ld_mha, const float* gate_msa,
                                          const float* scale_mlp, const float* shift_mlp, int ld_mod, int rows_per_batch,
                                          const float* weight, const float* bias, float epsilon, int rows, int C, void* resi_out,
                                          int ld_resi, void* adaln_out, int ld_out, void* stream) {
-  if (!x || !mha_out || !gate_msa || !scale_mlp || !shift_mlp || !resi_out || !adaln_out)
-    return fail(SD_ERR_INVALID, "mi355x_sd_fused_adaln_scale_residual: null pointer");
-  return finish(launch_fused_adaln_scale_residual((const bf16*)x, ldx, (const bf16*)mha_out, ld_mha, gate_msa, scale_mlp, shift_mlp,
-                                                  ld_mod, 0, rows_per_batch, weight, bias, epsilon, rows, C, (bf16*)resi_out, ld_resi,
-                                                  (bf16*)adaln_out, ld_out, S(stream)),
-                "mi355x_sd_fused_adaln_scale_residual");
+  return fused_adaln_scale_residual_entry("mi355x_sd_fused_adaln_scale_residual", x, ldx, mha_out, ld_mha, gate_msa, scale_mlp, shift_mlp,
+                                          ld_mod, MI355X_SD_MOD_F32, rows_per_batch, weight, bias, epsilon, rows, C, resi_out, ld_resi,
+                                          adaln_out, ld_out, stream);
 }
 
 int mi355x_sd_fused_adaln_scale_residual_ex(const void* x, int ldx, const void* mha_out, int ld_mha, const void* gate_msa,
                                             const void* scale_mlp, const void* shift_mlp, int ld_mod, int mod_dtype,
                                             int rows_per_batch, const void* weight, const void* bias, float epsilon, int rows, int C,
                                             void* resi_out, int ld_resi, void* adaln_out, int ld_out, void* stream) {
-  if (!x || !mha_out || !gate_msa || !scale_mlp || !shift_mlp || !resi_out || !adaln_out)
-    return fail(SD_ERR_INVALID, "mi355x_sd_fused_adaln_scale_residual_ex: null pointer");
-  if (mod_dtype != MI355X_SD_MOD_F32 && mod_dtype != MI355X_SD_MOD_ELEM)
-    return fail(SD_ERR_INVALID, "mi355x_sd_fused_adaln_scale_residual_ex: mod_dtype must be MI355X_SD_MOD_F32 or MI355X_SD_MOD_ELEM");
-  return finish(launch_fused_adaln_scale_residual((const bf16*)x, ldx, (const bf16*)mha_out, ld_mha, gate_msa, scale_mlp, shift_mlp,
-                                                  ld_mod, mod_dtype == MI355X_SD_MOD_ELEM, rows_per_batch, weight, bias, epsilon, rows,
-                                                  C, (bf16*)resi_out, ld_resi, (bf16*)adaln_out, ld_out, S(stream)),
-                "mi355x_sd_fused_adaln_scale_residual_ex");
+  return fused_adaln_scale_residual_entry("mi355x_sd_fused_adaln_scale_residual_ex", x, ldx, mha_out, ld_mha, gate_msa, scale_mlp,
+                                          shift_mlp, ld_mod, mod_dtype, rows_per_batch, weight, bias, epsilon, rows, C, resi_out, ld_resi,
+                                          adaln_out, ld_out, stream);
 }
 
 int mi355x_sd_split_concat(const void* x, const void* y, void* q_out, void* k_out, void* v_out, int B, int S1, int S2, int C,
@@ -518,18 +510,20 @@ int mi355x_sd_silu(const void* x, void* y, int64_t n, int in_f32, int out_f32, v
   return finish(launch_silu(x, y, (long)n, in_f32, out_f32, S(stream)), "mi355x_sd_silu");
 }
 
+static int conv_in3x3_entry(const char* who, const float* x_nchw, const float* in_scale, const void* w, const float* bias, void* y, int B,
+                            int Cin, int H, int W, int Cout, int ldy, int out_f32, void* stream) {
+  if (!x_nchw || !w || !y) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  return finish(launch_conv_in3x3(x_nchw, in_scale, (const bf16*)w, bias, y, out_f32, B, Cin, H, W, Cout, ldy, S(stream)), who);
+}
+
 int mi355x_sd_conv_in3x3(const float* x_nchw, const float* in_scale, const void* w, const float* bias, void* y, int B,
                          int Cin, int H, int W, int Cout, int ldy, void* stream) {
-  if (!x_nchw || !w || !y) return fail(SD_ERR_INVALID, "mi355x_sd_conv_in3x3: null pointer");
-  return finish(launch_conv_in3x3(x_nchw, in_scale, (const bf16*)w, bias, y, 0, B, Cin, H, W, Cout, ldy, S(stream)),
-                "mi355x_sd_conv_in3x3");
+  return conv_in3x3_entry("mi355x_sd_conv_in3x3", x_nchw, in_scale, w, bias, y, B, Cin, H, W, Cout, ldy, 0, stream);
 }
 
 int mi355x_sd_conv_in3x3_ex(const float* x_nchw, const float* in_scale, const void* w, const float* bias, void* y, int B,
                             int Cin, int H, int W, int Cout, int ldy, int out_f32, void* stream) {
-  if (!x_nchw || !w || !y) return fail(SD_ERR_INVALID, "mi355x_sd_conv_in3x3_ex: null pointer");
-  return finish(launch_conv_in3x3(x_nchw, in_scale, (const bf16*)w, bias, y, out_f32, B, Cin, H, W, Cout, ldy, S(stream)),
-                "mi355x_sd_conv_in3x3_ex");
+  return conv_in3x3_entry("mi355x_sd_conv_in3x3_ex", x_nchw, in_scale, w, bias, y, B, Cin, H, W, Cout, ldy, out_f32, stream);
 }
 
 int mi355x_sd_cast_rows(const float* x, int ldx, void* y, int ldy, int64_t rows, int C, void* stream) {
@@ -549,14 +543,17 @@ int mi355x_sd_copy_rows(const void* x, int ldx, void* y, int ldy, int64_t rows, 
   return finish(launch_copy_rows((const bf16*)x, ldx, (bf16*)y, ldy, (long)rows, C, S(stream)), "mi355x_sd_copy_rows");
 }
 
+static int add_nchw_entry(const char* who, void* x, int ldx, const float* r_nchw, int B, int C, int64_t HW, int x_f32, void* stream) {
+  if (!x || !r_nchw) return fail(SD_ERR_INVALID, "%s: null pointer", who);
+  return finish(launch_add_nchw(x, x_f32, ldx, r_nchw, B, C, (long)HW, S(stream)), who);
+}
+
 int mi355x_sd_add_nchw(void* x, int ldx, const float* r_nchw, int B, int C, int64_t HW, void* stream) {
-  if (!x || !r_nchw) return fail(SD_ERR_INVALID, "mi355x_sd_add_nchw: null pointer");
-  return finish(launch_add_nchw(x, 0, ldx, r_nchw, B, C, (long)HW, S(stream)), "mi355x_sd_add_nchw");
+  return add_nchw_entry("mi355x_sd_add_nchw", x, ldx, r_nchw, B, C, HW, 0, stream);
 }
 
 int mi355x_sd_add_nchw_ex(void* x, int ldx, const float* r_nchw, int B, int C, int64_t HW, int x_f32, void* stream) {
-  if (!x || !r_nchw) return fail(SD_ERR_INVALID, "mi355x_sd_add_nchw_ex: null pointer");
-  return finish(launch_add_nchw(x, x_f32, ldx, r_nchw, B, C, (long)HW, S(stream)), "mi355x_sd_add_nchw_ex");
+  return add_nchw_entry("mi355x_sd_add_nchw_ex", x, ldx, r_nchw, B, C, HW, x_f32, stream);
 }
 
 int mi355x_sd_latent_dist(const float* moments, int ld, int B, int L, int64_t HW, const float* noise_nchw, float out_scale,

@@ -54,7 +54,10 @@ Entry make_entry(const char* name, int (*f)(A...)) {
 }
 
 #define SD_OP(fn) make_entry(#fn, &fn)
-const std::vector<Entry>& op_table() {   // every stream-ordered launch of the header (the planners emit a subset)
+// Every function of the header whose last parameter is `void* stream`, except the handle and runtime entries (mi355x_sd_program_*,
+// mi355x_sd_unet_*, mi355x_sd_graph_*, mi355x_sd_comm_*) and mi355x_sd_probe_layouts: export.py writes any entry a planner emits, so
+// the loader knows every one a planner could (tests/test_abi.py holds the table to the header by this rule).
+const std::vector<Entry>& op_table() {
   static const std::vector<Entry> t = {
       SD_OP(mi355x_sd_mask_to_bias), SD_OP(mi355x_sd_linear), SD_OP(mi355x_sd_linear_ex), SD_OP(mi355x_sd_row_stats),
       SD_OP(mi355x_sd_linear_ln), SD_OP(mi355x_sd_linear_f8), SD_OP(mi355x_sd_adaln_f8), SD_OP(mi355x_sd_linear_f8_q),
@@ -68,7 +71,10 @@ const std::vector<Entry>& op_table() {   // every stream-ordered launch of the h
       SD_OP(mi355x_sd_conv_out3x3), SD_OP(mi355x_sd_copy_rows), SD_OP(mi355x_sd_add_nchw), SD_OP(mi355x_sd_add_nchw_ex),
       SD_OP(mi355x_sd_latent_dist), SD_OP(mi355x_sd_embed_tokens), SD_OP(mi355x_sd_activation), SD_OP(mi355x_sd_rmsnorm),
       SD_OP(mi355x_sd_gated_activation), SD_OP(mi355x_sd_conv1x1_nchw), SD_OP(mi355x_sd_softmax_rows), SD_OP(mi355x_sd_axpby),
-      SD_OP(mi355x_sd_cfg_axpby), SD_OP(mi355x_sd_freeu)};
+      SD_OP(mi355x_sd_cfg_axpby), SD_OP(mi355x_sd_freeu), SD_OP(mi355x_sd_pixel_unshuffle), SD_OP(mi355x_sd_avgpool2),
+      SD_OP(mi355x_sd_relu), SD_OP(mi355x_sd_tile_gather), SD_OP(mi355x_sd_tile_blend), SD_OP(mi355x_sd_cfg_rescale_axpby),
+      SD_OP(mi355x_sd_multistep_update), SD_OP(mi355x_sd_unipc_update), SD_OP(mi355x_sd_ancestral_update), SD_OP(mi355x_sd_heun_update),
+      SD_OP(mi355x_sd_dpm2_update), SD_OP(mi355x_sd_plms_update), SD_OP(mi355x_sd_singlestep_update)};
   return t;
 }
 

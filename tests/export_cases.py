@@ -85,11 +85,22 @@ def build(name, cpu, **kw):
         m = T5EncoderModel(C.MINI_T5, synth_t5_params(C.MINI_T5, seed=6), **kw)
         ids = torch.randint(0, 500, (2, 33), generator=g)
         return m, (lambda: m(_dev(ids, cpu))), ("out", "last")
+    if name == "t2i_adapter":   # the full adapter of tests/test_adapter_host.py, on a size whose pooled maps are ragged
+        from paddlemix_amd.adapter import T2IAdapter
+        from tests import adapter_ref as AR
+        cfg, image = AR.ADAPTERS["full"], torch.rand(2, 3, 72, 88, generator=g)
+        if cpu:   # (the adapter's own three entries: the emulator that has them, whichever the caller set)
+            from tests.abi_emulator import on_emulator
+            from tests.abi_emulator_adapter import AdapterEmulator
+            m = on_emulator(T2IAdapter, cfg, AR.synth_adapter_params(cfg, seed=21), backend=AdapterEmulator(), **kw)
+        else:
+            m = T2IAdapter(cfg, AR.synth_adapter_params(cfg, seed=21), **kw)
+        return m, (lambda: m(_dev(image, cpu))), ("features", "out")
     raise KeyError(name)
 
 
 NAMES = ["unet_tiny", "unet_mini_xl", "unet_tiny_masked_controlnet", "unet_class_labels", "unet_ip_adapter", "controlnet_tiny", "sd3_mini",
-         "dit_mini", "vae_decode", "vae_encode", "clip_text", "clip_vision", "t5_encoder"]
+         "dit_mini", "vae_decode", "vae_encode", "clip_text", "clip_vision", "t5_encoder", "t2i_adapter"]
 
 
 def last_plan(model):

@@ -9,7 +9,9 @@ pointer rewritten as (region, byte offset)) without the fixed 40-byte header, so
 buffer order, and an ABI bump does not move it.
 
     python -m tests.plan_table_cases tests/golden/plan_tables.json COMMIT      writes the fixture: done once, on the commit before
-                                                                               the planners moved onto PlanBuilder, which it names"""
+                                                                               the planners moved onto PlanBuilder, which it names
+A case of a model that came later is recorded on its own into tests/golden/plan_tables_later.json (same layout, `recorded_at` the
+commit it was taken on), so that the first fixture stays as recorded."""
 import hashlib
 import json
 import os

@@ -1,23 +1,92 @@
-"""The C-ABI library loads and exports exactly the symbols include/mi355x_sd.h declares (no compute, no GPU)."""
+"""The C-ABI library loads and exports exactly the symbols include/mi355x_sd.h declares, the binding gives each of them the header's
+types, and the exported-program runtime knows every launch of the header (no compute, no GPU)."""
 import ctypes
 import os
 import re
+import struct
 
 import pytest
 
 from paddlemix_amd import _lib
+from tests.header_decls import declared, launches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BY_VALUE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int32_t": ctypes.c_int32}
 
 
 def _declared():
-    src = open(os.path.join(ROOT, "include", "mi355x_sd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mi355x_sd_\w+)\s*\(", src)))
+    return sorted(declared())
+
+
+def _is_pointer_type(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)
+
+
+def _fits(ctype, kind):
+    """the binding's type against a parameter (or return) type of the header"""
+    if kind in BY_VALUE:
+        return ctype is BY_VALUE[kind]
+    assert kind.endswith("*"), kind
+    if kind == "const char*":
+        return ctype is ctypes.c_char_p
+    inner = kind[:-1].strip()
+    if inner.endswith("const"):
+        inner = inner[:-len("const")].strip()
+    if inner.endswith("*"):                                  # T**: a POINTER of a pointer type
+        return issubclass(ctype, ctypes._Pointer) and _is_pointer_type(ctype._type_)
+    base = inner[len("const "):] if inner.startswith("const ") else inner
+    return ctype is ctypes.c_void_p or (issubclass(ctype, ctypes._Pointer) and ctype._type_ is BY_VALUE.get(base))
 
 
 def test_header_and_binding_agree():
     assert _declared() == sorted(_lib.SIGNATURES)
+    for name, (ret, params) in declared().items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert _fits(restype, ret), (name, ret, restype)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for ctype, (kind, pname) in zip(argtypes, params):
+            assert _fits(ctype, kind), (name, pname, kind, ctype)
+
+
+def test_the_type_rule_refuses_what_would_load_and_pass_by_name():
+    """what the comparison is for: an `int` bound where the header says `int64_t`, a data pointer bound as a string, one level of
+    indirection too few"""
+    assert not _fits(ctypes.c_int, "int64_t") and not _fits(ctypes.c_int64, "int") and not _fits(ctypes.c_int, "float")
+    assert not _fits(ctypes.c_int64, "size_t") and not _fits(ctypes.c_void_p, "int") and not _fits(ctypes.c_int, "void*")
+    assert not _fits(ctypes.c_void_p, "const char*") and not _fits(ctypes.c_char_p, "const void*")
+    assert not _fits(ctypes.POINTER(ctypes.c_int), "int64_t*") and _fits(ctypes.POINTER(ctypes.c_int64), "const int64_t*")
+    assert not _fits(ctypes.c_void_p, "void**") and not _fits(ctypes.POINTER(ctypes.c_int), "void**")
+    assert _fits(ctypes.POINTER(ctypes.c_void_p), "const float* const*") and _fits(ctypes.POINTER(ctypes.c_char_p), "const char**")
+
+
+def _one_launch_program(name, params):
+    """a program file of one launch of `name` (the layout: paddlemix_amd/export.py): no region, no I/O; integers and floats 0, pointers
+    tagged null, the stream tagged as the stream"""
+    a_int, a_float, a_null, a_stream = 0, 1, 3, 4
+    tags = [a_int if kind in ("int", "int64_t", "size_t") else a_float if kind == "float" else a_null for kind, _ in params]
+    assert all(kind.endswith("*") for (kind, _), t in zip(params, tags) if t == a_null), name
+    if params and params[-1] == ("void*", "stream"):
+        tags[-1] = a_stream
+    sym = name.encode()
+    return (b"MI3SDPRG" + struct.pack("<IIIIIIQ", 1, _lib.ABI_VERSION, _lib._BUILDS[_lib.ELEM_NAME][1], 0, 1, 0, 0) +
+            struct.pack("<I", len(sym)) + sym + struct.pack("<I", len(tags)) + b"".join(struct.pack("<IQQ", t, 0, 0) for t in tags))
+
+
+def test_replay_table_knows_every_launch_of_the_header(tmp_path):
+    """csrc/program_exec.hip op_table(): paddlemix_amd/export.py writes any entry a planner emits, so the C loader must know every one
+    a planner could -- every function of the header whose last parameter is `void* stream`, bar the handle and runtime entries"""
+    from paddlemix_amd.export import ExportedProgram
+    assert {"mi355x_sd_linear", "mi355x_sd_relu", "mi355x_sd_tile_blend", "mi355x_sd_plms_update"} <= set(launches())
+    path = str(tmp_path / "one.mi3prg")
+    for name in launches():
+        open(path, "wb").write(_one_launch_program(name, declared()[name][1]))
+        prog = ExportedProgram(path)                # mi355x_sd_program_load: finds the entry and type-checks the launch against it
+        assert prog.num_launches == 1, name
+        prog.close()
+    assert "mi355x_sd_graph_begin" not in launches()
+    open(path, "wb").write(_one_launch_program("mi355x_sd_graph_begin", declared()["mi355x_sd_graph_begin"][1]))
+    with pytest.raises(_lib.MI355XError, match="unknown entry point 'mi355x_sd_graph_begin'"):
+        ExportedProgram(path)
 
 
 def test_library_loads_and_exports_everything():

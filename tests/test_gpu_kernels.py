@@ -658,3 +658,90 @@ def test_conv3x3_kb64_weight_order(ops, B, H, W, Cin, Cout, stride, up):
     assert (out.float() - out0.float()).abs().max() <= 2 * 2 ** -8 * ref.abs().max()
     with pytest.raises(Exception):
         ops.conv3x3(dev(torch.zeros(1, 4, 4, 40)), dev(torch.zeros(8, 360)), None, kb64=True)      # Cin % 64 != 0
+
+
+def _pair_cases():
+    """name -> build(g): (base entry, its arguments, `_ex` entry, the same arguments with the neutral extra, the tensors the call
+    writes, the tensors it only reads -- returned so that they outlive the addresses). The stream is appended by the test. Shapes: the
+    smallest that still run more than one block or a ragged tail."""
+    p = lambda t: t.data_ptr()  # noqa: E731
+    rn = lambda g, *s: torch.randn(*s, generator=g)  # noqa: E731
+    f32, out16 = (lambda t: t.cuda()), (lambda *s: torch.full(s, 7.25, dtype=torch.bfloat16, device="cuda"))
+
+    def layernorm(g):
+        rows, C = 5, 72
+        x, gam, bet, y = dev(rn(g, rows, C)), f32(rn(g, C)), f32(rn(g, C)), out16(rows, C)
+        a = (p(x), rows, C, C, p(gam), p(bet), 1e-5, p(y), C)
+        return "layernorm", a, "layernorm_ex", a + (0,), [y], [x, gam, bet]
+
+    def adaln(g):
+        rows, C, rpb = 5, 72, 3
+        x, sc, sh, y = dev(rn(g, rows, C)), f32(rn(g, 2, C)), f32(rn(g, 2, C)), out16(rows, C)
+        return ("adaln", (p(x), rows, C, C, p(sc), p(sh), C, rpb, 1e-6, p(y), C),
+                "adaln_ex", (p(x), rows, C, C, p(sc), p(sh), C, 0, rpb, 1e-6, p(y), C), [y], [x, sc, sh])
+
+    def groupnorm_stats(g):
+        from paddlemix_amd import _lib
+        B, HW, C, groups = 2, 9, 64, 8
+        x, gam, bet = dev(rn(g, B * HW, C)), f32(rn(g, C)), f32(rn(g, C))
+        ws = torch.zeros(max(1, _lib.load().mi355x_sd_groupnorm_workspace_floats(B, HW, C)), device="cuda")
+        ss = torch.full((B, 2, C), 7.25, device="cuda")
+        a = (p(x), B, HW, C, C, groups, 1e-5, p(gam), p(bet), p(ws), p(ss))
+        return "groupnorm_stats", a, "groupnorm_stats_ex", a + (0,), [ss], [x, gam, bet, ws]
+
+    def scale_shift_act(g):
+        B, HW, C = 2, 9, 64
+        x, ss, y = dev(rn(g, B * HW, C)), f32(rn(g, B, 2, C)), out16(B * HW, C)
+        a = (p(x), B, HW, C, C, p(ss), 1, p(y), C)
+        return "scale_shift_act", a, "scale_shift_act_ex", a + (0, None, 0), [y], [x, ss]
+
+    def fused_adaln_scale_residual(g):
+        rows, C, rpb = 6, 72, 3
+        x, mha, w, b = dev(rn(g, rows, C)), dev(rn(g, rows, C)), f32(rn(g, C)), f32(rn(g, C))
+        gate, sc, sh = f32(rn(g, 2, C)), f32(rn(g, 2, C)), f32(rn(g, 2, C))
+        resi, y = out16(rows, C), out16(rows, C)
+        head, tail = (p(x), C, p(mha), C, p(gate), p(sc), p(sh), C), (rpb, p(w), p(b), 1e-5, rows, C, p(resi), C, p(y), C)
+        return ("fused_adaln_scale_residual", head + tail, "fused_adaln_scale_residual_ex", head + (0,) + tail, [resi, y],
+                [x, mha, w, b, gate, sc, sh])
+
+    def conv_in3x3(g):
+        B, Cin, H, W, Cout = 1, 4, 5, 7, 32
+        x, w, b, y = f32(rn(g, B, Cin, H, W)), dev(rn(g, 9 * Cin, Cout) / 6), f32(rn(g, Cout)), out16(B * H * W, Cout)
+        a = (p(x), None, p(w), p(b), p(y), B, Cin, H, W, Cout, Cout)
+        return "conv_in3x3", a, "conv_in3x3_ex", a + (0,), [y], [x, w, b]
+
+    def add_nchw(g):
+        B, C, HW = 2, 8, 15
+        x, r = dev(rn(g, B * HW, C)), f32(rn(g, B, C, HW))   # in place: the test restores x between the two calls
+        a = (p(x), C, p(r), B, C, HW)
+        return "add_nchw", a, "add_nchw_ex", a + (0,), [x], [r]
+
+    def sdpa(g):
+        B, H, Sq, Skv, D = 1, 2, 70, 77, 64
+        q, k, v, o = dev(rn(g, B, Sq, H, D)), dev(rn(g, B, Skv, H, D)), dev(rn(g, B, Skv, H, D)), out16(B, Sq, H, D)
+        a = (p(q), p(k), p(v), None, p(o), B, H, Sq, Skv, D, Sq * H * D, H * D, Skv * H * D, H * D, Skv * H * D, H * D, Sq * H * D, H * D,
+             0, 0, 0, D ** -0.5)
+        return "sdpa", a, "sdpa_ex", a + (0,), [o], [q, k, v]
+
+    return {f.__name__: f for f in (layernorm, adaln, groupnorm_stats, scale_shift_act, fused_adaln_scale_residual, conv_in3x3, add_nchw,
+                                    sdpa)}
+
+
+@pytest.mark.parametrize("pair", list(_pair_cases()))
+def test_base_entry_is_its_ex_form_with_the_neutral_extra(ops, pair):
+    """csrc/capi.hip runs a base entry and its `_ex` form through one body, the base entry with x_f32 = 0, mod_dtype = MI355X_SD_MOD_F32,
+    out_f32 = 0, raw16 = NULL / ld_raw = 0 or flags = 0: the two calls write the same bytes."""
+    from paddlemix_amd import _lib
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    base, a, ex, a_ex, written, keep = _pair_cases()[pair](torch.Generator().manual_seed(11))
+    before = [t.clone() for t in written]
+    got = []
+    for entry, args in ((base, a), (ex, a_ex)):
+        for t, b in zip(written, before):
+            t.copy_(b)
+        _lib.check(getattr(lib, "mi355x_sd_" + entry)(*args, st))
+        torch.cuda.synchronize()
+        got.append([t.clone() for t in written])
+    for t0, t1, b in zip(got[0], got[1], before):
+        assert torch.isfinite(t0.float()).all() and not torch.equal(t0, b), (pair, "the base entry wrote nothing")
+        assert torch.equal(t0.view(torch.uint8), t1.view(torch.uint8)), pair

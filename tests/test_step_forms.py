@@ -3,17 +3,15 @@ the ABI: every row against its declaration in include/mi355x_sd.h and its genera
 drifts would have the binding, the wrappers, the loop, the emulators and the GPU children describe an entry that does not exist -- and,
 on a machine without a device, every refusal the table implies against the built library: csrc/capi.hip refuses before anything
 touches the device, so the rule can be asked there with addresses inside one host buffer."""
-import os
-import re
 from ctypes import c_float, c_int, c_int64, c_void_p
 
 import pytest
 import torch
 
 from paddlemix_amd import _lib, ops, step_forms
+from tests.header_decls import declared
 from tests.step_forms import FORMS, TAIL
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CTYPES = {"const float*": c_void_p, "float*": c_void_p, "void*": c_void_p, "int": c_int, "float": c_float, "int64_t": c_int64}
 
 
@@ -36,19 +34,11 @@ def _check(form):
     assert (None in form.written.values()) == ("order" in form.operands)   # a span of `order` planes needs the operand
 
 
-def _declared(entry):
-    """[(type, name)] of the parameters of mi355x_sd_<entry> in the header, comments stripped"""
-    src = open(os.path.join(ROOT, "include", "mi355x_sd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    (params,) = re.findall(r"\bint\s+mi355x_sd_%s\s*\(([^)]*)\)\s*;" % entry, src)
-    return [tuple(" ".join(p.split()).rsplit(" ", 1)) for p in params.split(",")]
-
-
 @pytest.mark.parametrize("name", list(step_forms.FORMS))
 def test_every_form_is_its_declaration_in_the_header(name):
     form = step_forms.FORMS[name]
-    params = _declared(form.entry)
-    assert [n for _, n in params] == list(form.operands + step_forms.TAIL + ("stream",))
+    ret, params = declared()["mi355x_sd_" + form.entry]
+    assert ret == "int" and [n for _, n in params] == list(form.operands + step_forms.TAIL + ("stream",))
     for kind, n in params[:len(form.operands)]:
         assert kind == ("int" if n == "order" else "float*" if n in form.written else "const float*"), (form.entry, kind, n)
     assert [kind for kind, _ in params[len(form.operands):]] == ["float", "float", "int", "int64_t", "void*"]
