@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 23
+#define MI355X_SD_ABI_VERSION 24
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -727,6 +727,46 @@ int mi355x_sd_plms_update(const float* x, const float* eps_uncond, const float* 
 int mi355x_sd_singlestep_update(const float* x, const float* eps_uncond, const float* eps_text, float* park, float* hist, float* out,
                                 const float* coef, float guidance_scale, float guidance_rescale, int batch, int64_t per_sample,
                                 void* stream);
+
+/* ---- InstructPix2Pix (StableDiffusionInstructPix2PixPipeline / StableDiffusionXLInstructPix2PixPipeline; ABI 24) ----
+ * The three-way guidance combine (pipeline_stable_diffusion_instruct_pix2pix.py:394-400), optionally with rescale_noise_cfg
+ * (pipeline_stable_diffusion_xl_instruct_pix2pix.py:105-117, 917-919), into ONE guided plane: what every step-tail entry above takes
+ * as its eps_uncond with eps_text == NULL ("already guided"), so the nine tails run behind it with their bits unchanged.
+ *   eps     the U-Net output of 3 * batch samples of per_sample floats in the reference's order: t = text, i = image, u = uncond
+ *           (plane k starts at eps + k * batch * per_sample)
+ *   out     batch samples
+ * Per element, IN THIS ORDER (tests/ip2p_bounds.py derives its bound from it; each fma rounds once):
+ *   c = fma(guidance_scale, t - i, fma(image_guidance_scale, i - u, u))
+ * Three forms:
+ *  - guidance_rescale <= 0: out = c. x and coef are ignored (not dereferenced): in real arithmetic the reference's conversion to
+ *    predicted originals and back (:388-391, :408-409) cancels, because the weights of t, i, u sum to 1. A grid-stride elementwise
+ *    kernel with 16-byte vectors when eps and out are 16-byte aligned and batch * per_sample is a multiple of 4, element by element
+ *    otherwise; nothing past the planes is read or written.
+ *  - guidance_rescale > 0, x == NULL (a scheduler without `sigmas`): per sample  k = guidance_rescale * std(t) / std(c) + 1 -
+ *    guidance_rescale,  out = c * k. std is the unbiased estimator over the sample's per_sample elements, each variance by two passes
+ *    (the mean, then the squared deviations), every sum the fixed tree of mi355x_sd_cfg_rescale_axpby: no atomics, equal inputs give
+ *    equal bits. One 1024-thread block per sample, no scratch; a sample of <= 32768 elements stays in registers, larger ones are
+ *    re-read. A sample of zero variance divides as the reference does (inf / NaN).
+ *  - guidance_rescale > 0, x != NULL (a sigma-space scheduler; the reference combines and rescales predicted originals, :903-930):
+ *    x is the UNSCALED latents of batch samples, sigma = coef[0] a float in device memory (a row of the loop's sigma table, so a
+ *    captured graph replays with another row). p_b = fma(-sigma, e_b, x) for b in t, i, u;  cp = the combine above of p_t, p_i, p_u;
+ *    k from std(p_t) and std(cp);  out = (cp * k - x) / (-sigma). sigma == 0 divides by zero: no step of a loop has it.
+ * MI355X_SD_ERR_INVALID before any launch: a null eps or out; x without coef (under the rescale); batch <= 0, per_sample < 1,
+ * per_sample < 2 with guidance_rescale > 0, 3 * batch * per_sample * 4 bytes past int64_t; out overlapping eps, or -- under the
+ * rescale -- x or coef. */
+int mi355x_sd_guidance3(const float* eps, const float* x, const float* coef, float* out, float guidance_scale,
+                        float image_guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream);
+/* The U-Net input of an InstructPix2Pix step in one launch (pipeline_stable_diffusion_instruct_pix2pix.py:373-377:
+ * concat([latents] * 3), scheduler.scale_model_input, the channel concat with the image latents). out[g * batch + b], g < groups, is an
+ * NCHW sample of c_lat + c_img channels of hw elements:
+ *   channels [0, c_lat)              scale * x[b]          one fp32 multiply per element; the same plane for every g
+ *   channels [c_lat, c_lat + c_img)  image_latents[g * batch + b]     copied bit for bit
+ * x is batch samples of c_lat * hw floats, image_latents groups * batch samples of c_img * hw floats. groups is 3 under guidance and 1
+ * without it. 16-byte vectors when the three pointers are 16-byte aligned and c_lat * hw and c_img * hw are multiples of 4, element by
+ * element otherwise. MI355X_SD_ERR_INVALID: a null pointer; groups, batch, c_lat, c_img or hw < 1; out's size in bytes past int64_t;
+ * out overlapping x or image_latents. MI355X_SD_ERR_UNSUPPORTED: groups * batch > 65535. */
+int mi355x_sd_ip2p_input(const float* x, const float* image_latents, float* out, float scale, int groups, int batch, int c_lat,
+                         int c_img, int64_t hw, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

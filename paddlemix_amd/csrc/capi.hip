@@ -180,6 +180,37 @@ static int step_entry(const char* who, std::initializer_list<StepOperand> operan
   return finish(launch(rescale ? guidance_rescale : 0.0f), who);
 }
 
+// The argument rule of the InstructPix2Pix entries (ip2p.hip), stated once: an entry names its pointers in the header's order with the
+// floats each spans -- paddlemix_amd/ip2p_forms.py holds the same rows for the Python side, tests/test_ip2p_host.py generates every
+// refusal from them. A pointer that takes no part in the call (`used` false) is neither checked nor dereferenced. The rule: no null
+// among the used pointers unless optional; the entry's own range check, after which the span lengths are meaningful; a written span
+// overlaps no other used span.
+struct Span {
+  const char* name;
+  const void* p;
+  int64_t floats;
+  bool written, optional, used;
+};
+template <class Launch>
+static int span_entry(const char* who, std::initializer_list<Span> spans, const char* range_rule, bool in_range, Launch launch) {
+  auto refuse = [who](const char* rule, const char* a = "", const char* b = "") {
+    snprintf(g_err, sizeof(g_err), rule, who, a, b);
+    return (int)SD_ERR_INVALID;
+  };
+  for (const Span& s : spans)
+    if (s.used && !s.p && !s.optional) return refuse("%s: null pointer (%s)", s.name);
+  if (!in_range) return refuse(range_rule);
+  for (const Span& w : spans) {
+    if (!w.written) continue;
+    for (const Span& v : spans) {
+      if (&v == &w || !v.used || !v.p) continue;
+      const uintptr_t a = (uintptr_t)w.p, la = (uintptr_t)w.floats * 4, b = (uintptr_t)v.p, lb = (uintptr_t)v.floats * 4;
+      if (a < b + lb && b < a + la) return refuse("%s: %s must not overlap %s", w.name, v.name);
+    }
+  }
+  return finish(launch(), who);
+}
+
 extern "C" {
 
 int mi355x_sd_abi_version(void) { return MI355X_SD_ABI_VERSION; }
@@ -733,6 +764,34 @@ int mi355x_sd_singlestep_update(const float* x, const float* eps_uncond, const f
                     {coef, 8, 1, true}, eps_text, guidance_rescale, false, batch, per_sample, [&](float gr) {
                       return launch_singlestep_update(x, eps_uncond, eps_text, park, hist, out, coef, guidance_scale, gr, batch,
                                                       (long)per_sample, S(stream));
+                    });
+}
+
+// ---- the InstructPix2Pix entries (ip2p.hip): each is one call of span_entry(), defined before the extern "C" block ----
+int mi355x_sd_guidance3(const float* eps, const float* x, const float* coef, float* out, float guidance_scale,
+                        float image_guidance_scale, float guidance_rescale, int batch, int64_t per_sample, void* stream) {
+  const bool rescale = guidance_rescale > 0.0f, x0 = rescale && x;
+  const bool ok = batch > 0 && per_sample >= (rescale ? 2 : 1) && per_sample <= INT64_MAX / 4 / 3 / batch;
+  const int64_t n = ok ? (int64_t)batch * per_sample : 0;
+  return span_entry("mi355x_sd_guidance3", {{"eps", eps, 3 * n, false, false, true}, {"x", x, n, false, true, rescale},
+                                            {"coef", coef, 1, false, false, x0}, {"out", out, n, true, false, true}},
+                    "%s: needs batch > 0 and per_sample >= 1 (>= 2 with guidance_rescale: the estimator divides by per_sample - 1)", ok,
+                    [&] {
+                      return launch_guidance3(eps, x0 ? x : nullptr, x0 ? coef : nullptr, out, guidance_scale, image_guidance_scale,
+                                              rescale ? guidance_rescale : 0.0f, batch, (long)per_sample, S(stream));
+                    });
+}
+
+int mi355x_sd_ip2p_input(const float* x, const float* image_latents, float* out, float scale, int groups, int batch, int c_lat,
+                         int c_img, int64_t hw, void* stream) {
+  const bool ok = groups > 0 && batch > 0 && c_lat > 0 && c_img > 0 && hw > 0 &&
+                  hw <= INT64_MAX / 4 / groups / batch / ((int64_t)c_lat + c_img);
+  const int64_t gb = ok ? (int64_t)groups * batch : 0;
+  return span_entry("mi355x_sd_ip2p_input", {{"x", x, ok ? (int64_t)batch * c_lat * hw : 0, false, false, true},
+                                             {"image_latents", image_latents, gb * c_img * hw, false, false, true},
+                                             {"out", out, gb * ((int64_t)c_lat + c_img) * hw, true, false, true}},
+                    "%s: needs groups, batch, c_lat, c_img and hw >= 1", ok, [&] {
+                      return launch_ip2p_input(x, image_latents, out, scale, groups, batch, c_lat, c_img, (long)hw, S(stream));
                     });
 }
 

@@ -190,6 +190,12 @@ int launch_plms_update(const float* x, const float* eu, const float* et, float* 
                        float gs, float gr, int batch, long per_sample, hipStream_t stream);
 int launch_singlestep_update(const float* x, const float* eu, const float* et, float* park, float* hist, float* out, const float* coef,
                              float gs, float gr, int batch, long per_sample, hipStream_t stream);
+// InstructPix2Pix (ip2p.hip): the three-way guidance combine (+ rescale, in eps or in x0 space) into one guided plane, and the
+// [scale * latents | image latents] model input of `groups` x batch samples
+int launch_guidance3(const float* eps, const float* x, const float* coef, float* out, float gs, float gi, float gr, int batch,
+                     long per_sample, hipStream_t stream);
+int launch_ip2p_input(const float* x, const float* img, float* out, float scale, int groups, int batch, int c_lat, int c_img, long hw,
+                      hipStream_t stream);
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 

@@ -28,6 +28,7 @@
 //                                        scheduling_dpmsolver_singlestep.py
 #include "common.h"
 #include "kernels.h"
+#include "rescale_stats.h"
 
 namespace sd {
 
@@ -41,28 +42,9 @@ namespace sd {
 // c in registers: samples of up to CRA_THREADS * CRA_RES = 32768 elements are read from memory once (RESIDENT); larger ones (the
 // 4 x 128 x 128 SDXL latent is 65536) read eu / et three times, the second and third time from L2 (<= 2 MB per step: latency, not
 // bandwidth). The step's own operands are read and written by the same lane in the last pass only, so out may be x.
-constexpr int CRA_THREADS = 1024, CRA_RES = 32;
+// (CRA_THREADS, CRA_RES and block_sum2, the block-wide pair of sums: rescale_stats.h, shared with ip2p.hip)
 
 __device__ __forceinline__ float cfg_mix(float u, float t, float gs) { return fmaf(gs, t - u, u); }
-
-// a, b <- their sums over the block, in every lane; part: LDS [2][16]
-__device__ __forceinline__ void block_sum2(float& a, float& b, float (*part)[CRA_THREADS / 64]) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63;
-  __syncthreads();   // (the readers of the previous call are done with part)
-  if (lane == 0) {
-    part[0][threadIdx.x >> 6] = a;
-    part[1][threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  a = part[0][lane & 15];
-  b = part[1][lane & 15];
-  for (int o = 8; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-}
 
 // The statistics passes of a sample: k = gr * std(et) / std(c) + (1 - gr), the same bits in every lane. RESIDENT: cv[j] <- c of the
 // lane's element tid + j * CRA_THREADS (0 past n), kept for the caller's last pass.

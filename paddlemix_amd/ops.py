@@ -456,6 +456,55 @@ def unipc_update(x: Tensor, eps_uncond: Tensor, eps_text: Optional[Tensor], last
     return _step(FORMS["unipc"], locals(), "coef: expected a contiguous, 16-byte aligned fp32 GPU tensor of the 12 UniPC coefficients")
 
 
+def guidance3(eps: Tensor, guidance_scale: float, image_guidance_scale: float, guidance_rescale: float = 0.0,
+              x: Optional[Tensor] = None, sigma: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The InstructPix2Pix guidance in one launch -> out [B, ...]. eps: contiguous fp32 [3 B, ...], the U-Net output in the order
+    text, image, uncond. c = fma(gs, t - i, fma(gi, i - u, u)); guidance_rescale > 0: c * (gr * std(t) / std(c) + 1 - gr) per sample --
+    with ``x`` (the unscaled latents [B, ...]) and ``sigma`` (an fp32 GPU tensor, its first element read on the device) combined and
+    rescaled on the predicted originals x - sigma * e and converted back, as the reference does for a sigma-space scheduler."""
+    lib = _lib.load()
+    _flat_f32(eps, "eps")
+    if eps.dim() < 2 or eps.shape[0] < 3 or eps.shape[0] % 3 or eps.numel() < 3:
+        raise ValueError(f"eps: expected a non-empty [3 * B, ...], got {tuple(eps.shape)}")
+    shape = (eps.shape[0] // 3,) + tuple(eps.shape[1:])
+    n = eps.numel() // 3
+    if guidance_rescale > 0.0 and n // shape[0] < 2:
+        raise ValueError(f"eps: guidance_rescale needs at least 2 elements per sample, got {tuple(eps.shape)}")
+    if x is not None:
+        _flat_f32(x, "x", n)
+        if not isinstance(sigma, torch.Tensor) or not sigma.is_cuda or sigma.dtype != torch.float32 or sigma.numel() < 1 or \
+                not sigma.is_contiguous():
+            raise ValueError("sigma: `x` needs a contiguous fp32 GPU tensor whose first element is the step's sigma")
+    if out is None:
+        out = torch.empty(shape, device=eps.device, dtype=torch.float32)
+    else:
+        _flat_f32(out, "out", n)
+    check(lib.mi355x_sd_guidance3(eps.data_ptr(), _p(x), _p(sigma) if x is not None else None, out.data_ptr(), float(guidance_scale),
+                                  float(image_guidance_scale), float(guidance_rescale), shape[0], n // shape[0], _stream()))
+    return out
+
+
+def ip2p_input(x: Tensor, image_latents: Tensor, scale: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """The U-Net input of an InstructPix2Pix step in one launch -> [G B, c_lat + c_img, H, W]: channels [0, c_lat) are scale * x[b]
+    for every group, the others image_latents[g B + b]. x: contiguous fp32 [B, c_lat, H, W]; image_latents: [G B, c_img, H, W]."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    _flat_f32(image_latents, "image_latents")
+    if x.dim() != 4 or image_latents.dim() != 4 or x.numel() < 1 or image_latents.numel() < 1 or \
+            image_latents.shape[0] % x.shape[0] or image_latents.shape[2:] != x.shape[2:]:
+        raise ValueError(f"expected x [B, c_lat, H, W] and image_latents [G * B, c_img, H, W], got {tuple(x.shape)} and "
+                         f"{tuple(image_latents.shape)}")
+    B, c_lat, H, W = x.shape
+    GB, c_img = image_latents.shape[:2]
+    if out is None:
+        out = torch.empty((GB, c_lat + c_img, H, W), device=x.device, dtype=torch.float32)
+    else:
+        _flat_f32(out, "out", GB * (c_lat + c_img) * H * W)
+    check(lib.mi355x_sd_ip2p_input(x.data_ptr(), image_latents.data_ptr(), out.data_ptr(), float(scale), GB // B, B, c_lat, c_img, H * W,
+                                   _stream()))
+    return out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

@@ -12,6 +12,7 @@ stays outside: the loop starts from ``prompt_embeds``.
 from __future__ import annotations
 
 import inspect
+import warnings
 from contextlib import nullcontext
 from typing import Callable, Dict, Optional
 
@@ -449,6 +450,137 @@ class StableDiffusionDenoiser(_VaeSwitches):
         ts = torch.as_tensor(np.asarray(timestep).reshape(-1)[:1]).repeat(init.shape[0])
         return self.scheduler.add_noise(init, noise, ts)
 
+    def prepare_ip2p_image_latents(self, image: torch.Tensor, batch_size: int, do_cfg: bool) -> torch.Tensor:
+        """InstructPix2Pix ``prepare_image_latents`` (pipeline_stable_diffusion_instruct_pix2pix.py:706-745): the MODE of the
+        posterior, left unscaled (no ``scaling_factor``); latents passed as `image` (4 channels) are taken as they are; duplicated to
+        the prompt batch with the reference's deprecation warning, or refused with its ValueError; ``[img, img, zeros]`` under guidance. The SDXL pipeline (pipeline_stable_diffusion_xl_instruct_pix2pix.py:
+        513-553) differs only in running a float16 VAE in float32 for the encode (:516-526) -- this VAE always encodes from fp32
+        input -- and applies no latent statistics (``latents_mean`` / ``latents_std`` enter only its decode, :948-957)."""
+        if not torch.is_tensor(image) or image.dim() != 4:
+            raise ValueError(f"`image` has to be of type `torch.Tensor` [B, C, H, W] but is {type(image)}")
+        image = image.to(torch.float32)
+        if image.shape[1] == 4:
+            il = image
+        else:
+            if self.vae is None:
+                raise ValueError("an image input needs a `vae` with encoder parameters")
+            il = self.vae.encode(image).latent_dist.mode()
+        if batch_size > il.shape[0] and batch_size % il.shape[0] == 0:
+            warnings.warn(   # (:724-731: the reference's deprecation message, word for word)
+                f"You have passed {batch_size} text prompts (`prompt`), but only {il.shape[0]} initial images (`image`). Initial images "
+                "are now duplicating to match the number of text prompts. Note that this behavior is deprecated and will be removed in "
+                "a version 1.0.0. Please make sure to update your script to pass as many initial images as text prompts to suppress "
+                "this warning.", FutureWarning, stacklevel=2)
+            il = torch.cat([il] * (batch_size // il.shape[0]), dim=0)
+        elif batch_size > il.shape[0]:
+            raise ValueError(f"Cannot duplicate `image` of batch size {il.shape[0]} to {batch_size} text prompts.")
+        if do_cfg:
+            il = torch.cat([il, il, torch.zeros_like(il)], dim=0)
+        return il.contiguous()
+
+    def _instruct_pix2pix(self, prompt_embeds, negative_prompt_embeds, image, num_inference_steps, guidance_scale,
+                          image_guidance_scale, guidance_rescale, latents, generator, added_cond_kwargs, negative_added_cond_kwargs,
+                          callback_on_step_end, vae_scale_factor, output_type, ids, original_size, crops_coords_top_left, target_size,
+                          fused_update, eta):
+        """The loop of StableDiffusionInstructPix2PixPipeline.__call__ (pipeline_stable_diffusion_instruct_pix2pix.py:283-430) and of
+        its SDXL twin (pipeline_stable_diffusion_xl_instruct_pix2pix.py:756-938). Per step two launches around the U-Net:
+        ``mi355x_sd_ip2p_input`` builds ``[scale * latents | image latents]`` for the three guidance groups (:373-377), and
+        ``mi355x_sd_guidance3`` writes the guided output (:394-400; with ``guidance_rescale`` also rescale_noise_cfg, SDXL :917-919, on
+        the predicted originals when the scheduler has ``sigmas``, :903-906, :927-928). The scheduler's tail then runs with no guidance
+        of its own. Without the rescale the reference's detour through predicted originals cancels in real arithmetic -- the three
+        weights sum to 1 -- and is not taken."""
+        if image is None:
+            raise ValueError("`image` input cannot be undefined.")
+        if getattr(self.unet.config, "time_cond_proj_dim", None) is not None:
+            raise NotImplementedError("a guidance-distilled U-Net (`time_cond_proj_dim`) together with `image_guidance_scale` "
+                                      "(InstructPix2Pix) is not implemented")
+        lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
+        if lib is None:
+            raise _lib.MI355XError("InstructPix2Pix runs its guidance and input kernels through the U-Net's library: the `unet` has none")
+        do_cfg = guidance_scale > 1.0 and image_guidance_scale >= 1.0   # (SD :764)
+        prompt_ids, negative_prompt_ids, prompt_ids_2, negative_prompt_ids_2 = ids
+        pooled = neg_pooled = None
+        if prompt_embeds is None:
+            if prompt_ids is None:
+                raise ValueError("Provide either `prompt_embeds` or `prompt_ids`")
+            prompt_embeds, pooled = self.encode_prompt(prompt_ids, prompt_ids_2)
+            if do_cfg and negative_prompt_embeds is None:
+                if negative_prompt_ids is not None:
+                    negative_prompt_embeds, neg_pooled = self.encode_prompt(negative_prompt_ids, negative_prompt_ids_2)
+                elif self.text_encoder_2 is not None:   # SDXL: force_zeros_for_empty_prompt
+                    negative_prompt_embeds, neg_pooled = torch.zeros_like(prompt_embeds), torch.zeros_like(pooled)
+        if do_cfg and negative_prompt_embeds is None:
+            raise ValueError("classifier-free guidance needs `negative_prompt_embeds` (or `negative_prompt_ids`)")
+        B, cfg, sch = prompt_embeds.shape[0], self.unet.config, self.scheduler
+        # asked before ``set_timesteps``, as the reference asks (SD :307 before :323, SDXL :772 before :801): Euler, Euler a, Heun and
+        # DPM2 have ``sigmas`` from ``__init__``; the DPM-Solver classes and UniPC build theirs in ``set_timesteps`` and, freshly built,
+        # rescale in eps space (they are alpha-space: x - sigma * e is no predicted original there)
+        in_sigma_space = hasattr(sch, "sigmas")
+        sch.set_timesteps(num_inference_steps)
+        timesteps = sch.timesteps
+        il = self.prepare_ip2p_image_latents(image, B, do_cfg).to(prompt_embeds.device)
+        h, w = il.shape[-2:]
+        c_lat = self.vae.config.latent_channels if self.vae is not None else 4
+        latents = self.prepare_latents(B, c_lat, h, w, torch.float32, generator, latents, prompt_embeds.device)
+        c_img = il.shape[1]
+        if c_lat + c_img != cfg.in_channels:   # (SD :353-360)
+            raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet`: {cfg} expects {cfg.in_channels} but "
+                             f"received `num_channels_latents`: {c_lat} + `num_channels_image`: {c_img}  = {c_lat + c_img}. Please "
+                             "verify the config of `pipeline.unet` or your `image` input.")
+        if pooled is not None and added_cond_kwargs is None:   # SDXL micro-conditioning (SDXL :839-852)
+            hw = (h * vae_scale_factor, w * vae_scale_factor)
+            tids = self.get_add_time_ids(tuple(original_size or hw), tuple(crops_coords_top_left), tuple(target_size or hw),
+                                         pooled.shape[-1], pooled.device).repeat(B, 1)
+            added_cond_kwargs = {"text_embeds": pooled, "time_ids": tids}
+            if do_cfg:
+                negative_added_cond_kwargs = {"text_embeds": neg_pooled, "time_ids": tids}
+        if do_cfg:   # [text, negative, negative] (SD :591, SDXL :856-860)
+            prompt_embeds = torch.cat([prompt_embeds, negative_prompt_embeds, negative_prompt_embeds])
+            if added_cond_kwargs is not None:
+                neg = negative_added_cond_kwargs or added_cond_kwargs
+                added_cond_kwargs = {k: torch.cat([v, neg[k], neg[k]]) for k, v in added_cond_kwargs.items()}
+        step_params = inspect.signature(sch.step).parameters
+        extra = {}
+        if "eta" in step_params:
+            extra["eta"] = eta
+        if "generator" in step_params:
+            extra["generator"] = generator
+        dev = latents.device
+        tail = (self._fused_plan(False, dev, timesteps, generator) if fused_update and not eta else None) or _GenericTail(sch, extra)
+        fused = isinstance(tail, _FusedTail)
+        rescale = float(guidance_rescale) if do_cfg and guidance_rescale > 0.0 else 0.0
+        sigmas = None
+        if rescale and in_sigma_space:   # the loop's sigmas as a device table, uploaded once: a step passes its row's address
+            sigmas = torch.tensor(np.asarray(sch.sigmas, dtype=np.float32), device=dev).contiguous()
+        groups, per_sample = (3 if do_cfg else 1), c_lat * h * w
+        model_in = torch.empty((groups * B, c_lat + c_img, h, w), dtype=torch.float32, device=dev)
+        for i, t in enumerate(timesteps):
+            stream = program.caller_stream(dev, emulated)
+            lat = latents.contiguous()
+            if fused:
+                x_in, scale = lat, (1.0 if tail.scales is None else tail.scales[i])
+            else:
+                x_in, scale = tail.scale(lat, i, t).contiguous(), 1.0
+            _lib.check(lib.mi355x_sd_ip2p_input(x_in.data_ptr(), il.data_ptr(), model_in.data_ptr(), float(scale), groups, B, c_lat,
+                                                c_img, h * w, stream))
+            e = self.unet(model_in, t, encoder_hidden_states=prompt_embeds, added_cond_kwargs=added_cond_kwargs, return_dict=False)[0]
+            if do_cfg:
+                eps, e = e.contiguous(), torch.empty_like(lat)
+                x_ptr = row = None
+                if sigmas is not None:
+                    # the reference's ``(timesteps == t).nonzero()[0]``: the FIRST match (Heun and DPM2 repeat their timesteps)
+                    first = int(np.nonzero(np.asarray(sch.timesteps) == np.asarray(t))[0][0])
+                    x_ptr, row = lat.data_ptr(), sigmas.data_ptr() + 4 * first
+                _lib.check(lib.mi355x_sd_guidance3(eps.data_ptr(), x_ptr, row, e.data_ptr(), float(guidance_scale),
+                                                   float(image_guidance_scale), rescale, B, per_sample, stream))
+            latents = tail.update(lat, e.contiguous(), i, t, False, 1.0, 0.0)
+            if callback_on_step_end is not None:
+                out = callback_on_step_end(self, i, t, {"latents": latents})
+                latents = out.pop("latents", latents)
+        if output_type == "latent":
+            return latents
+        return self.decode_latents(latents, output_type)
+
     @torch.no_grad()
     def __call__(self, prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
@@ -464,7 +596,7 @@ class StableDiffusionDenoiser(_VaeSwitches):
                  mask_image: Optional[torch.Tensor] = None, masked_image_latents: Optional[torch.Tensor] = None,
                  control_image: Optional[torch.Tensor] = None, controlnet_conditioning_scale: float = 1.0,
                  guess_mode: bool = False, adapter_image=None, adapter_conditioning_scale=1.0,
-                 adapter_conditioning_factor: float = 1.0):
+                 adapter_conditioning_factor: float = 1.0, image_guidance_scale: Optional[float] = None):
         """``image`` (extension of the text2img call = StableDiffusionImg2ImgPipeline.__call__,
         pipeline_stable_diffusion_img2img.py:735-1010): start from the encoded, re-noised image and run the last
         ``int(num_inference_steps * strength)`` steps (strength defaults to 0.8).
@@ -480,7 +612,19 @@ class StableDiffusionDenoiser(_VaeSwitches):
         ``adapter_conditioning_scale`` (a list for a MultiAdapter: its ``adapter_weights``), repeated to the prompt batch and doubled
         under classifier-free guidance, go to the U-Net as ``down_intrablock_additional_residuals`` on the steps
         ``i < int(num_inference_steps * adapter_conditioning_factor)``; the other steps run the plain plan. Height and width default
-        to the image's, floored to a multiple of ``adapter.downscale_factor``."""
+        to the image's, floored to a multiple of ``adapter.downscale_factor``.
+
+        ``image`` + ``image_guidance_scale`` (= StableDiffusionInstructPix2PixPipeline / StableDiffusionXLInstructPix2PixPipeline
+        .__call__): instruction-based editing on an 8-channel U-Net, see ``_instruct_pix2pix``. ``strength`` is not used."""
+        if image_guidance_scale is not None:
+            for name, v in (("mask_image", mask_image), ("control_image", control_image), ("adapter_image", adapter_image)):
+                if v is not None:
+                    raise NotImplementedError(f"`{name}` together with `image_guidance_scale` (InstructPix2Pix) is not implemented")
+            return self._instruct_pix2pix(
+                prompt_embeds, negative_prompt_embeds, image, num_inference_steps, guidance_scale, image_guidance_scale,
+                guidance_rescale, latents, generator, added_cond_kwargs, negative_added_cond_kwargs, callback_on_step_end,
+                vae_scale_factor, output_type, (prompt_ids, negative_prompt_ids, prompt_ids_2, negative_prompt_ids_2), original_size,
+                crops_coords_top_left, target_size, fused_update, eta)
         inpaint = mask_image is not None
         adapter_hw = None
         if adapter_image is not None:
