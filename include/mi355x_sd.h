@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 24
+#define MI355X_SD_ABI_VERSION 25
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -767,6 +767,45 @@ int mi355x_sd_guidance3(const float* eps, const float* x, const float* coef, flo
  * out overlapping x or image_latents. MI355X_SD_ERR_UNSUPPORTED: groups * batch > 65535. */
 int mi355x_sd_ip2p_input(const float* x, const float* image_latents, float* out, float scale, int groups, int batch, int c_lat,
                          int c_img, int64_t hw, void* stream);
+
+/* ---- Semantic guidance (SEGA: SemanticStableDiffusionPipeline, pipeline_semantic_stable_diffusion.py:541-699; ABI 25) ----
+ * ONE launch between the U-Net and a step-tail entry (which takes `out` as its eps_uncond with eps_text == NULL): the classifier-free
+ * guidance, every editing concept's quantile-masked direction, the warm-up regimes, the momentum and the caller's extra plane.
+ *   eps       the U-Net output of (2 + n_concepts) * batch NCHW samples of channels * hw floats, groups in the reference's order
+ *             u = uncond, t = text, e_0 .. e_{n-1}, concept-major (group k starts at eps + k * batch * channels * hw)
+ *   momentum  batch samples, read and written in place (zero before the first step; it lives as long as the loop)
+ *   extra     the step's sem_guidance plane of batch samples, or NULL
+ *   row       this step's row of the table paddlemix_amd/sega_forms.py builds, 8 + 5 * n_concepts 32-bit words in DEVICE memory (a
+ *             captured step replays with the next row):
+ *               0 regime (int: 0 none warm, 1 partial, 2 all warm)   1 active (int, bit c: concept c is not cooled down)
+ *               2 warm (int, bit c)   3 unused   4 gs   5 ms = edit_momentum_scale   6 beta = edit_mom_beta   7 omb = 1 - beta
+ *               per concept c at 8 + 5 c:  +0 scale (signed)  +1 lo (int)  +2 frac  +3 w_full  +4 w_part
+ *   out       batch samples: the guided noise prediction
+ *   stats     NULL, or 3 * n_concepts * batch * channels floats: (v[lo], v[hi], thr) of plane (c, sample, channel), for tests; zeros
+ *             for a cooled-down concept
+ * Per (sample, channel) plane of hw elements and per active concept c:
+ *   g = (e_c - u) * scale                        a subtraction, then a multiplication: the reference's two roundings
+ *   v = the ascending order statistics of |g| over the plane; hi = lo when frac == 0, else lo + 1 (lo clamped to [0, hw - 1])
+ *   thr = lerp(v[lo], v[hi], frac)               torch.quantile's rule; frac < 0.5: fma(frac, v[hi] - v[lo], v[lo]), otherwise
+ *                                                fma(frac - 1, v[hi] - v[lo], v[hi]); NaN when the plane holds a NaN
+ *   g_c = |g| >= thr ? g : 0                     (a cooled-down concept: g_c = 0)
+ * The selection is EXACT: a radix select over the bit patterns of |g| (they order as unsigned integers) with integer counts in LDS;
+ * no floating-point value is reduced across elements, so equal inputs give equal bits. Then per element, IN THIS ORDER
+ * (tests/sega_bounds.py derives its bound from it; each fma rounds once):
+ *   guid = gs * (t - u)
+ *   edit = 0; part = 0;  for c = 0 .. n - 1:  edit = fma(w_full_c, g_c, edit);  if warm bit c:  part = fma(w_part_c, g_c, part)
+ *   regime 1:  guid = guid + part
+ *   edit = fma(ms, momentum, edit);  momentum' = fma(beta, momentum, omb * edit)
+ *   regime 2:  guid = guid + edit
+ *   extra:     guid = guid + extra
+ *   out = u + guid
+ * One block of 1024 threads per (sample, channel); the keys are recomputed from eps on every digit pass (L2-resident), LDS holds a
+ * 256-bin histogram. 16-byte loads in the selection when eps is 16-byte aligned and hw % 4 == 0.
+ * MI355X_SD_ERR_INVALID before any launch: a null eps, momentum, row or out; n_concepts, batch, channels or hw < 1; a size in bytes
+ * past int64_t; momentum, out or stats overlapping any other operand. MI355X_SD_ERR_UNSUPPORTED: n_concepts > 8, hw > 65536 (a
+ * 256 x 256 latent), batch * channels > 2^31 - 1. */
+int mi355x_sd_sega_guidance(const float* eps, float* momentum, const float* extra, const float* row, float* out, float* stats,
+                            int n_concepts, int batch, int channels, int64_t hw, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

@@ -795,6 +795,24 @@ int mi355x_sd_ip2p_input(const float* x, const float* image_latents, float* out,
                     });
 }
 
+// ---- semantic guidance (sega.hip): the same span rule; paddlemix_amd/sega_forms.py holds the row for the Python side ----
+int mi355x_sd_sega_guidance(const float* eps, float* momentum, const float* extra, const float* row, float* out, float* stats,
+                            int n_concepts, int batch, int channels, int64_t hw, void* stream) {
+  const bool ok = n_concepts > 0 && batch > 0 && channels > 0 && hw > 0 &&
+                  hw <= INT64_MAX / 4 / ((int64_t)n_concepts + 2) / batch / channels;
+  const int64_t planes = ok ? (int64_t)batch * channels : 0, n = planes * hw;
+  return span_entry("mi355x_sd_sega_guidance",
+                    {{"eps", eps, (2 + (int64_t)n_concepts) * n, false, false, true},
+                     {"momentum", momentum, n, true, false, true},
+                     {"extra", extra, n, false, true, extra != nullptr},
+                     {"row", row, 8 + 5 * (int64_t)n_concepts, false, false, true},
+                     {"out", out, n, true, false, true},
+                     {"stats", stats, 3 * n_concepts * planes, true, true, stats != nullptr}},
+                    "%s: needs n_concepts, batch, channels and hw >= 1", ok, [&] {
+                      return launch_sega_guidance(eps, momentum, extra, row, out, stats, n_concepts, batch, channels, (long)hw, S(stream));
+                    });
+}
+
 int mi355x_sd_graph_begin(void* stream) {
   if (hipStreamBeginCapture(S(stream), hipStreamCaptureModeThreadLocal) != hipSuccess)
     return finish(SD_ERR_HIP, "mi355x_sd_graph_begin");

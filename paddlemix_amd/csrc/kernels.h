@@ -196,6 +196,10 @@ int launch_guidance3(const float* eps, const float* x, const float* coef, float*
                      long per_sample, hipStream_t stream);
 int launch_ip2p_input(const float* x, const float* img, float* out, float scale, int groups, int batch, int c_lat, int c_img, long hw,
                       hipStream_t stream);
+// Semantic guidance (sega.hip): per (concept, sample, channel) plane an exact radix select of the quantile of |g|, then the guided
+// output and the momentum update in one elementwise pass; every per-step scalar from `row` in device memory
+int launch_sega_guidance(const float* eps, float* momentum, const float* extra, const float* row, float* out, float* stats, int n,
+                         int batch, int channels, long hw, hipStream_t stream);
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 

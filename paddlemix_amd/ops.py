@@ -505,6 +505,37 @@ def ip2p_input(x: Tensor, image_latents: Tensor, scale: float = 1.0, out: Option
     return out
 
 
+def sega_guidance(eps: Tensor, momentum: Tensor, row: Tensor, n_concepts: int, extra: Optional[Tensor] = None,
+                  out: Optional[Tensor] = None, stats: Optional[Tensor] = None) -> Tensor:
+    """Semantic guidance in one launch -> out [B, C, H, W], the guided noise prediction; ``momentum`` [B, C, H, W] is updated in place.
+    eps: contiguous fp32 [(2 + n) B, C, H, W], the U-Net output in the order uncond, text, concept 0 .. n - 1 (concept-major); row: one
+    row of ``sega_forms.rows`` on the GPU (int32 or fp32, 8 + 5 n words), read on the device; extra: the step's ``sem_guidance``
+    plane; stats: fp32 [n, B, C, 3] receiving (v[lo], v[hi], thr) of every plane's selection."""
+    from . import sega_forms
+    lib = _lib.load()
+    _flat_f32(eps, "eps")
+    n = int(n_concepts)
+    if n < 1 or eps.dim() != 4 or eps.shape[0] % (2 + n) or eps.numel() < 1:
+        raise ValueError(f"eps: expected a non-empty [(2 + {n}) * B, C, H, W], got {tuple(eps.shape)}")
+    B, C, H, W = eps.shape[0] // (2 + n), eps.shape[1], eps.shape[2], eps.shape[3]
+    plane = B * C * H * W
+    _flat_f32(momentum, "momentum", plane)
+    if extra is not None:
+        _flat_f32(extra, "extra", plane)
+    if not isinstance(row, torch.Tensor) or not row.is_cuda or row.dtype not in (torch.float32, torch.int32) or \
+            not row.is_contiguous() or row.numel() < sega_forms.row_words(n):
+        raise ValueError(f"row: expected a contiguous GPU tensor of {sega_forms.row_words(n)} 32-bit words (sega_forms.rows)")
+    if stats is not None:
+        _flat_f32(stats, "stats", 3 * n * B * C)
+    if out is None:
+        out = torch.empty((B, C, H, W), device=eps.device, dtype=torch.float32)
+    else:
+        _flat_f32(out, "out", plane)
+    check(lib.mi355x_sd_sega_guidance(eps.data_ptr(), momentum.data_ptr(), _p(extra), row.data_ptr(), out.data_ptr(), _p(stats), n, B, C,
+                                      H * W, _stream()))
+    return out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

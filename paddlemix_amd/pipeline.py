@@ -19,7 +19,7 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, program
+from . import _lib, program, sega_forms
 from .step_forms import FORMS
 
 
@@ -581,6 +581,143 @@ class StableDiffusionDenoiser(_VaeSwitches):
             return latents
         return self.decode_latents(latents, output_type)
 
+    @staticmethod
+    def semantic_guidance_torch(i, raw, n, momentum, extra, guidance_scale, edit_momentum_scale, edit_mom_beta, per_concept):
+        """One step of the reference's semantic guidance (pipeline_semantic_stable_diffusion.py:541-699) in torch ops on the device of
+        `raw`, the U-Net output of (2 + n) * B samples -> (noise_pred, momentum'): what ``mi355x_sd_sega_guidance`` replaces
+        (``fused_guidance=False``; the cross-check and the measurement's other side). One ``torch.quantile`` per live concept."""
+        chunks = raw.chunk(2 + n)
+        u, t = chunks[0], chunks[1]
+        guidance = guidance_scale * (t - u)
+        dec = sega_forms.step_decisions(i, n, **per_concept)
+        g, weights = [], []
+        for (scale, q, weight, _), e in zip(dec, chunks[2:]):
+            if weight is None:   # cooled down (:611-613)
+                g.append(torch.zeros_like(u))
+                weights.append(0.0)
+                continue
+            d = (e - u) * float(scale)
+            thr = torch.quantile(d.abs().flatten(2), q, dim=2, keepdim=False)
+            g.append(torch.where(d.abs() >= thr[:, :, None, None], d, torch.zeros_like(d)))
+            weights.append(float(weight))
+        w = torch.tensor(weights, dtype=u.dtype, device=u.device)
+        w = torch.where(w < 0, torch.zeros_like(w), w)
+        warm = [c for c, d in enumerate(dec) if d[3]]
+        if 0 < len(warm) < n:   # (:654-677; no nan_to_num here)
+            wp = w[warm] / w[warm].sum()
+            part = torch.zeros_like(u)
+            for k, c in enumerate(warm):
+                part = part + wp[k] * g[c]
+            guidance = guidance + part
+        w = torch.nan_to_num(w)
+        edit = torch.zeros_like(u)
+        for c in range(n):
+            edit = edit + w[c] * g[c]
+        edit = edit + edit_momentum_scale * momentum
+        momentum = edit_mom_beta * momentum + (1 - edit_mom_beta) * edit
+        if len(warm) == n:
+            guidance = guidance + edit
+        if extra is not None:
+            guidance = guidance + extra
+        return u + guidance, momentum
+
+    def _semantic_guidance(self, prompt_embeds, negative_prompt_embeds, edit_embeds, num_inference_steps, guidance_scale, latents,
+                           generator, callback_on_step_end, vae_scale_factor, output_type, ids, height, width, fused_update, eta,
+                           fused_guidance, sem_guidance, per_concept, edit_momentum_scale, edit_mom_beta):
+        """The loop of SemanticStableDiffusionPipeline.__call__ (pipeline_semantic_stable_diffusion.py:529-707). Per step ONE U-Net call
+        on (2 + n) * B samples -- embeddings ``[negative | text | concept 0 | ... | concept n-1]``, B rows each -- then ONE
+        ``mi355x_sd_sega_guidance`` (the guidance, every concept's quantile mask, the warm-up regimes, the momentum and
+        ``sem_guidance[i]``), its per-step scalars row i of a device table built once (sega_forms.rows), then the scheduler's tail
+        with no guidance of its own. The momentum plane is allocated zeroed here and lives for the call.
+
+        ``edit_embeds``: [n, T, D], one embedding per concept used for every sample, or [n, B, T, D]. The batch is always
+        CONCEPT-MAJOR, the order the reference's string path builds (:426). Its ``editing_prompt_embeddings.tile([batch, 1, 1])``
+        (:445) interleaves the concepts for B > 1 and then chunks them as if concept-major; that is not reproduced. The reference's
+        per-step CPU copies (``uncond_estimates``, ``text_estimates``, ``edit_estimates``, ``sem_guidance[i]``) are not kept."""
+        from .export import ExportedProgram
+        if isinstance(self.unet, ExportedProgram):
+            raise NotImplementedError("an exported program as `unet` together with editing prompts (semantic guidance) is not "
+                                      "implemented: the exporter does not plan `mi355x_sd_sega_guidance`")
+        if guidance_scale <= 1.0:
+            raise NotImplementedError("editing prompts (semantic guidance) need `guidance_scale` > 1: without classifier-free "
+                                      "guidance the reference silently ignores them")
+        cfg, sch = self.unet.config, self.scheduler
+        if getattr(cfg, "time_cond_proj_dim", None) is not None:
+            raise NotImplementedError("a guidance-distilled U-Net (`time_cond_proj_dim`) together with editing prompts (semantic "
+                                      "guidance) is not implemented")
+        if getattr(cfg, "addition_embed_type", None) is not None or self.text_encoder_2 is not None:
+            raise NotImplementedError("a U-Net with added conditioning (`addition_embed_type`: SDXL) together with editing prompts "
+                                      "(semantic guidance) is not implemented: the reference has no such pipeline")
+        lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
+        if lib is None:
+            raise _lib.MI355XError("semantic guidance runs its kernel through the U-Net's library: the `unet` has none")
+        if not hasattr(lib, "mi355x_sd_sega_guidance"):
+            raise _lib.MI355XError("the U-Net's library has no `mi355x_sd_sega_guidance` (ABI 25)")
+        prompt_ids, negative_prompt_ids, edit_ids = ids
+        if prompt_embeds is None:
+            if prompt_ids is None:
+                raise ValueError("Provide either `prompt_embeds` or `prompt_ids`")
+            prompt_embeds = self.encode_prompt(prompt_ids)[0]
+        if negative_prompt_embeds is None:
+            if negative_prompt_ids is None:
+                raise ValueError("classifier-free guidance needs `negative_prompt_embeds` (or `negative_prompt_ids`)")
+            negative_prompt_embeds = self.encode_prompt(negative_prompt_ids)[0]
+        if edit_embeds is None:
+            edit_embeds = self.encode_prompt(edit_ids)[0]
+        B = prompt_embeds.shape[0]
+        if edit_embeds.dim() == 3:
+            edit_embeds = edit_embeds[:, None].expand(-1, B, -1, -1)
+        if edit_embeds.dim() != 4 or edit_embeds.shape[1] != B or edit_embeds.shape[2:] != prompt_embeds.shape[1:]:
+            raise ValueError(f"`editing_prompt_embeds`: expected [n, T, D] or [n, {B}, T, D] with the prompt's T and D, got "
+                             f"{tuple(edit_embeds.shape)}")
+        n = edit_embeds.shape[0]
+        embeds = torch.cat([negative_prompt_embeds, prompt_embeds, edit_embeds.reshape((n * B,) + tuple(prompt_embeds.shape[1:]))])
+        h = (height // vae_scale_factor) if height else cfg.sample_size
+        w = (width // vae_scale_factor) if width else cfg.sample_size
+        if latents is not None and height is None and width is None:
+            h, w = latents.shape[-2:]
+        sch.set_timesteps(num_inference_steps)
+        timesteps = sch.timesteps
+        latents = self.prepare_latents(B, cfg.in_channels, h, w, torch.float32, generator, latents, prompt_embeds.device)
+        dev, C = latents.device, latents.shape[1]
+        table = sega_forms.rows(len(timesteps), n, h * w, guidance_scale, edit_momentum_scale, edit_mom_beta, **per_concept)
+        extras = None
+        if sem_guidance is not None:
+            extras = (sem_guidance if torch.is_tensor(sem_guidance) else torch.stack(list(sem_guidance))).to(dev, torch.float32).contiguous()
+            if extras.shape[0] < len(timesteps) or tuple(extras.shape[1:]) != tuple(latents.shape):
+                raise ValueError(f"`sem_guidance`: expected at least {len(timesteps)} planes of shape {tuple(latents.shape)}, got "
+                                 f"{tuple(extras.shape)}")
+        step_params = inspect.signature(sch.step).parameters
+        extra = {}
+        if "eta" in step_params:
+            extra["eta"] = eta
+        if "generator" in step_params:
+            extra["generator"] = generator
+        tail = (self._fused_plan(False, dev, timesteps, generator) if fused_update and not eta else None) or _GenericTail(sch, extra)
+        momentum = torch.zeros_like(latents)
+        rows = torch.from_numpy(table.view(np.int32)).to(dev) if fused_guidance else None
+        stride = 4 * sega_forms.row_words(n)
+        for i, t in enumerate(timesteps):
+            lat = latents.contiguous()
+            model_input = tail.scale(torch.cat([lat] * (2 + n)), i, t)
+            raw = self.unet(model_input, t, encoder_hidden_states=embeds, return_dict=False)[0].contiguous()
+            ex = None if extras is None else extras[i]
+            if fused_guidance:
+                e = torch.empty_like(lat)
+                _lib.check(lib.mi355x_sd_sega_guidance(raw.data_ptr(), momentum.data_ptr(), None if ex is None else ex.data_ptr(),
+                                                       rows.data_ptr() + stride * i, e.data_ptr(), None, n, B, C, h * w,
+                                                       program.caller_stream(dev, emulated)))
+            else:
+                e, momentum = self.semantic_guidance_torch(i, raw, n, momentum, ex, guidance_scale, edit_momentum_scale, edit_mom_beta,
+                                                           per_concept)
+            latents = tail.update(lat, e.contiguous(), i, t, False, 1.0, 0.0)
+            if callback_on_step_end is not None:
+                out = callback_on_step_end(self, i, t, {"latents": latents})
+                latents = out.pop("latents", latents)
+        if output_type == "latent":
+            return latents
+        return self.decode_latents(latents, output_type)
+
     @torch.no_grad()
     def __call__(self, prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
@@ -596,7 +733,11 @@ class StableDiffusionDenoiser(_VaeSwitches):
                  mask_image: Optional[torch.Tensor] = None, masked_image_latents: Optional[torch.Tensor] = None,
                  control_image: Optional[torch.Tensor] = None, controlnet_conditioning_scale: float = 1.0,
                  guess_mode: bool = False, adapter_image=None, adapter_conditioning_scale=1.0,
-                 adapter_conditioning_factor: float = 1.0, image_guidance_scale: Optional[float] = None):
+                 adapter_conditioning_factor: float = 1.0, image_guidance_scale: Optional[float] = None,
+                 editing_prompt_embeds: Optional[torch.Tensor] = None, editing_prompt_ids: Optional[torch.Tensor] = None,
+                 reverse_editing_direction=False, edit_guidance_scale=5, edit_warmup_steps=10, edit_cooldown_steps=None,
+                 edit_threshold=0.9, edit_momentum_scale: float = 0.1, edit_mom_beta: float = 0.4, edit_weights=None,
+                 sem_guidance=None, fused_guidance: bool = True):
         """``image`` (extension of the text2img call = StableDiffusionImg2ImgPipeline.__call__,
         pipeline_stable_diffusion_img2img.py:735-1010): start from the encoded, re-noised image and run the last
         ``int(num_inference_steps * strength)`` steps (strength defaults to 0.8).
@@ -615,7 +756,25 @@ class StableDiffusionDenoiser(_VaeSwitches):
         to the image's, floored to a multiple of ``adapter.downscale_factor``.
 
         ``image`` + ``image_guidance_scale`` (= StableDiffusionInstructPix2PixPipeline / StableDiffusionXLInstructPix2PixPipeline
-        .__call__): instruction-based editing on an 8-channel U-Net, see ``_instruct_pix2pix``. ``strength`` is not used."""
+        .__call__): instruction-based editing on an 8-channel U-Net, see ``_instruct_pix2pix``. ``strength`` is not used.
+
+        ``editing_prompt_embeds`` / ``editing_prompt_ids`` (= SemanticStableDiffusionPipeline.__call__,
+        pipelines/semantic_stable_diffusion/pipeline_semantic_stable_diffusion.py:225-727): semantic guidance, see
+        ``_semantic_guidance``; the ``edit_*`` arguments and ``sem_guidance`` are the reference's, with its defaults and its
+        scalar-or-list rules. ``fused_guidance=False`` takes the same step with torch ops."""
+        if editing_prompt_embeds is not None or editing_prompt_ids is not None:
+            for name, v in (("guidance_rescale", guidance_rescale or None), ("image_guidance_scale", image_guidance_scale),
+                            ("image", image), ("mask_image", mask_image), ("control_image", control_image),
+                            ("adapter_image", adapter_image), ("added_cond_kwargs", added_cond_kwargs)):
+                if v is not None:
+                    raise NotImplementedError(f"`{name}` together with editing prompts (semantic guidance) is not implemented")
+            return self._semantic_guidance(
+                prompt_embeds, negative_prompt_embeds, editing_prompt_embeds, num_inference_steps, guidance_scale, latents, generator,
+                callback_on_step_end, vae_scale_factor, output_type, (prompt_ids, negative_prompt_ids, editing_prompt_ids), height,
+                width, fused_update, eta, fused_guidance, sem_guidance,
+                dict(reverse_editing_direction=reverse_editing_direction, edit_guidance_scale=edit_guidance_scale,
+                     edit_warmup_steps=edit_warmup_steps, edit_cooldown_steps=edit_cooldown_steps, edit_threshold=edit_threshold,
+                     edit_weights=edit_weights), edit_momentum_scale, edit_mom_beta)
         if image_guidance_scale is not None:
             for name, v in (("mask_image", mask_image), ("control_image", control_image), ("adapter_image", adapter_image)):
                 if v is not None:
