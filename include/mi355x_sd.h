@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MI355X_SD_ABI_VERSION 25
+#define MI355X_SD_ABI_VERSION 26
 #define MI355X_SD_OK 0
 #define MI355X_SD_ERR_INVALID 1      /* bad argument (shape <= 0, null pointer ...)          */
 #define MI355X_SD_ERR_UNSUPPORTED 2  /* well-formed but outside the implemented configurations */
@@ -806,6 +806,37 @@ int mi355x_sd_ip2p_input(const float* x, const float* image_latents, float* out,
  * 256 x 256 latent), batch * channels > 2^31 - 1. */
 int mi355x_sd_sega_guidance(const float* eps, float* momentum, const float* extra, const float* row, float* out, float* stats,
                             int n_concepts, int batch, int channels, int64_t hw, void* stream);
+
+/* ---- Panorama (MultiDiffusion: StableDiffusionPanoramaPipeline, pipeline_stable_diffusion_panorama.py; ABI 26) ----
+ * The two passes around the U-Net and the step tails of a panorama step, one launch each. View geometry (the reference's get_views,
+ * :473-491, window and stride as arguments): ny x nx views; view v = iy * nx + ix starts at row iy * stride, column ix * stride of the
+ * [batch, C, H, W] source and has win_h x win_w elements. Without `circular` every window lies inside the source; with it column j of
+ * a view is source column (ix * stride + j) mod W, and rows never wrap.
+ *
+ * mi355x_sd_view_input: the U-Net input of the views [first, first + count) (:675-709: the slices, the circular concat, the concat
+ * over the view batch, the doubling under guidance, scale_model_input). out is [groups][count * batch] NCHW samples of
+ * C x win_h x win_w; sample (v - first) * batch + b of EVERY group is scale * x[b] over view v's window: one fp32 multiply per
+ * element, the bits of torch's x * scale. groups is 2 under guidance and 1 without it; group-major is this library's
+ * [uncond | text] order (what the step tails take as eps and eps + n), not the reference's repeat_interleave. count == 0 launches
+ * nothing. 16-byte vectors when W, win_w and stride are multiples of 4 and x and out are 16-byte aligned (a vector then never
+ * straddles the wrap); element by element otherwise.
+ *
+ * mi355x_sd_view_merge: the MultiDiffusion average (:736-754) of all ny * nx views; views is [ny * nx * batch] samples, view v of
+ * image b at v * batch + b. Every element of out [batch, C, H, W] is written exactly once, in GATHER form: the views that cover it are
+ * visited in ascending v, their values added one by one in fp32 to a sum that starts at +0.0f, the sum divided by their number with
+ * a correctly rounded fp32 division -- the reference's value / count / where(count > 0, value / count, value) bit for bit: no
+ * atomics, no reciprocal, no reassociation. An element no view covers (without `circular`, the columns past the last window when
+ * (W - win_w) % stride != 0) gets the sum itself, +0.0f. The same vector rule, with views in place of x.
+ *
+ * MI355X_SD_ERR_INVALID before any launch, the message naming the argument: a null pointer; groups not 1 or 2; batch, C, H, W, win_h,
+ * win_w, stride, ny or nx < 1; win_h > H or win_w > W; (ny - 1) * stride + win_h > H; without `circular` (nx - 1) * stride + win_w > W,
+ * with it (nx - 1) * stride >= W; first or count outside [0, ny * nx] or first + count > ny * nx; a size in bytes past int64_t; out
+ * overlapping x / views. MI355X_SD_ERR_UNSUPPORTED: count * batch * C (view_input) or batch * C (view_merge) > 65535, or more than
+ * 4 * 65535 rows in a window (view_input) or in the source (view_merge). */
+int mi355x_sd_view_input(const float* x, float* out, float scale, int groups, int batch, int C, int H, int W, int win_h, int win_w,
+                         int stride, int ny, int nx, int circular, int first, int count, void* stream);
+int mi355x_sd_view_merge(const float* views, float* out, int batch, int C, int H, int W, int win_h, int win_w, int stride, int ny,
+                         int nx, int circular, void* stream);
 
 /* hipGraph capture of a sequence of the calls above issued on `stream` (one denoising step). */
 int mi355x_sd_graph_begin(void* stream);

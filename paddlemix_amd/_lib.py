@@ -5,7 +5,7 @@ import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p, POINTER
 
-from . import ip2p_forms, sega_forms, step_forms
+from . import ip2p_forms, panorama_forms, sega_forms, step_forms
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -26,7 +26,7 @@ if os.environ.get("MI355X_SD_LIB") == "dbg":
         raise ValueError("MI355X_SD_LIB=dbg: the debug-switch build exists for bf16 elements only")
     LIB_PATH = os.path.join(_HERE, "libmi355x_sd_dbg.so")
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 GEGLU, OUT_F32, SILU, GELU_TANH, PAD_BR, R_F32, CONV_KB64 = 1, 2, 4, 8, 16, 32, 64
 UNET_ENC_MASK, UNET_SELF_MASK, UNET_CONTROLNET = 1, 2, 4   # mi355x_sd_unet_plan_ex flags
 SDPA_LOG2 = 1
@@ -187,6 +187,8 @@ SIGNATURES.update(("mi355x_sd_" + form.entry, step_forms.signature(form)) for fo
 SIGNATURES.update(("mi355x_sd_" + e.entry, ip2p_forms.signature(e)) for e in ip2p_forms.ENTRIES.values())
 # (semantic guidance, csrc/sega.hip, ABI 25: the same row type, from sega_forms.ENTRIES)
 SIGNATURES.update(("mi355x_sd_" + e.entry, ip2p_forms.signature(e)) for e in sega_forms.ENTRIES.values())
+# (panorama / MultiDiffusion, csrc/panorama.hip, ABI 26: from panorama_forms.ENTRIES)
+SIGNATURES.update(("mi355x_sd_" + e.entry, ip2p_forms.signature(e)) for e in panorama_forms.ENTRIES.values())
 
 _lib = None
 

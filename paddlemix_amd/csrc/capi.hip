@@ -211,6 +211,37 @@ static int span_entry(const char* who, std::initializer_list<Span> spans, const 
   return finish(launch(), who);
 }
 
+// The view geometry both panorama entries (panorama.hip) share, as span_entry's range rule: the first rule the call breaks, with the
+// argument's name in it ("%s" stands for the entry), or NULL. paddlemix_amd/panorama_forms.py geometry_rule states the same rules in
+// the same order for the Python side. On success *window = batch * C * win_h * win_w, the floats of one view of the whole batch, and
+// 4 * ny * nx * *window as well as 4 * batch * C * H * W fit int64_t.
+static const char* view_rule(int batch, int C, int H, int W, int win_h, int win_w, int stride, int ny, int nx, int circular,
+                             int64_t* window) {
+  static thread_local char rule[160];
+  const struct {
+    const char* name;
+    int v;
+  } dims[] = {{"batch", batch}, {"C", C}, {"H", H}, {"W", W}, {"win_h", win_h}, {"win_w", win_w}, {"stride", stride}, {"ny", ny}, {"nx", nx}};
+  for (const auto& d : dims)
+    if (d.v < 1) {
+      snprintf(rule, sizeof(rule), "%%s: %s must be >= 1", d.name);
+      return rule;
+    }
+  if (win_h > H) return "%s: win_h is larger than H";
+  if (win_w > W) return "%s: win_w is larger than W";
+  if (((int64_t)ny - 1) * stride + win_h > H) return "%s: ny: the last row of views leaves the source ((ny - 1) * stride + win_h > H)";
+  if (!circular && ((int64_t)nx - 1) * stride + win_w > W)
+    return "%s: nx: the last column of views leaves the source ((nx - 1) * stride + win_w > W) without circular";
+  if (circular && ((int64_t)nx - 1) * stride >= W) return "%s: nx: a circular view starts past the source ((nx - 1) * stride >= W)";
+  int64_t src = 4, win = 4;
+  for (int v : {batch, C, H, W})
+    if (__builtin_mul_overflow(src, (int64_t)v, &src)) return "%s: H, W: the source's size in bytes is past int64_t";
+  for (int v : {batch, C, win_h, win_w, ny, nx})
+    if (__builtin_mul_overflow(win, (int64_t)v, &win)) return "%s: ny, nx: the views' size in bytes is past int64_t";
+  *window = (int64_t)batch * C * win_h * win_w;
+  return nullptr;
+}
+
 extern "C" {
 
 int mi355x_sd_abi_version(void) { return MI355X_SD_ABI_VERSION; }
@@ -810,6 +841,35 @@ int mi355x_sd_sega_guidance(const float* eps, float* momentum, const float* extr
                      {"stats", stats, 3 * n_concepts * planes, true, true, stats != nullptr}},
                     "%s: needs n_concepts, batch, channels and hw >= 1", ok, [&] {
                       return launch_sega_guidance(eps, momentum, extra, row, out, stats, n_concepts, batch, channels, (long)hw, S(stream));
+                    });
+}
+
+// ---- panorama / MultiDiffusion (panorama.hip): the same span rule, the range rule from view_rule() above; paddlemix_amd/
+// panorama_forms.py holds the rows for the Python side ----
+int mi355x_sd_view_input(const float* x, float* out, float scale, int groups, int batch, int C, int H, int W, int win_h, int win_w,
+                         int stride, int ny, int nx, int circular, int first, int count, void* stream) {
+  int64_t window = 0;
+  const char* bad = (groups != 1 && groups != 2) ? "%s: groups must be 1 or 2"
+                                                 : view_rule(batch, C, H, W, win_h, win_w, stride, ny, nx, circular, &window);
+  if (!bad && (first < 0 || count < 0 || (int64_t)first + count > (int64_t)ny * nx))
+    bad = "%s: first, count: [first, first + count) is not a range of the ny * nx views";
+  if (!bad && count > 0 && count > INT64_MAX / 4 / groups / window) bad = "%s: count: out's size in bytes is past int64_t";
+  return span_entry("mi355x_sd_view_input", {{"x", x, bad ? 0 : (int64_t)batch * C * H * W, false, false, true},
+                                             {"out", out, bad ? 0 : groups * count * window, true, false, true}},
+                    bad ? bad : "", !bad, [&] {
+                      return launch_view_input(x, out, scale, groups, batch, C, H, W, win_h, win_w, stride, ny, nx, circular, first,
+                                               count, S(stream));
+                    });
+}
+
+int mi355x_sd_view_merge(const float* views, float* out, int batch, int C, int H, int W, int win_h, int win_w, int stride, int ny,
+                         int nx, int circular, void* stream) {
+  int64_t window = 0;
+  const char* bad = view_rule(batch, C, H, W, win_h, win_w, stride, ny, nx, circular, &window);
+  return span_entry("mi355x_sd_view_merge", {{"views", views, bad ? 0 : (int64_t)ny * nx * window, false, false, true},
+                                             {"out", out, bad ? 0 : (int64_t)batch * C * H * W, true, false, true}},
+                    bad ? bad : "", !bad, [&] {
+                      return launch_view_merge(views, out, batch, C, H, W, win_h, win_w, stride, ny, nx, circular, S(stream));
                     });
 }
 

@@ -200,6 +200,12 @@ int launch_ip2p_input(const float* x, const float* img, float* out, float scale,
 // output and the momentum update in one elementwise pass; every per-step scalar from `row` in device memory
 int launch_sega_guidance(const float* eps, float* momentum, const float* extra, const float* row, float* out, float* stats, int n,
                          int batch, int channels, long hw, hipStream_t stream);
+// Panorama / MultiDiffusion (panorama.hip): the scaled windows of the views [first, first + count) for `groups` guidance groups, and
+// the per-element average of all ny * nx denoised views in gather form (ascending view order onto +0.0f, one IEEE division)
+int launch_view_input(const float* x, float* out, float scale, int groups, int batch, int C, int H, int W, int wh, int ww, int stride,
+                      int ny, int nx, int circular, int first, int count, hipStream_t stream);
+int launch_view_merge(const float* views, float* out, int batch, int C, int H, int W, int wh, int ww, int stride, int ny, int nx,
+                      int circular, hipStream_t stream);
 int launch_axpby(const float* x, const float* y, float* out, const float* coef, long n, hipStream_t stream);
 int launch_mask_to_bias(const float* mask, float* bias, long n, hipStream_t stream);
 

@@ -75,7 +75,8 @@ const std::vector<Entry>& op_table() {
       SD_OP(mi355x_sd_relu), SD_OP(mi355x_sd_tile_gather), SD_OP(mi355x_sd_tile_blend), SD_OP(mi355x_sd_cfg_rescale_axpby),
       SD_OP(mi355x_sd_multistep_update), SD_OP(mi355x_sd_unipc_update), SD_OP(mi355x_sd_ancestral_update), SD_OP(mi355x_sd_heun_update),
       SD_OP(mi355x_sd_dpm2_update), SD_OP(mi355x_sd_plms_update), SD_OP(mi355x_sd_singlestep_update), SD_OP(mi355x_sd_guidance3),
-      SD_OP(mi355x_sd_ip2p_input), SD_OP(mi355x_sd_sega_guidance)};
+      SD_OP(mi355x_sd_ip2p_input), SD_OP(mi355x_sd_sega_guidance), SD_OP(mi355x_sd_view_input),
+      SD_OP(mi355x_sd_view_merge)};
   return t;
 }
 

@@ -536,6 +536,63 @@ def sega_guidance(eps: Tensor, momentum: Tensor, row: Tensor, n_concepts: int, e
     return out
 
 
+def _view_geometry(shape, window, stride, counts, circular):
+    """(batch, C, H, W, win_h, win_w, stride, ny, nx, circular) in the order of the two panorama entries, checked against
+    panorama_forms.geometry_rule (csrc/capi.hip refuses the same, by the same names)"""
+    from . import panorama_forms
+    B, C, H, W = shape
+    a = dict(batch=B, C=C, H=H, W=W, win_h=int(window[0]), win_w=int(window[1]), stride=int(stride), ny=int(counts[0]), nx=int(counts[1]),
+             circular=int(bool(circular)))
+    bad = panorama_forms.geometry_rule(a)
+    if bad:
+        raise ValueError(f"view geometry: `{bad}` is out of range for a source {tuple(shape)}, window {tuple(window)}, stride {stride}, "
+                         f"{tuple(counts)} views, circular={bool(circular)}")
+    return tuple(a.values())
+
+
+def view_input(x: Tensor, window, stride: int, counts, scale: float = 1.0, groups: int = 1, circular: bool = False, first: int = 0,
+               count: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The U-Net input of the panorama views [first, first + count) in one launch -> [groups * count * B, C, win_h, win_w]: sample
+    (v - first) * B + b of every group is scale * x[b] over view v's window. x: contiguous fp32 [B, C, H, W]; window = (win_h, win_w),
+    counts = (ny, nx); view v = iy * nx + ix starts at (iy * stride, ix * stride), its columns taken mod W under ``circular``."""
+    lib = _lib.load()
+    _flat_f32(x, "x")
+    if x.dim() != 4 or x.numel() < 1:
+        raise ValueError(f"x: expected a non-empty [B, C, H, W], got {tuple(x.shape)}")
+    geo = _view_geometry(x.shape, window, stride, counts, circular)
+    total = geo[7] * geo[8]
+    count = total - first if count is None else count
+    if groups not in (1, 2) or first < 0 or count < 0 or first + count > total:
+        raise ValueError(f"expected groups 1 or 2 and [first, first + count) within the {total} views, got {groups}, {first}, {count}")
+    shape = (groups * count * geo[0], geo[1], geo[4], geo[5])
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _flat_f32(out, "out", shape[0] * shape[1] * shape[2] * shape[3])
+    check(lib.mi355x_sd_view_input(x.data_ptr(), out.data_ptr(), float(scale), groups, *geo, first, count, _stream()))
+    return out
+
+
+def view_merge(views: Tensor, shape, stride: int, counts, circular: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """The MultiDiffusion average in one launch -> out [B, C, H, W] = ``shape``: every element is the fp32 sum, in ascending view
+    order from +0.0, of the views that cover it, divided by their number (an uncovered element: +0.0). views: contiguous fp32
+    [ny * nx * B, C, win_h, win_w], view v of image b at v * B + b."""
+    lib = _lib.load()
+    _flat_f32(views, "views")
+    if views.dim() != 4 or len(shape) != 4 or views.numel() < 1:
+        raise ValueError(f"expected views [ny * nx * B, C, win_h, win_w] and a shape (B, C, H, W), got {tuple(views.shape)}, {tuple(shape)}")
+    geo = _view_geometry(tuple(int(v) for v in shape), views.shape[2:], stride, counts, circular)
+    if views.shape[0] != geo[7] * geo[8] * geo[0] or views.shape[1] != geo[1]:
+        raise ValueError(f"views: expected [{geo[7] * geo[8]} * {geo[0]}, {geo[1]}, win_h, win_w], got {tuple(views.shape)}")
+    n = geo[0] * geo[1] * geo[2] * geo[3]
+    if out is None:
+        out = torch.empty(tuple(int(v) for v in shape), device=views.device, dtype=torch.float32)
+    else:
+        _flat_f32(out, "out", n)
+    check(lib.mi355x_sd_view_merge(views.data_ptr(), out.data_ptr(), *geo, _stream()))
+    return out
+
+
 def probe_layouts(device="cuda") -> Tensor:
     lib = _lib.load()
     out = torch.zeros((64, 24), device=device, dtype=torch.float32)

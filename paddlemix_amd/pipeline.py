@@ -19,7 +19,7 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, program, sega_forms
+from . import _lib, panorama_forms, program, sega_forms
 from .step_forms import FORMS
 
 
@@ -337,10 +337,23 @@ class StableDiffusionDenoiser(_VaeSwitches):
             out.append(torch.cat([v] * 2) if do_cfg else v)
         return out
 
-    def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
-        """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1)."""
+    def decode_latents(self, latents: torch.Tensor, output_type: str = "pt", circular_padding: bool = False):
+        """pipeline_stable_diffusion.py:911 + VaeImageProcessor.postprocess: decode, (x / 2 + 0.5).clamp(0, 1).
+        ``circular_padding``: ``decode_latents_with_padding`` (pipeline_stable_diffusion_panorama.py:371-382): the last
+        panorama_forms.CIRCULAR_PAD latent columns are put in front and the first ones behind, the padded latents go through the same
+        decode (tiling included), and the pixels of the padding are cropped from both sides."""
+        if circular_padding:
+            pad, width = panorama_forms.CIRCULAR_PAD, latents.shape[-1]
+            latents = torch.cat((latents[..., -pad:], latents, latents[..., :pad]), dim=-1)
 
         def decode():
+            image = decode_padded()
+            if circular_padding:
+                px = pad * (image.shape[-1] // (width + 2 * pad))
+                image = image[..., px:-px]
+            return image
+
+        def decode_padded():
             vc = self.vae.config
             mean, std = getattr(vc, "latents_mean", None), getattr(vc, "latents_std", None)
             if mean is None or std is None:
@@ -718,6 +731,173 @@ class StableDiffusionDenoiser(_VaeSwitches):
             return latents
         return self.decode_latents(latents, output_type)
 
+    @staticmethod
+    def view_input_torch(x, views, circular):
+        """The latents of `views` (rows of panorama_forms.views) stacked view-major, in the reference's expressions
+        (pipeline_stable_diffusion_panorama.py:675-698): what ``mi355x_sd_view_input`` replaces at scale 1 and one group"""
+        W, out = x.shape[3], []
+        for h0, h1, w0, w1 in views:
+            if circular and w1 > W:
+                out.append(torch.cat((x[:, :, h0:h1, w0:], x[:, :, h0:h1, :w1 - W]), dim=-1))
+            else:
+                out.append(x[:, :, h0:h1, w0:w1])
+        return torch.cat(out)
+
+    @staticmethod
+    def view_merge_torch(denoised, views, shape, circular):
+        """``value`` / ``count`` / ``where`` of the reference (:736-754) on the device of `denoised` [len(views) * B, C, win_h, win_w]:
+        what ``mi355x_sd_view_merge`` replaces"""
+        value = torch.zeros(shape, dtype=denoised.dtype, device=denoised.device)
+        count = torch.zeros_like(value)
+        W = shape[3]
+        for d, (h0, h1, w0, w1) in zip(denoised.chunk(len(views)), views):
+            if circular and w1 > W:
+                value[:, :, h0:h1, w0:] += d[:, :, :, :W - w0]
+                value[:, :, h0:h1, :w1 - W] += d[:, :, :, W - w0:]
+                count[:, :, h0:h1, w0:] += 1
+                count[:, :, h0:h1, :w1 - W] += 1
+            else:
+                value[:, :, h0:h1, w0:w1] += d
+                count[:, :, h0:h1, w0:w1] += 1
+        return torch.where(count > 0, value / count, value)
+
+    def _panorama(self, prompt_embeds, negative_prompt_embeds, num_inference_steps, guidance_scale, latents, generator,
+                  callback_on_step_end, vae_scale_factor, output_type, ids, height, width, fused_update, eta, view_batch_size,
+                  circular_padding, fused_views):
+        """The loop of StableDiffusionPanoramaPipeline.__call__ (pipeline_stable_diffusion_panorama.py:589-783; MultiDiffusion). Every
+        step cuts the latents into overlapping windows of panorama_forms.WINDOW at panorama_forms.STRIDE (``get_views``, :473-491),
+        denoises every view with scheduler state of its own and averages the results per element. Per step and chunk of
+        ``view_batch_size`` views (default: all of them): ONE ``mi355x_sd_view_input`` (a second one, unscaled, for the tail's sample
+        where the scheduler scales its model input), ONE U-Net call on ``[negative x views | text x views]``, the scheduler's fused
+        tail over the chunk's stacked views -- every tail is elementwise with its history in planes it owns, one tail object per
+        chunk, so that is the reference's per-view-batch ``views_scheduler_status`` with no copy of any scheduler -- then ONE
+        ``mi355x_sd_view_merge`` for the step. ``fused_update=False`` keeps ``scheduler.step`` with one copied scheduler state per
+        chunk, as the reference does; ``fused_views=False`` takes the same step with the reference's torch expressions for the two
+        passes. A latent smaller than the window on an axis clips the window to it.
+
+        Departures from the reference. (1) Above batch 1 it interleaves the latents (``repeat_interleave(2)``) but tiles the
+        embeddings ``[neg_0 .. neg_B-1, text_0 .. text_B-1]``: image 0 meets a negative prompt in both guidance halves, image 1 a
+        text prompt in both, which is no guidance at all, even for one prompt repeated over the batch. Here every image goes with
+        its own two prompts, in this library's group-major ``[uncond | text]`` order. The two agree at batch 1 and, at any batch,
+        without guidance. (2) ``view_batch_size`` only chunks the U-Net calls: for the schedulers accepted here the
+        reference's result does not depend on it either. Schedulers that draw noise are refused: the reference draws one tensor per
+        view batch, so its result depends on ``view_batch_size`` and nothing pins a stacked draw."""
+        import copy
+        from .export import ExportedProgram
+        if isinstance(self.unet, ExportedProgram):
+            raise NotImplementedError("an exported program as `unet` together with `panorama` is not implemented: the exporter does "
+                                      "not plan `mi355x_sd_view_input` / `mi355x_sd_view_merge`")
+        cfg, sch = self.unet.config, self.scheduler
+        if getattr(cfg, "time_cond_proj_dim", None) is not None:
+            raise NotImplementedError("a guidance-distilled U-Net (`time_cond_proj_dim`) together with `panorama` is not implemented")
+        if getattr(cfg, "addition_embed_type", None) is not None or self.text_encoder_2 is not None:
+            raise NotImplementedError("a U-Net with added conditioning (`addition_embed_type`: SDXL) together with `panorama` is not "
+                                      "implemented: the reference has no such pipeline")
+        step_params = inspect.signature(sch.step).parameters
+        if hasattr(sch, "ancestral_coefficients") or (hasattr(sch, "dpm2_coefficients") and "generator" in step_params) or \
+                str(getattr(sch.config, "algorithm_type", "")).startswith("sde") or type(sch).__name__ == "LCMScheduler" or \
+                (eta and "eta" in step_params):
+            raise NotImplementedError(f"a scheduler that draws noise in its step ({type(sch).__name__}"
+                                      f"{', eta > 0' if eta and 'eta' in step_params else ''}) together with `panorama` is not "
+                                      "implemented: the reference draws one noise tensor per view batch, so its result depends on "
+                                      "`view_batch_size`")
+        lib, emulated = getattr(self.unet, "_lib", None), getattr(self.unet, "_emulated", False)
+        if lib is None:
+            raise _lib.MI355XError("`panorama` runs its view kernels through the U-Net's library: the `unet` has none")
+        if fused_views and not (hasattr(lib, "mi355x_sd_view_input") and hasattr(lib, "mi355x_sd_view_merge")):
+            raise _lib.MI355XError("the U-Net's library has no `mi355x_sd_view_input` / `mi355x_sd_view_merge` (ABI 26)")
+        do_cfg = guidance_scale > 1.0
+        prompt_ids, negative_prompt_ids = ids
+        if prompt_embeds is None:
+            if prompt_ids is None:
+                raise ValueError("Provide either `prompt_embeds` or `prompt_ids`")
+            prompt_embeds = self.encode_prompt(prompt_ids)[0]
+        if do_cfg and negative_prompt_embeds is None:
+            if negative_prompt_ids is None:
+                raise ValueError("classifier-free guidance needs `negative_prompt_embeds` (or `negative_prompt_ids`)")
+            negative_prompt_embeds = self.encode_prompt(negative_prompt_ids)[0]
+        B = prompt_embeds.shape[0]
+        h = (height // vae_scale_factor) if height else cfg.sample_size
+        w = (width // vae_scale_factor) if width else cfg.sample_size
+        if latents is not None and height is None and width is None:
+            h, w = latents.shape[-2:]
+        window, stride = panorama_forms.WINDOW, panorama_forms.STRIDE
+        ny, nx, wh, ww = panorama_forms.grid(h, w, window, stride, circular_padding)
+        if circular_padding and ny > 1:
+            raise NotImplementedError("`circular_padding` with more than one row of views is not implemented: the reference itself "
+                                      "fails there (it slices the view's own rows by the view's place in the panorama)")
+        if circular_padding and w < window:
+            raise NotImplementedError("`circular_padding` with latents narrower than the window is not implemented")
+        views = panorama_forms.views(h, w, window, stride, circular_padding)
+        total = len(views)
+        per = total if view_batch_size is None else int(view_batch_size)
+        if per < 1:
+            raise ValueError(f"`view_batch_size` has to be a positive integer or None (all views), got {view_batch_size}")
+        chunks = [(f, min(per, total - f)) for f in range(0, total, per)]
+        sch.set_timesteps(num_inference_steps)
+        timesteps = sch.timesteps
+        latents = self.prepare_latents(B, cfg.in_channels, h, w, torch.float32, generator, latents, prompt_embeds.device)
+        dev, C = latents.device, latents.shape[1]
+        groups = 2 if do_cfg else 1
+        embeds = {}
+        for c in {c for _, c in chunks}:   # sample (v - first) * B + b of a group goes with prompt b
+            text = prompt_embeds.repeat(c, 1, 1)
+            embeds[c] = torch.cat([negative_prompt_embeds.repeat(c, 1, 1), text]) if do_cfg else text
+        extra = {}
+        if "eta" in step_params:
+            extra["eta"] = eta
+        if "generator" in step_params:
+            extra["generator"] = generator
+        tail = (self._fused_plan(False, dev, timesteps, generator) if fused_update and not eta else None) or _GenericTail(sch, extra)
+        fused = isinstance(tail, _FusedTail)
+        tails = [copy.copy(tail) for _ in chunks]                   # (a fused tail builds the state it owns on its first launch)
+        status = None if fused else [copy.deepcopy(sch.__dict__) for _ in chunks]   # (:651)
+        geo = (B, C, h, w, wh, ww, stride, ny, nx, int(bool(circular_padding)))
+        stack = torch.empty((total * B, C, wh, ww), dtype=torch.float32, device=dev)      # the views of the latents, unscaled
+        denoised = torch.empty_like(stack)
+        model_in = {c: torch.empty((groups * c * B, C, wh, ww), dtype=torch.float32, device=dev) for c in embeds} if fused_views else None
+        gs = float(guidance_scale)
+        for i, t in enumerate(timesteps):
+            stream = program.caller_stream(dev, emulated)
+            lat = latents.contiguous()
+            for j, (f, c) in enumerate(chunks):
+                tl, n = tails[j], c * B
+                if fused:
+                    src, scale = lat, (1.0 if tl.scales is None else float(tl.scales[i]))
+                else:   # the scheduler's own ``scale_model_input`` on the whole latents (elementwise: the windows' bits), in this chunk's state
+                    sch.__dict__.update(status[j])
+                    src, scale = tl.scale(lat, i, t).contiguous(), 1.0
+                xs = stack[f * B:f * B + n]
+                if fused_views:
+                    x_in = model_in[c]
+                    _lib.check(lib.mi355x_sd_view_input(src.data_ptr(), x_in.data_ptr(), scale, groups, *geo, f, c, stream))
+                    if src is lat and scale == 1.0:
+                        xs = x_in[:n]                               # (x * 1.0f is x: the first group is the tail's sample)
+                    else:
+                        _lib.check(lib.mi355x_sd_view_input(lat.data_ptr(), xs.data_ptr(), 1.0, 1, *geo, f, c, stream))
+                else:
+                    xs = self.view_input_torch(lat, views[f:f + c], circular_padding)
+                    scaled = xs * scale if src is lat else self.view_input_torch(src, views[f:f + c], circular_padding)
+                    x_in = torch.cat([scaled] * groups)
+                e = self.unet(x_in, t, encoder_hidden_states=embeds[c], return_dict=False)[0].contiguous()
+                if fused:
+                    _lib.check(tl.launch(xs, e.data_ptr(), e.data_ptr() + 4 * xs.numel() if do_cfg else None, denoised[f * B:f * B + n],
+                                         i, gs, 0.0, stream))
+                else:
+                    denoised[f * B:f * B + n] = tl.update(xs, e, i, t, do_cfg, guidance_scale, 0.0)
+                    status[j] = copy.deepcopy(sch.__dict__)         # (:733)
+            if fused_views:
+                latents = torch.empty_like(lat)
+                _lib.check(lib.mi355x_sd_view_merge(denoised.data_ptr(), latents.data_ptr(), *geo, stream))
+            else:
+                latents = self.view_merge_torch(denoised, views, lat.shape, circular_padding)
+            if callback_on_step_end is not None:
+                out = callback_on_step_end(self, i, t, {"latents": latents})
+                latents = out.pop("latents", latents)
+        if output_type == "latent":
+            return latents
+        return self.decode_latents(latents, output_type, circular_padding=bool(circular_padding))
+
     @torch.no_grad()
     def __call__(self, prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 50,
@@ -737,7 +917,8 @@ class StableDiffusionDenoiser(_VaeSwitches):
                  editing_prompt_embeds: Optional[torch.Tensor] = None, editing_prompt_ids: Optional[torch.Tensor] = None,
                  reverse_editing_direction=False, edit_guidance_scale=5, edit_warmup_steps=10, edit_cooldown_steps=None,
                  edit_threshold=0.9, edit_momentum_scale: float = 0.1, edit_mom_beta: float = 0.4, edit_weights=None,
-                 sem_guidance=None, fused_guidance: bool = True):
+                 sem_guidance=None, fused_guidance: bool = True, panorama: bool = False, view_batch_size: Optional[int] = None,
+                 circular_padding: bool = False, fused_views: bool = True):
         """``image`` (extension of the text2img call = StableDiffusionImg2ImgPipeline.__call__,
         pipeline_stable_diffusion_img2img.py:735-1010): start from the encoded, re-noised image and run the last
         ``int(num_inference_steps * strength)`` steps (strength defaults to 0.8).
@@ -761,7 +942,22 @@ class StableDiffusionDenoiser(_VaeSwitches):
         ``editing_prompt_embeds`` / ``editing_prompt_ids`` (= SemanticStableDiffusionPipeline.__call__,
         pipelines/semantic_stable_diffusion/pipeline_semantic_stable_diffusion.py:225-727): semantic guidance, see
         ``_semantic_guidance``; the ``edit_*`` arguments and ``sem_guidance`` are the reference's, with its defaults and its
-        scalar-or-list rules. ``fused_guidance=False`` takes the same step with torch ops."""
+        scalar-or-list rules. ``fused_guidance=False`` takes the same step with torch ops.
+
+        ``panorama=True`` (= StableDiffusionPanoramaPipeline.__call__, pipeline_stable_diffusion_panorama.py:495-783): MultiDiffusion
+        over overlapping 64 x 64 latent windows at stride 8, see ``_panorama``. ``view_batch_size``: the views per U-Net call (None:
+        all of them; the reference's default is 1); ``circular_padding``: the windows wrap around the right edge, and a non-latent
+        output is decoded with wrapped padding; ``fused_views=False`` takes the same step with torch ops for the two view passes."""
+        if panorama:
+            for name, v in (("guidance_rescale", guidance_rescale or None), ("image_guidance_scale", image_guidance_scale),
+                            ("image", image), ("mask_image", mask_image), ("control_image", control_image),
+                            ("adapter_image", adapter_image), ("added_cond_kwargs", added_cond_kwargs),
+                            ("editing_prompt_embeds", editing_prompt_embeds), ("editing_prompt_ids", editing_prompt_ids)):
+                if v is not None:
+                    raise NotImplementedError(f"`{name}` together with `panorama` is not implemented")
+            return self._panorama(prompt_embeds, negative_prompt_embeds, num_inference_steps, guidance_scale, latents, generator,
+                                  callback_on_step_end, vae_scale_factor, output_type, (prompt_ids, negative_prompt_ids), height, width,
+                                  fused_update, eta, view_batch_size, circular_padding, fused_views)
         if editing_prompt_embeds is not None or editing_prompt_ids is not None:
             for name, v in (("guidance_rescale", guidance_rescale or None), ("image_guidance_scale", image_guidance_scale),
                             ("image", image), ("mask_image", mask_image), ("control_image", control_image),
